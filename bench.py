@@ -18,6 +18,8 @@ Rank 0 prints ONE JSON line:
     640x640, inference 1152x1920 N=32, the gradient exchange at world size 1, the three head-only fine-tuning phases;
   * cpu_baseline: the fp32 oracle (a port, oracle/hydranet_oracle.py) timed on this box's host cores on a bounded sample;
   * env_overrides: every HN_* environment variable that was set (tools/ hooks change what runs; none of them skips work in the timed region).
+--dump-outputs DIR writes what the last timed step computed (dump_outputs / step_outputs) and lists it in the line as dumped_outputs: the
+inputs and the initial weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import contextlib
@@ -419,6 +421,42 @@ def median(v):
     return v[len(v) // 2] if v else None
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: write every {name: tensor} as out_dir/<name>.npy (float64 stays float64, anything else becomes float32), within
+    `budget` bytes in all, so that two builds can be compared output for output on the same seeded inputs.  The smallest arrays go first and
+    are written whole; an array larger than its share of what is left is written as a flat sample of that share: indices drawn by
+    torch.randint with torch.Generator().manual_seed(seed), sorted -- the same positions in every run with the same shapes.
+    -> {name: {"shape": full shape, "written": elements written}} for the JSON line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(((k, v.detach()) for k, v in arrays.items() if v is not None), key=lambda kv: kv[1].numel())
+    left = budget - 256 * len(items)                  # (room for each file's .npy header)
+    rec = {}
+    for i, (name, t) in enumerate(items):
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        cap = max(1, left // (len(items) - i) // t.element_size())
+        a = t
+        if t.numel() > cap:
+            idx = torch.randint(t.numel(), (cap,), generator=torch.Generator().manual_seed(seed)).sort().values
+            a = t.reshape(-1)[idx.to(t.device)]
+        a = a.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+        rec[name] = {"shape": list(t.shape), "written": int(a.size)}
+    return rec
+
+
+def step_outputs(net, loss):
+    """what a caller of the training step receives: the total loss and every parameter's .grad (named_parameters order; parameters without a
+    gradient left out) -> {loss, grad_norms: per-parameter L2 norms in float64, grads: all gradients flattened into one vector}"""
+    grads = [p.grad for _, p in net.named_parameters() if p.grad is not None]
+    return {"loss": loss.detach().float(), "grad_norms": torch.stack([g.double().norm() for g in grads]),
+            "grads": torch.cat([g.float().reshape(-1) for g in grads])}
+
+
 def build_net(cfg_path, h, w, dev):
     from multitask_hydranet_amd import HydraNet
     cfgs = yaml.safe_load(open(cfg_path))
@@ -448,21 +486,28 @@ def infer_measure(net, batch_n, h, w, dev, steps, warmup, use_graph=True, world=
     x = torch.randn(batch_n, 3, h, w, generator=g).to(dev)
     with torch.no_grad():
         fn = lambda: net(x, "deploy")
+        last = [None]                       # the outputs of the last timed step (a captured graph rewrites the same tensors every replay)
         if use_graph:
-            graph, out = capture(fn)
+            graph, last[0] = capture(fn)
             step = graph.replay
         else:
-            graph, out = None, fn()
-            step = fn
+            graph, last[0] = None, fn()
+
+            def step():
+                last[0] = fn()
         dt, per = time_replays(step, steps, warmup, world)
+    out = last[0]
     assert bool(torch.isfinite(out[2]).all()) and out[0].dtype == torch.int64
-    return dt, per, graph is not None
+    return dt, per, graph is not None, out
 
 
 def infer_bench(args, net, cfgs, h, w, dev, rank, world):
     """BASELINE config 5: inference-only deploy forward (seg arg-max + detection / lane head outputs), batch per GPU, replicas only (no
     collective on the data path).  One captured hipGraph per step; BatchNorm folded into the packed weights (HydraNet.prepare_inference)."""
-    dt, per, graphed = infer_measure(net, args.batch, h, w, dev, args.steps, args.warmup, not args.no_graph, world, seed=1 + rank)
+    dt, per, graphed, out = infer_measure(net, args.batch, h, w, dev, args.steps, args.warmup, not args.no_graph, world, seed=1 + rank)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, dict(zip(("seg_mask", "anchors", "regression", "classification", "lane_cls", "lane_loc"), out)))
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -481,6 +526,8 @@ def infer_bench(args, net, cfgs, h, w, dev, rank, world):
                       "parallelism": "replicas x%d (no collective)" % world, "hipgraph": graphed,
                       "padding": "1080-row frames are zero-padded (post-normalisation) by 36 rows top and bottom to 1152 = 9 x 128"},
            "model_tflops": round(value * FWD_GFLOP_PER_IMG_512x1024 * scale / 1e3, 2), "env_overrides": env_overrides()}
+    if dumped is not None:
+        res["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     try:
         res["roofline"] = dominant_launch_roofline(net, args.batch, h, w)
     except Exception as e:      # noqa: BLE001
@@ -819,7 +866,7 @@ def extra_configs(args, dev, headline_net, headline_cfgs):
 
     def infer():
         net, cfgs = build_net(args.cfg, 1152, 1920, dev)
-        dt, per, graphed = infer_measure(net, 32, 1152, 1920, dev, K_STEPS, K_WARM)
+        dt, per, graphed, _ = infer_measure(net, 32, 1152, 1920, dev, K_STEPS, K_WARM)
         return {"value": round(32 * K_STEPS / dt, 2), "unit": "images/sec", "ms_per_step": round(dt / K_STEPS * 1e3, 3),
                 "ms_per_step_median": round(median(per), 3), "steps": K_STEPS, "warmup": K_WARM, "batch": 32, "resolution": "3x1152x1920",
                 "hipgraph": graphed, "workload": "BASELINE config 5: eval-mode deploy forward, BatchNorm folded, 1080-row frames zero-padded to 1152"}
@@ -903,7 +950,14 @@ def main():
                     "the exchange in its OTHER form (forked onto the side stream instead of in line); a second capture of RCCL collectives in "
                     "one process, guarded by a watchdog (exit code 4 on a wedge)")
     ap.add_argument("--phase", default=None, choices=("lane", "det", "seg"), help="head-only fine-tuning phase (train.py:441-515)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step computed as "
+                    "DIR/<name>.npy (float32 / float64, at most 64 MB in all: a larger output is written as a fixed, seeded sample). "
+                    "Training step: loss, grad_norms, grads; --infer: the deploy outputs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     h, w = (int(v) for v in args.res.split("x"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -973,13 +1027,17 @@ def main():
     run = TrainRun(net, cfgs, batch, dev, rank, world, backend, backbone_only=args.backbone_only, use_graph=not args.no_graph,
                    exchange=exchange, force_world1=args.ddp_world1, payload=payload, exchange_after_replay=args.exchange_after_replay)
 
+    last = [None]                                    # the loss of the last timed step
+
     def step():
-        loss = run.step()
+        loss = last[0] = run.step()
         if os.environ.get("HN_BENCH_DEBUG"):
             print("rank", rank, "loss", float(loss.detach()), file=sys.stderr, flush=True)
         return loss
     dt, per = time_replays(step, args.steps, args.warmup, world)
-    loss = run.static_loss if run.graph is not None else step()
+    loss = last[0]
+    # (written before anything below replaces the parameters' .grad: the exposed-exchange capture and the segment table reset them)
+    dumped = dump_outputs(args.dump_outputs, step_outputs(net, loss)) if args.dump_outputs and rank == 0 else None
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
     per_rank_ms = [round(dt / args.steps * 1e3, 3)]
     if world > 1:
@@ -1073,6 +1131,8 @@ def main():
             "step_roofline": {"floor_ms_per_img": round(0.177 * scale, 4), "frac": round(value / world * 0.177e-3 * scale, 4)},
             "env_overrides": env_overrides(),
         }
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if not args.no_roofline:
             try:
                 # top-level fields = the dominant kernel by FLOPs (the contract's single entry); the same object again as

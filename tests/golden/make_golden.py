@@ -265,6 +265,7 @@ def big_digest(cond=False):
         assert cfgs[sec] == ours[sec], sec
     h = w = 640
     assert cfgs["dataloader"]["network_input_height"] == h and cfgs["dataloader"]["network_input_width"] == w
+    torch.set_num_threads(8)                        # = tests/test_oracle_golden.py DIGEST_THREADS: the fp32 sums depend on the thread count
     torch.manual_seed(0)
     net = HydraNet(cfgs)
     keys = list(net.state_dict().keys())

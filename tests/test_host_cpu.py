@@ -296,6 +296,41 @@ def test_live_traffic_sampling_fails_soft():
     assert bench.measured_traffic(8, 512, 1024, "phase") == (None, None)
 
 
+def test_bench_dump_outputs_budget_dtypes_and_sample(tmp_path):
+    """bench.py --dump-outputs (dump_outputs / step_outputs on host tensors): float32 / float64 files only, at most 64 MB in all, small arrays
+    whole and in shape, a larger one as the documented seeded sample -- the same positions in every run; --steps 0 is refused"""
+    import subprocess
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    big = torch.randn(20_000_000, generator=g)
+    arrays = {"loss": torch.tensor(3.5), "norms": torch.rand(700, dtype=torch.float64, generator=g),
+              "mask": torch.randint(0, 5, (2, 64, 64), generator=g), "grads": big, "absent": None}
+    recs = [bench.dump_outputs(str(tmp_path / d), arrays) for d in ("a", "b")]
+    assert recs[0] == recs[1] and set(recs[0]) == {"loss", "norms", "mask", "grads"}
+    for d in ("a", "b"):
+        assert sum(os.path.getsize(f) for f in (tmp_path / d).iterdir()) <= bench.DUMP_BUDGET_BYTES == 64 * 10 ** 6
+    z = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in recs[0]}
+    assert z["loss"].dtype == np.float32 and float(z["loss"]) == 3.5
+    assert z["norms"].dtype == np.float64 and np.array_equal(z["norms"], arrays["norms"].numpy())
+    assert z["mask"].dtype == np.float32 and np.array_equal(z["mask"], arrays["mask"].float().numpy())
+    n = recs[0]["grads"]["written"]
+    assert recs[0]["grads"]["shape"] == [20_000_000] and 10_000_000 < n < 16_000_000 and z["grads"].shape == (n,)
+    idx = torch.randint(big.numel(), (n,), generator=torch.Generator().manual_seed(0)).sort().values
+    assert np.array_equal(z["grads"], big[idx].numpy()) and np.array_equal(z["grads"], np.load(tmp_path / "b" / "grads.npy"))
+    # step_outputs: the loss and every parameter gradient, in named_parameters order
+    lin = torch.nn.Sequential(torch.nn.Linear(3, 4), torch.nn.Linear(4, 2, bias=False))
+    loss = lin(torch.randn(5, 3, generator=g)).square().sum()
+    loss.backward()
+    so = bench.step_outputs(lin, loss)
+    grads = [p.grad for p in lin.parameters()]
+    assert float(so["loss"]) == float(loss.detach()) and so["grad_norms"].dtype == torch.float64
+    assert torch.allclose(so["grad_norms"], torch.stack([q.double().norm() for q in grads]))
+    assert torch.equal(so["grads"], torch.cat([q.reshape(-1) for q in grads]))
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--steps" in r.stderr and not r.stdout.strip()
+
+
 def test_policy_switches_are_constants_without_the_tuning_flag():
     """the package reads no HN_* environment variable unless HN_TUNING=1 / ab is set (_lib.policy): a stray HN_FUSED_BN=0
     or HN_LIB_AB in a user's environment must not change what the product runs"""

@@ -147,6 +147,46 @@ def test_rccl_gradient_exchange_world1_in_graph():
     assert "bfloat16" in ddp16["config"]["grad_allreduce"]
 
 
+def test_bench_dump_outputs_are_what_the_last_timed_step_computed():
+    """bench.py --dump-outputs DIR: the training step's loss and gradients, and the --infer deploy outputs, as float32 / float64 .npy files of
+    at most 64 MB in all.  Inputs and initial weights are seeded and the step is deterministic, so two runs with different numbers of timed
+    steps write identical files; ms_per_step is the time of one of the --steps timed steps (value = batch / ms_per_step)."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    if not torch.cuda.is_available():
+        pytest.skip("needs the MI355X")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--no-optimizer", "--no-extras", "--no-roofline", "--warmup", "1"]
+    runs = []
+    with tempfile.TemporaryDirectory() as d:
+        for steps, batch, extra in ((2, 2, ["--res", "256x512"]), (3, 2, ["--res", "256x512"]), (2, 32, ["--infer", "--res", "1152x1920"])):
+            out = os.path.join(d, str(len(runs)))
+            r = subprocess.run(base + extra + ["--steps", str(steps), "--batch", str(batch), "--dump-outputs", out], capture_output=True,
+                               text=True, timeout=600)
+            assert r.returncode == 0, r.stderr[-2000:]
+            o = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
+            assert o["steps"] == steps and abs(o["value"] * o["ms_per_step"] / 1e3 - batch) <= 0.01 * batch
+            files = sorted(os.listdir(out))
+            assert files == sorted(n + ".npy" for n in o["dumped_outputs"]["arrays"])
+            assert sum(os.path.getsize(os.path.join(out, f)) for f in files) <= 64 * 10 ** 6
+            z = {f[:-4]: np.load(os.path.join(out, f)) for f in files}
+            assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in z.values())
+            runs.append((o, z))
+    (o, z), (o3, z3), (oi, zi) = runs
+    assert set(z) == {"loss", "grad_norms", "grads"} and z["grad_norms"].dtype == np.float64 and z["grad_norms"].shape == (693,)
+    assert round(float(z["loss"]), 4) == o["loss"]
+    g = o["dumped_outputs"]["arrays"]["grads"]
+    assert g["shape"][0] > g["written"] == z["grads"].size                # 42.7 M gradients: a seeded sample
+    for k in z:
+        assert np.array_equal(z[k], z3[k]), k
+    assert set(zi) == {"seg_mask", "anchors", "regression", "classification", "lane_cls", "lane_loc"}
+    assert np.array_equal(zi["seg_mask"], np.round(zi["seg_mask"])) and zi["seg_mask"].min() >= 0 and zi["seg_mask"].max() < 5
+    anchors = sum((1152 >> s) * (1920 >> s) for s in (3, 4, 5, 6, 7)) * 9
+    assert oi["dumped_outputs"]["arrays"]["classification"]["shape"] == [32, anchors, 9]
+
+
 def test_two_rank_control_flow_on_one_gpu():
     """the N > 1 launch contract of bench.py (torch.distributed.run, one process per rank, barrier + max-over-ranks timing, rank 0 prints
     the JSON line) with the two test hooks that make it runnable on a 1-GPU box: both ranks on cuda:0, gloo instead of RCCL (which refuses
