@@ -495,6 +495,19 @@ int hn_seg_focal_fwd(const float* logits, int ldl, int C, const void* target, in
                      float alpha, int N, long HW, void* ws, float* out, hipStream_t stream);
 int hn_seg_focal_bwd(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* class_weights, float gamma,
                      float alpha, int N, long HW, const float* gout, float* dlogits, int ldd, hipStream_t stream);
+/* Lovasz-softmax variant of the seg loss (segment.use_lovasz: head_seg/loss_lovasz.py lovasz_softmax(softmax(logits), gt, ignore=255),
+ * classes='present', per_image=False; hn_lovasz.hip).  logits fp32 [N*HW][ldl], target int64 / float32 class ids; labels == ignore_index
+ * are dropped, other labels outside [0, C) are background for every class.  Per-class sort order: error descending, then pixel index
+ * ascending (deterministic; the reference's unstable sort leaves ties unspecified).  2 <= C <= 16.  ws: hn_seg_lovasz_ws_bytes(N, HW, C)
+ * bytes, written by fwd and read by bwd (per-pixel gradient w.r.t. the probabilities, class counts).  out[0] = loss (0 when no class is
+ * present); bwd writes dlogits (fp32, row stride ldd), bwd_s2d the space-to-depth bf16 operand of hn_seg_loss_bwd_s2d's layout. */
+long hn_seg_lovasz_ws_bytes(int N, long HW, int C);
+int hn_seg_lovasz_fwd(const float* logits, int ldl, int C, const void* target, int target_is_float, int ignore_index, int N, long HW,
+                      void* ws, float* out, hipStream_t stream);
+int hn_seg_lovasz_bwd(const float* logits, int ldl, int C, const void* target, int target_is_float, int ignore_index, int N, long HW,
+                      const void* ws, const float* gout, float* dlogits, int ldd, hipStream_t stream);
+int hn_seg_lovasz_bwd_s2d(const float* logits, int ldl, int C, const void* target, int target_is_float, int ignore_index, int N, int H,
+                          int W, const void* ws, const float* gout, void* dz, int ldz, hipStream_t stream);
 /* Detection loss (FocalLoss.forward, head_detect/detection_loss.py:132-267): cls fp32 [N][A][K] (post-sigmoid), reg [N][A][4], anchors
  * [A][4] (y1,x1,y2,x2), ann [N][Mx][5] (x1,y1,x2,y2,class; rows with class -1 are padding).  out[0] / out[1] = batch-mean classification /
  * regression loss.  assign: int16 [N][A]; part: fp32 [N][hn_det_loss_blocks(A)][3]; npos: fp32 [N] (all written by fwd, read by bwd). */

@@ -139,8 +139,7 @@ class HydraNet(nn.Module):
         if self.train_seg:
             self._declare_seg(spec)
             s = cfgs["segment"]
-            self.use_lovasz = s["use_lovasz"]
-            assert not self.use_lovasz, "Lovasz loss is off in every shipped cfg and outside the hot path"
+            self.use_lovasz = bool(s["use_lovasz"])          # Lovasz-softmax wins over use_top_k / use_focal / class_weight (model.py:119-126)
             # device-resident copy of the class weights (non-persistent: not part of the reference's state_dict)
             self.register_buffer("_seg_class_weight", torch.tensor(s["class_weight"], dtype=torch.float32), persistent=False)
             self._seg_cfg = (s["use_top_k"], s["top_k_ratio"], s["use_focal"])
@@ -841,10 +840,14 @@ class HydraNet(nn.Module):
 
     def _seg_loss(self, logits, target):
         """CrossEntropyLoss.forward (head_seg/segmentation_loss.py:27-65) on HIP kernels: the weighted-CE / top-k path of the big cfgs
-        (hn_seg_loss_*) and the focal variant of the small cfg (hn_seg_focal_*).  No CPU fallback: raises off-device."""
+        (hn_seg_loss_*) and the focal variant of the small cfg (hn_seg_focal_*); with use_lovasz the Lovasz-softmax loss instead
+        (lovasz_softmax(F.softmax(seg, 1), gt, ignore=255), model.py:207-210; hn_seg_lovasz_*).  No CPU fallback: raises off-device."""
         use_top_k, ratio, use_focal = self._seg_cfg
         key = getattr(self, "_seg_grad_slot", None)
         self._seg_grad_slot = None                                    # consumed (or dropped) by the first loss call after the forward
+        if self.use_lovasz:
+            slot = key[0] if (key is not None and key[1]() is logits) else None
+            return K.seg_lovasz_loss_hip(logits, target, ignore_index=255, slot=slot)
         if use_focal:
             # (the reference always hands gt_seg.long() to the loss, model.py:212; to_gpu delivers float32 class ids: both are accepted)
             return K.seg_focal_loss_hip(logits, target, self._seg_class_weight)

@@ -107,6 +107,53 @@ def seg_focal_loss_hip(seg_nchw, target, class_weights, gamma=2.0, alpha=1.0):
     return SegFocalLoss.apply(logits, target.contiguous(), class_weights, gamma, alpha)
 
 
+class SegLovaszLoss(torch.autograd.Function):
+    """Lovasz-softmax variant of the seg loss (head_seg/loss_lovasz.py lovasz_softmax on softmax(logits), classes='present', per_image=False):
+    logits fp32 NHWC [N, H, W, C] (dense rows), target [N, H, W] int64 or float32 class ids.  The per-class sorts, weights and per-pixel
+    gradient live in the workspace the backward reads (hn_lovasz.hip)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, slot=None):
+        """slot: GradSlot of the producing SegOutUp node, as for SegLoss (hn_seg_lovasz_bwd_s2d hands the gradient over in its operand form)"""
+        n, h, w, c = logits.shape
+        hw = h * w
+        ctx.slot = slot if (slot is not None and h % 2 == 0 and w % 2 == 0) else None
+        ctx.hw_dims = (h, w)
+        dev = logits.device
+        ws = torch.empty((lib().query("hn_seg_lovasz_ws_bytes", n, hw, c),), device=dev, dtype=torch.uint8)
+        out = torch.empty((1,), device=dev, dtype=F32)
+        tf = 1 if target.dtype == torch.float32 else 0
+        assert target.dtype in (torch.float32, torch.int64) and target.is_contiguous()
+        lib().call("hn_seg_lovasz_fwd", ptr(logits), logits.stride(2), c, ptr(target), tf, ignore_index, n, hw, ptr(ws), ptr(out))
+        ctx.meta = (n, hw, c, tf, ignore_index)
+        ctx.save_for_backward(logits, target, ws)
+        return out.view(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, target, ws = ctx.saved_tensors
+        n, hw, c, tf, ign = ctx.meta
+        g = gout.contiguous().to(F32).view(1)
+        if ctx.slot is not None and ctx.slot.buf is None:
+            h, w = ctx.hw_dims
+            dz = new_act(n, h // 2, w // 2, pad8(4 * c), logits.device)
+            lib().call("hn_seg_lovasz_bwd_s2d", ptr(logits), logits.stride(2), c, ptr(target), tf, ign, n, h, w, ptr(ws), ptr(g), ptr(dz), ld(dz))
+            ctx.slot.buf = dz
+            return None, None, None, None
+        dl = torch.empty_like(logits)
+        lib().call("hn_seg_lovasz_bwd", ptr(logits), logits.stride(2), c, ptr(target), tf, ign, n, hw, ptr(ws), ptr(g), ptr(dl), dl.stride(2))
+        return dl, None, None, None
+
+
+def seg_lovasz_loss_hip(seg_nchw, target, ignore_index=255, slot=None):
+    """model.py cal_loss with use_lovasz: lovasz_softmax(F.softmax(seg, 1), gt_seg.long(), ignore=255).  seg_nchw: the module's "seg"
+    output (fp32, NCHW-shaped view of NHWC memory); slot as for seg_loss_hip."""
+    logits = seg_nchw.permute(0, 2, 3, 1)
+    if not logits.is_contiguous():
+        logits, slot = logits.contiguous(), None
+    return SegLovaszLoss.apply(logits, target.contiguous(), ignore_index, slot)
+
+
 def argmax_channels(seg_nchw):
     logits = seg_nchw.permute(0, 2, 3, 1)
     if not logits.is_contiguous():

@@ -136,6 +136,52 @@ def _ce_backward(ctx, gloss, gws_unused):
 seg_topk_ce_fwd.register_autograd(_ce_backward, setup_context=_ce_setup)
 
 
+# ---- Lovasz-softmax seg loss (head_seg/loss_lovasz.py lovasz_softmax on softmax(logits), classes='present', ignore=255) ------------------
+@torch.library.custom_op(f"{NS}::seg_lovasz_fwd", mutates_args=(), device_types="cuda")
+def seg_lovasz_fwd(logits: Tensor, target: Tensor, ignore_index: int) -> Tuple[Tensor, Tensor]:
+    """logits fp32 NHWC [N,H,W,C] dense, target int64|float32 [N,H,W] -> (loss [], workspace kept for backward)"""
+    n, h, w, c = logits.shape
+    hw = h * w
+    ws = torch.empty((lib().query("hn_seg_lovasz_ws_bytes", n, hw, c),), device=logits.device, dtype=torch.uint8)
+    out = torch.empty((1,), device=logits.device, dtype=torch.float32)
+    lib().call("hn_seg_lovasz_fwd", logits.data_ptr(), logits.stride(2), c, target.data_ptr(), 1 if target.dtype == torch.float32 else 0,
+               ignore_index, n, hw, ws.data_ptr(), out.data_ptr())
+    return out.view(()), ws
+
+
+@seg_lovasz_fwd.register_fake
+def _(logits, target, ignore_index):
+    return logits.new_empty(()), logits.new_empty((1,), dtype=torch.uint8)
+
+
+@torch.library.custom_op(f"{NS}::seg_lovasz_bwd", mutates_args=(), device_types="cuda")
+def seg_lovasz_bwd(gout: Tensor, logits: Tensor, target: Tensor, ws: Tensor, ignore_index: int) -> Tensor:
+    n, h, w, c = logits.shape
+    dl = torch.empty_like(logits)
+    g = gout.contiguous().to(torch.float32).view(1)
+    lib().call("hn_seg_lovasz_bwd", logits.data_ptr(), logits.stride(2), c, target.data_ptr(), 1 if target.dtype == torch.float32 else 0,
+               ignore_index, n, h * w, ws.data_ptr(), g.data_ptr(), dl.data_ptr(), dl.stride(2))
+    return dl
+
+
+@seg_lovasz_bwd.register_fake
+def _(gout, logits, target, ws, ignore_index):
+    return torch.empty_like(logits)
+
+
+def _lovasz_setup(ctx, inputs, output):
+    logits, target, ctx.ignore = inputs
+    ctx.save_for_backward(logits, target, output[1])
+
+
+def _lovasz_backward(ctx, gloss, gws_unused):
+    logits, target, ws = ctx.saved_tensors
+    return torch.ops.hydranet_hip.seg_lovasz_bwd(gloss, logits, target, ws, ctx.ignore), None, None
+
+
+seg_lovasz_fwd.register_autograd(_lovasz_backward, setup_context=_lovasz_setup)
+
+
 # ---- inference-side ops (no gradient) ------------------------------------------------------------------------------------------------
 @torch.library.custom_op(f"{NS}::argmax_channels", mutates_args=(), device_types="cuda")
 def argmax_channels(logits: Tensor) -> Tensor:
