@@ -3148,8 +3148,7 @@ __global__ __launch_bounds__(256) void pack_small_batched_kernel(const long* job
 // ---------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------
-static XSrc make_xsrc(const void* x0, const void* x1, int mode, int n_img, int H, int W, int C0, int C1, int ld0, int ld1,
-                      int up, long M) {
+static XSrc make_xsrc(const void* x0, const void* x1, int mode, int H, int W, int C0, int C1, int ld0, int ld1, int up, long M) {
     XSrc s;
     s.x0 = (const bf16*)x0;
     s.x1 = (const bf16*)x1;
@@ -3163,7 +3162,6 @@ static XSrc make_xsrc(const void* x0, const void* x1, int mode, int n_img, int H
     if (mode == 3) { s.Hi = H - 2; s.Wi = W - 2; }
     s.C0 = C0; s.C1 = C1; s.ld0 = ld0; s.ld1 = ld1; s.up = up;
     s.M = M;
-    (void)n_img;
     return s;
 }
 
@@ -3234,20 +3232,13 @@ static constexpr int g_nt_force_bc = 0, g_nt_force_r = 0;
 #endif
 
 // Ring depth: R = 2 (double buffer) in production; R = 3/4 stay instantiated behind the tuning hook.
-template <int BC, int BP, int WGC, int WGP, int RDEEP>
+template <int BC, int BP, int WGC, int WGP>
 static int launch_nt(const GemmNT& p, int out_f32, hipStream_t st) {
-    const long blocks = (long)cdiv(p.x.M, BP) * cdiv(p.Nout, BC);
-    const int stages = (p.taps * (p.KP >> 5) + 1) >> 1;
-    int r = 2;     // measured: the deeper rings never beat the double buffer (their LDS footprint costs the second resident workgroup)
-    (void)blocks; (void)stages;
+    // measured: the deeper rings never beat the double buffer (their LDS footprint costs the second resident workgroup)
 #ifdef HN_TUNING
-    if (g_nt_force_r && BC >= 32) r = g_nt_force_r;
-    if (BC >= 32) {
-        if (r == 3) return launch_nt_r<BC, BP, WGC, WGP, (BC >= 32 ? 3 : 2)>(p, out_f32, st);
-        if (r == 4) return launch_nt_r<BC, BP, WGC, WGP, (BC >= 32 ? 4 : 2)>(p, out_f32, st);
-    }
+    if (BC >= 32 && g_nt_force_r == 3) return launch_nt_r<BC, BP, WGC, WGP, (BC >= 32 ? 3 : 2)>(p, out_f32, st);
+    if (BC >= 32 && g_nt_force_r == 4) return launch_nt_r<BC, BP, WGC, WGP, (BC >= 32 ? 4 : 2)>(p, out_f32, st);
 #endif
-    (void)r;
     return launch_nt_r<BC, BP, WGC, WGP, 2>(p, out_f32, st);
 }
 
@@ -3286,26 +3277,209 @@ extern "C" int hn_nt_stat_rows(long M, int Nout) {               // one partial 
 }
 extern "C" int hn_nt_stat_tile(long M, int Nout) { return small_tile(M, Nout) ? 64 : 128; }   // pixel rows per partial row (the last tile may be ragged)
 
-struct NextStat { int mode; const bf16* z; int ldz; const float* coef; const bf16* y; int ldy; };
-static thread_local NextStat g_next_stat = {0, nullptr, 0, nullptr, nullptr, 0};   // set by hn_conv_gemm_nt_stat for the launch it makes
-struct NextFold { bf16* ring; const bf16* y; int ldy; int form; bf16* out2; int ld2; };   // form: GemmNT::fold (1 plain, 2 space-to-depth, 3 both)
-static thread_local NextFold g_next_fold = {nullptr, nullptr, 0, 0, nullptr, 0};   // set by hn_conv3x3_dgrad_fold for the launch it makes
-static thread_local long* g_next_amax = nullptr;    // set by hn_conv3x3_out_argmax for the launch it makes (same thread, same call)
-struct NextImgW { long stride; long rpi; };
-static thread_local NextImgW g_next_imgw = {0, 0};  // set by hn_conv_gemm_nt_imgw for the launch it makes
-struct NextLvl { const float* coef; int n; long row[HN_MAX_LEVELS + 1]; int nimg; unsigned hw[HN_MAX_LEVELS]; unsigned pix[HN_MAX_LEVELS]; };
-static thread_local NextLvl g_next_lvl = {nullptr, 0, {0}, 0, {0}, {0}};   // set by hn_conv_gemm_nt_lvl for the launch it makes
-static int conv_gemm_nt_impl(const void* x0, const void* x1, int mode, int n_img, int H, int W, int C0, int C1, int ld0, int ld1,
-                             int up, long M, const void* w, int Nout, int KP, int taps, const float* bias, int act, void* out,
-                             int out_f32, int ldc, long rpi, long img_stride, float* psum, float* psq, const float* xscale,
-                             const float* xshift, const float* xgate, long xhw, int xact, const void* addend, int ld_add, int add_mode,
-                             int phase_mode, int phase_span, hipStream_t st);
+static bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+
+// The launch description every NT entry point starts from; the entry point then sets its own epilogue / operand options on it and
+// hands it to run_gemm_nt.
+static GemmNT nt_desc(const XSrc& x, const void* w, int Nout, int KP, int taps, const float* bias, int act, void* out, int ldc) {
+    GemmNT p{};
+    p.x = x;
+    p.w = (const bf16*)w; p.Nout = Nout; p.KP = KP; p.taps = taps;
+    p.bias = bias; p.act = act; p.out = out; p.ldc = ldc;
+    return p;
+}
+
+// plain pixel rows (mode 0, one tap)
+static GemmNT nt_rows(const void* x0, int ld0, long M, int C0, const void* w, int Nout, int KP, const float* bias, int act, void* out, int ldc) {
+    return nt_desc(make_xsrc(x0, nullptr, 0, 0, 0, C0, 0, ld0, 0, 0, M), w, Nout, KP, 1, bias, act, out, ldc);
+}
+
+// the arguments hn_conv_gemm_nt, _ex and _stat share; img_stride = -k (mode 4) is the ABI's request for the depth-to-space store of
+// k channels per output pixel (GemmNT::d2s)
+static GemmNT nt_conv(const void* x0, const void* x1, int mode, int H, int W, int C0, int C1, int ld0, int ld1, int up, long M, const void* w,
+                      int Nout, int KP, int taps, const float* bias, int act, void* out, int ldc, long rpi, long img_stride, float* psum,
+                      float* psq) {
+    GemmNT p = nt_desc(make_xsrc(x0, x1, mode, H, W, C0, C1, ld0, ld1, up, M), w, Nout, KP, taps, bias, act, out, ldc);
+    p.rpi = rpi; p.psum = psum; p.psq = psq;
+    if (img_stride < 0) p.d2s = (int)(-img_stride);
+    else p.img_stride = img_stride;
+    return p;
+}
+
+// the addend of hn_conv_gemm_nt_ex / _stat: ld_add < 0 = row stride -ld_add, added BEFORE the activation
+static void nt_addend(GemmNT& p, const void* addend, int ld_add, int add_mode) {
+    p.addend = (const bf16*)addend;
+    p.ld_add = ld_add < 0 ? -ld_add : ld_add;
+    p.add_pre = ld_add < 0 ? 1 : 0;
+    p.add_s2 = add_mode;
+}
+
+// Direct 3x3 kernels (modes 2..5): the persistent seg-head forms where they apply, else conv3x3_direct_kernel
+static int launch_direct(GemmNT& p, int n_img, bool out_f32, hipStream_t st) {
+    const XSrc& x = p.x;
+    const long npatch = (long)cdiv(x.W, 16) * cdiv(x.H, 16) * n_img;
+    // the last decoder block's phase-form conv (64 -> 4 x 64): the persistent form, one phase per workgroup
+    if (x.clamp == 1 && !x.diag && !out_f32 && p.d2s == 64 && p.phase_mode == 1 && p.phase_span == 64 && p.taps == 9 && p.KP == 64 && x.C0 == 64 &&
+        x.C1 == 0 && p.Nout == 256 && !p.psum && !p.addend && (p.act == HN_ACT_ELU || p.act == HN_ACT_NONE) && (x.ld0 & 7) == 0 &&
+        (p.ldc & 7) == 0 && p.ldc >= 64 && aligned16(p.out) && g_hn_knob[11] != 3 && npatch >= 1024) {
+        SegPhase q;
+        q.x = x.x0; q.ldx = x.ld0; q.N = n_img; q.H = x.H; q.W = x.W; q.w = p.w; q.bias = p.bias; q.out = (bf16*)p.out; q.ldc = p.ldc;
+        q.act = p.act; q.npatch = (int)npatch;
+        q.ppw = cdiv(npatch, 64);                                      // 64 patch ranges x 4 phases = 256 workgroups
+        const int grid = 4 * cdiv(npatch, q.ppw);
+        const size_t lds = 2 * (size_t)((18 * 18 * 8 + 63) / 64) * 1024 + 256 * 128;
+        static std::atomic<unsigned long long> optin_sp{0};
+        if (!lds_optin(optin_sp, {(const void*)seg_phase64_conv_kernel})) return HN_ERR_LAUNCH;
+        hipLaunchKernelGGL(seg_phase64_conv_kernel, dim3(grid), dim3(512), lds, st, q);
+        HN_LAUNCH_CHECK();
+    }
+    // the seg output conv on a map big enough to give every CU several patches: the persistent form with the weights in registers
+    if (x.clamp == 1 && !x.diag && out_f32 && p.d2s && p.taps == 9 && p.KP == 64 && x.C0 == 64 && x.C1 == 0 && p.Nout == 4 * p.d2s &&
+        p.Nout <= 32 && !p.psum && !p.addend && p.phase_mode == 0 && p.act == HN_ACT_NONE && (x.ld0 & 7) == 0 && ((32 * p.d2s) & 3) == 0 &&
+        ((2 * x.W * p.d2s) & 3) == 0 && aligned16(p.out) && g_hn_knob[11] != 3 && npatch >= 1024) {
+        SegOut q;
+        q.x = x.x0; q.ldx = x.ld0; q.N = n_img; q.H = x.H; q.W = x.W; q.w = p.w; q.Nout = p.Nout; q.k = p.d2s; q.bias = p.bias;
+        q.out = p.amax ? nullptr : (float*)p.out; q.amax = p.amax; q.npatch = (int)npatch;
+        q.ppw = cdiv(npatch, 256);
+        const int grid = cdiv(npatch, q.ppw);
+        const size_t lds = 2 * (size_t)((18 * 18 * 8 + 63) / 64) * 1024 + (size_t)32 * 32 * p.d2s * 4;
+        static std::atomic<unsigned long long> optin_so{0};
+        if (!lds_optin(optin_so, {(const void*)seg_out_conv_kernel<true>, (const void*)seg_out_conv_kernel<false>})) return HN_ERR_LAUNCH;
+        if (p.amax) hipLaunchKernelGGL(seg_out_conv_kernel<true>, dim3(grid), dim3(512), lds, st, q);
+        else hipLaunchKernelGGL(seg_out_conv_kernel<false>, dim3(grid), dim3(512), lds, st, q);
+        HN_LAUNCH_CHECK();
+    }
+    HN_CHECK_ARG(x.Wi < 8192 && x.Hi < 32768);      // packed patch coordinates of the direct kernel
+    int bc = x.diag ? 64 : (p.Nout <= 16 ? 16 : (p.Nout <= 32 ? 32 : (p.Nout <= 64 ? 64 : 128)));
+    if (p.phase_mode == 1 && p.phase_span < bc) bc = 64;          // a cout tile must lie inside one phase
+    // bf16 tiles of >= 64 couts leave through the LDS-staged epilogue only (whole 16-byte pieces of aligned rows)
+    const bool staged_ok = (p.ldc & 7) == 0 && (p.Nout & 7) == 0 && aligned16(p.out) && (!p.d2s || ((p.d2s & 7) == 0 && p.Nout % bc == 0));
+    if (bc >= 64 && !out_f32 && !staged_ok) {       // (odd channel counts / unaligned slices: the 32-cout tile keeps the generic epilogue)
+        if (x.diag) return HN_ERR_UNSUPPORTED;
+        bc = 32;
+    }
+    dim3 grid((unsigned)(cdiv(p.Nout, bc) * cdiv(x.W, 16) * cdiv(x.H, 16) * n_img));
+    // preloaded form: one chunk, all its tap tiles (<= 16) in at most 32 KB next to the patch (two or three workgroups per CU as before)
+    const int nsteps = p.phase_mode ? 4 : 9;
+    p.wpre = (!x.diag && p.KP <= 64 && (size_t)nsteps * bc * 128 <= 32768 && g_hn_knob[11] != 2) ? 1 : 0;
+    // software-pipelined variant (32-channel chunks, two patch buffers + ring of four weight tiles, counted waits; still two workgroups
+    // per CU): the multi-chunk bf16 launches with >= 64 couts per tile
+    // (the multi-chunk form measured slower on every seg-decoder shape: tools/bench_seg.py; tuning builds can force it)
+    // K <= 32 channels per tap in ONE chunk (the output layer's data gradient: 24 real channels of a 64-channel chunk): 32-channel
+    // chunks halve the MFMAs, LDS fragment reads and weight DMA of a tap step, and with a single patch buffer (24 KB) + the ring of
+    // four weight tiles (32 KB) two workgroups share a CU
+    const bool narrow = bc == 64 && !out_f32 && !x.diag && !p.wpre && p.KP <= 32 && nsteps == 9 && g_hn_knob[18] == 0;
+    if (narrow) p.wpre = 1;                                     // all nine 4 KB tap tiles next to the patch: no barrier in the tap loop
+#ifdef HN_TUNING
+    const bool pipe = narrow || (g_direct_pipe && bc >= 64 && !out_f32 && !x.diag && !p.wpre && p.KP > 64);
+#else
+    const bool pipe = narrow;
+#endif
+    const size_t lds = narrow ? (size_t)(((18 * 18 * 4 + 511) / 512) * 512 * 16) + 9 * (size_t)(64 * 64)
+                     : pipe ? (size_t)2 * (((18 * 18 * 4 + 511) / 512) * 512 * 16) + 4 * (size_t)(512 * 16)
+                            : (size_t)((18 * 18 * 128 + 1023) / 1024 * 1024) + (p.wpre ? nsteps : 2) * (size_t)bc * 128;
+    const size_t lds_bias = (size_t)bc * 4 + 36 * 4;            // the tile's bias values + the patch source table behind the operand buffers
+    // > 64 KiB of dynamic LDS needs an explicit opt-in, once per kernel (done on the first, un-captured call)
+    static std::atomic<unsigned long long> optin{0};
+    if (!lds_optin(optin, {(const void*)conv3x3_direct_kernel<16, true, false>, (const void*)conv3x3_direct_kernel<16, false, false>,
+                           (const void*)conv3x3_direct_kernel<32, true, false>, (const void*)conv3x3_direct_kernel<32, false, false>,
+                           (const void*)conv3x3_direct_kernel<64, true, false>, (const void*)conv3x3_direct_kernel<64, false, false>,
+                           (const void*)conv3x3_direct_kernel<128, true, false>, (const void*)conv3x3_direct_kernel<128, false, false>}))
+        return HN_ERR_LAUNCH;
+    if (narrow) {
+        hipLaunchKernelGGL((conv3x3_direct_kernel<64, false, true, 1>), grid, dim3(512), lds + lds_bias, st, p);
+        HN_LAUNCH_CHECK();
+    }
+#ifdef HN_TUNING
+    static std::atomic<unsigned long long> optin_pipe{0};
+    if (pipe) {
+        if (!lds_optin(optin_pipe, {(const void*)conv3x3_direct_kernel<64, false, true>, (const void*)conv3x3_direct_kernel<128, false, true>}))
+            return HN_ERR_LAUNCH;
+        if (bc == 64) hipLaunchKernelGGL((conv3x3_direct_kernel<64, false, true>), grid, dim3(512), lds + lds_bias, st, p);
+        else hipLaunchKernelGGL((conv3x3_direct_kernel<128, false, true>), grid, dim3(512), lds + lds_bias, st, p);
+        HN_LAUNCH_CHECK();
+    }
+#endif
+#define DIRECT_CASE(BC_) \
+    if (bc == BC_) { \
+        if (out_f32) hipLaunchKernelGGL((conv3x3_direct_kernel<BC_, true, false>), grid, dim3(512), lds + lds_bias, st, p); \
+        else hipLaunchKernelGGL((conv3x3_direct_kernel<BC_, false, false>), grid, dim3(512), lds + lds_bias, st, p); \
+    }
+    DIRECT_CASE(16) DIRECT_CASE(32) DIRECT_CASE(64) DIRECT_CASE(128)
+#undef DIRECT_CASE
+    HN_LAUNCH_CHECK();
+}
+
+// Every NT launch: validates the description against what the kernels support, then picks the kernel.  x.mode is the gather mode:
+// API modes 4 and 5 are mode 2 with x.clamp = 1 (replicate padding) and x.diag (grouped) respectively.  n_img: images of the output
+// grid [n_img][x.H][x.W] (modes 1..5; plain rows have no grid and pass 0).
+static int run_gemm_nt(GemmNT& p, int n_img, bool out_f32, hipStream_t st) {
+    const XSrc& x = p.x;
+    const int Nout = p.Nout, KP = p.KP, taps = p.taps;
+    const long M = x.M;
+    HN_CHECK_ARG(x.x0 && p.w && p.out && M > 0 && Nout > 0 && KP > 0 && (KP & 31) == 0 && taps >= 1 && taps <= 9);
+    // operand transform: plain / stride-2 row gathers, bf16 output; addend: staged bf16 epilogue only (aligned rows, no per-image mapping)
+    HN_CHECK_ARG(!p.xscale || (p.xshift && x.mode <= 1 && !out_f32 && x.C1 == 0 && (!p.xgate || p.xhw > 0)));
+    HN_CHECK_ARG(p.phase_mode == 0 || ((x.mode == 3 || x.clamp == 1) && p.phase_span >= 64 && p.phase_span % 64 == 0 && !p.psum && !p.rpi));
+    HN_CHECK_ARG(!p.addend || p.add_pre || (!out_f32 && (Nout & 7) == 0 && (p.ldc & 7) == 0 && (p.ld_add & 7) == 0 && p.rpi == 0 && x.mode <= 1 &&
+                                            aligned16(p.out) && aligned16(p.addend)));
+    // add_pre: the addend goes in BEFORE the activation (any epilogue form)
+    HN_CHECK_ARG(!p.addend || !p.add_pre || ((x.mode <= 1 || p.phase_mode == 1) && p.rpi == 0 && (p.ld_add & 3) == 0));
+    HN_CHECK_ARG((x.C0 & 7) == 0 && (x.C1 & 7) == 0 && (x.ld0 & 7) == 0 && (x.C1 == 0 || (x.x1 && (x.ld1 & 7) == 0)));
+    HN_CHECK_ARG(x.mode >= 0 && x.mode <= 3 && (!x.clamp || (x.up == 0 && x.C1 == 0)));
+    HN_CHECK_ARG(x.diag ? (KP == 64 && Nout == x.C0 && !p.rpi) : x.C0 + x.C1 <= KP);
+    HN_CHECK_ARG(x.mode == 0 || (long)n_img * x.H * x.W == M);
+    HN_CHECK_ARG(x.mode < 2 ? taps == 1 : taps == 9);
+    HN_CHECK_ARG(x.mode != 2 || x.clamp || (x.H >= 2 && x.W >= 2));
+    HN_CHECK_ARG(p.add_s2 == 0 || (p.add_s2 == 1 && p.addend && !p.add_pre && p.ld_add > 0 && x.mode == 0 && !(x.H & 1) && !(x.W & 1) &&
+                                   (long)n_img * x.H * x.W == M && M < (1L << 32)));
+    HN_CHECK_ARG(!p.lcoef || (x.mode == 0 && taps == 1 && !p.psum && !p.xscale));
+    // level-mapped output: the generic (fp32) epilogue only, plain rows
+    HN_CHECK_ARG(!p.lo_n || (x.mode == 0 && taps == 1 && out_f32 && !p.psum && !p.xscale && p.rpi == 0 && !p.addend && M < (1L << 32)));
+    HN_CHECK_ARG(p.w_rpi == 0 || (x.mode == 0 && taps == 1 && !p.xscale && p.w_rpi % 128 == 0 && M < (1L << 32)));
+    HN_CHECK_ARG(p.emode != 3 || (x.mode == 0 && taps == 1 && p.psum && p.psq && !out_f32 && p.addend && !p.add_pre && p.ld_add > 0 && !p.add_s2 &&
+                                   (Nout & 7) == 0 && (p.ldc & 7) == 0 && p.rpi == 0 && aligned16(p.out) && small_tile(M, Nout)));
+    // depth-to-space store (mode 4): d2s channels per output pixel
+    HN_CHECK_ARG(!p.d2s || (x.clamp == 1 && (out_f32 || p.phase_mode == 1) && p.rpi == 0 && !p.psum && Nout == 4 * p.d2s));
+    p.tile_major = g_hn_knob[11] == 1 ? 1 : 0;
+    p.dbg = (int)g_hn_knob[14];
+    p.dbg_buf = reinterpret_cast<unsigned long long*>(g_hn_knob[15]);          // (read by the kernels with -DHN_TUNING only)
+    // statistics epilogue on the direct kernel: grouped convs only (one partial row per 16x16 patch)
+    if (x.mode >= 2 && (!p.psum || x.diag) && !p.rpi) return launch_direct(p, n_img, out_f32, st);
+    if (p.xscale) {
+#ifdef HN_TUNING
+        if (small_tile(M, Nout)) return launch_nt_xf<64, 64, 2, 2>(p, st);
+        switch (pick_bc(Nout)) {
+            case 16: return launch_nt_xf<16, 128, 1, 4>(p, st);
+            case 32: return launch_nt_xf<32, 128, 1, 4>(p, st);
+            case 64: return launch_nt_xf<64, 128, 2, 2>(p, st);
+            default: return launch_nt_xf<128, 128, 2, 2>(p, st);
+        }
+#else
+        return HN_ERR_UNSUPPORTED;                                   // operand-transform loader: tuning builds only (see launch_nt_xf)
+#endif
+    }
+    if (small_tile(M, Nout)) {
+        // 1x1 convs of the deep stages: two K groups per workgroup when the K loop is long enough to split
+        // (K >= 512 only: at stage 3 -- K = 376, 8192 rows -- the 768 two-group workgroups of 64 KB LDS do not fit the chip's 512 slots in
+        // one round, the 256-thread form's 768 do: 775 -> 781 img/s; knob 6 = 1 turns the form off, > 1 sets the threshold)
+        if (x.mode <= 1 && taps == 1 && KP >= (g_hn_knob[6] > 1 ? g_hn_knob[6] : 512) && g_hn_knob[6] != 1 && !g_nt_force_r)
+            return launch_nt_r<64, 64, 2, 2, 2, 2>(p, out_f32, st);
+        return launch_nt<64, 64, 2, 2>(p, out_f32, st);
+    }
+    switch (pick_bc(Nout)) {
+        case 16: return launch_nt<16, 128, 1, 4>(p, out_f32, st);
+        case 32: return launch_nt<32, 128, 1, 4>(p, out_f32, st);
+        case 64: return launch_nt<64, 128, 2, 2>(p, out_f32, st);
+        default: return launch_nt<128, 128, 2, 2>(p, out_f32, st);
+    }
+}
 
 extern "C" int hn_conv_gemm_nt(const void* x0, const void* x1, int mode, int n_img, int H, int W, int C0, int C1, int ld0, int ld1,
                                int up, long M, const void* w, int Nout, int KP, int taps, const float* bias, int act, void* out,
                                int out_f32, int ldc, long rpi, long img_stride, float* psum, float* psq, hipStream_t st) {
-    return conv_gemm_nt_impl(x0, x1, mode, n_img, H, W, C0, C1, ld0, ld1, up, M, w, Nout, KP, taps, bias, act, out, out_f32, ldc, rpi,
-                             img_stride, psum, psq, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0, 0, 0, st);
+    GemmNT p = nt_conv(x0, x1, mode, H, W, C0, C1, ld0, ld1, up, M, w, Nout, KP, taps, bias, act, out, ldc, rpi, img_stride, psum, psq);
+    return run_gemm_nt(p, n_img, out_f32, st);
 }
 
 /* hn_conv_gemm_nt for plain rows (mode 0, one tap) with ONE PACKED WEIGHT MATRIX PER IMAGE: rows [n * rows_per_image, (n + 1) *
@@ -3315,11 +3489,11 @@ extern "C" int hn_conv_gemm_nt(const void* x0, const void* x1, int mode, int n_i
 extern "C" int hn_conv_gemm_nt_imgw(const void* x0, int ld0, long M, int C0, const void* w, long w_img_stride, long rows_per_image, int Nout,
                                     int KP, const float* bias, int act, void* out, int ldc, const void* addend, int ld_add, hipStream_t st) {
     HN_CHECK_ARG(rows_per_image > 0 && rows_per_image % 128 == 0 && M % rows_per_image == 0 && w_img_stride >= (long)Nout * KP);
-    g_next_imgw = {w_img_stride, rows_per_image};
-    const int rc = conv_gemm_nt_impl(x0, nullptr, 0, 1, 1, (int)(M < (1L << 30) ? M : 1), C0, 0, ld0, 0, 0, M, w, Nout, KP, 1, bias, act, out, 0, ldc, 0, 0,
-                                     nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, addend, addend ? -ld_add : 0, 0, 0, 0, st);
-    g_next_imgw = {0, 0};
-    return rc;
+    HN_CHECK_ARG(!addend || ld_add > 0);
+    GemmNT p = nt_rows(x0, ld0, M, C0, w, Nout, KP, bias, act, out, ldc);
+    p.w_img_stride = w_img_stride; p.w_rpi = (unsigned)rows_per_image;
+    if (addend) { p.addend = (const bf16*)addend; p.ld_add = ld_add; p.add_pre = 1; }
+    return run_gemm_nt(p, 0, false, st);
 }
 
 /* hn_conv_gemm_nt for level-packed plain rows (mode 0, one tap) with the per-level eval-mode BatchNorm + activation of the det towers
@@ -3328,17 +3502,14 @@ extern "C" int hn_conv_gemm_nt_imgw(const void* x0, int ld0, long M, int C0, con
 extern "C" int hn_conv_gemm_nt_lvl(const void* x0, int ld0, long M, int C0, const void* w, int Nout, int KP, const float* bias, int act,
                                    void* out, int ldc, const float* coef, int nlev, const long* rows, hipStream_t st) {
     HN_CHECK_ARG(coef && rows && nlev >= 1 && nlev <= HN_MAX_LEVELS);
-    NextLvl nl = {coef, nlev, {0}, 0, {0}, {0}};
+    GemmNT p = nt_rows(x0, ld0, M, C0, w, Nout, KP, bias, act, out, ldc);
+    p.lcoef = coef; p.ln = nlev;
     for (int l = 0; l < nlev; ++l) {
         HN_CHECK_ARG(rows[l] > 0 && rows[l] % 128 == 0);
-        nl.row[l + 1] = nl.row[l] + rows[l];
+        p.lrow[l + 1] = p.lrow[l] + rows[l];
     }
-    HN_CHECK_ARG(nl.row[nlev] == M);
-    g_next_lvl = nl;
-    const int rc = conv_gemm_nt_impl(x0, nullptr, 0, 1, 1, (int)(M < (1L << 30) ? M : 1), C0, 0, ld0, 0, 0, M, w, Nout, KP, 1, bias, act, out, 0, ldc, 0, 0,
-                                     nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0, 0, 0, st);
-    g_next_lvl.coef = nullptr;
-    return rc;
+    HN_CHECK_ARG(p.lrow[nlev] == M);
+    return run_gemm_nt(p, 0, false, st);
 }
 
 /* hn_conv_gemm_nt for level-packed plain rows (mode 0, one tap) whose fp32 output is the per-image concatenation of the levels
@@ -3349,23 +3520,21 @@ extern "C" int hn_conv_gemm_nt_lvl(const void* x0, int ld0, long M, int C0, cons
 extern "C" int hn_conv_gemm_nt_lvlout(const void* x0, int ld0, long M, int C0, const void* w, int Nout, int KP, const float* bias, int act,
                                       float* out, int ldc, long img_stride, int n_img, int nlev, const int* H, const int* W, int row_align,
                                       hipStream_t st) {
-    HN_CHECK_ARG(out && H && W && n_img > 0 && nlev >= 1 && nlev <= HN_MAX_LEVELS && row_align > 0 && row_align % 128 == 0);
-    NextLvl nl = {nullptr, nlev, {0}, n_img, {0}, {0}};
+    HN_CHECK_ARG(out && H && W && n_img > 0 && nlev >= 1 && nlev <= HN_MAX_LEVELS && row_align > 0 && row_align % 128 == 0 && img_stride >= 0);
+    GemmNT p = nt_rows(x0, ld0, M, C0, w, Nout, KP, bias, act, out, ldc);
+    p.img_stride = img_stride;
+    p.ln = nlev; p.lo_n = n_img;
     unsigned pix = 0;
     for (int l = 0; l < nlev; ++l) {
         HN_CHECK_ARG(H[l] > 0 && W[l] > 0);
         const long real = (long)n_img * H[l] * W[l];
-        nl.row[l + 1] = nl.row[l] + (real + row_align - 1) / row_align * row_align;
-        nl.hw[l] = (unsigned)(H[l] * W[l]);
-        nl.pix[l] = pix;
-        pix += nl.hw[l];
+        p.lrow[l + 1] = p.lrow[l] + (real + row_align - 1) / row_align * row_align;
+        p.lo_hw[l] = (unsigned)(H[l] * W[l]);
+        p.lo_pix[l] = pix;
+        pix += p.lo_hw[l];
     }
-    HN_CHECK_ARG(nl.row[nlev] == M);
-    g_next_lvl = nl;
-    const int rc = conv_gemm_nt_impl(x0, nullptr, 0, 1, 1, (int)(M < (1L << 30) ? M : 1), C0, 0, ld0, 0, 0, M, w, Nout, KP, 1, bias, act, out, 1, ldc, 0,
-                                     img_stride, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0, 0, 0, st);
-    g_next_lvl.nimg = 0; g_next_lvl.n = 0;
-    return rc;
+    HN_CHECK_ARG(p.lrow[nlev] == M);
+    return run_gemm_nt(p, 0, true, st);
 }
 
 // out[n][co][k] = bf16(wp[co][k] * gate[n][k]) (k < C; the K padding stays zero): the per-image operands of hn_conv_gemm_nt_imgw
@@ -3398,8 +3567,10 @@ extern "C" int hn_conv_gemm_nt_ex(const void* x0, const void* x1, int mode, int 
                                   int out_f32, int ldc, long rpi, long img_stride, float* psum, float* psq, const float* xscale,
                                   const float* xshift, const float* xgate, long xhw, int xact, const void* addend, int ld_add,
                                   int add_mode, hipStream_t st) {
-    return conv_gemm_nt_impl(x0, x1, mode, n_img, H, W, C0, C1, ld0, ld1, up, M, w, Nout, KP, taps, bias, act, out, out_f32, ldc, rpi,
-                             img_stride, psum, psq, xscale, xshift, xgate, xhw, xact, addend, ld_add, add_mode, 0, 0, st);
+    GemmNT p = nt_conv(x0, x1, mode, H, W, C0, C1, ld0, ld1, up, M, w, Nout, KP, taps, bias, act, out, ldc, rpi, img_stride, psum, psq);
+    p.xscale = xscale; p.xshift = xshift; p.xgate = xgate; p.xhw = xhw; p.xact = xact;
+    nt_addend(p, addend, ld_add, add_mode);
+    return run_gemm_nt(p, n_img, out_f32, st);
 }
 
 /* hn_conv_gemm_nt_ex with a statistics-epilogue operand (GemmNT::emode): the partial rows psum / psq carry, instead of the BatchNorm
@@ -3412,11 +3583,10 @@ extern "C" int hn_conv_gemm_nt_stat(const void* x0, const void* x1, int mode, in
                                     int add_mode, int emode, const void* ez, int ld_ez, const float* ecoef, hipStream_t st) {
     HN_CHECK_ARG((emode == 1 || emode == 2) && psum && (psq || emode == 1) && ez && ecoef && (Nout & 7) == 0 && (ld_ez & 3) == 0 && !out_f32 &&
                  act == HN_ACT_NONE && (mode <= 1 || mode == 5) && (reinterpret_cast<uintptr_t>(ez) & 7) == 0);
-    g_next_stat = {emode, (const bf16*)ez, ld_ez, ecoef, nullptr, 0};
-    const int rc = conv_gemm_nt_impl(x0, x1, mode, n_img, H, W, C0, C1, ld0, ld1, up, M, w, Nout, KP, taps, bias, act, out, out_f32, ldc, rpi,
-                                     img_stride, psum, psq, nullptr, nullptr, nullptr, 0, 0, addend, ld_add, add_mode, 0, 0, st);
-    g_next_stat = {0, nullptr, 0, nullptr, nullptr, 0};
-    return rc;
+    GemmNT p = nt_conv(x0, x1, mode, H, W, C0, C1, ld0, ld1, up, M, w, Nout, KP, taps, bias, act, out, ldc, rpi, img_stride, psum, psq);
+    nt_addend(p, addend, ld_add, add_mode);
+    p.emode = emode; p.ez = (const bf16*)ez; p.ld_ez = ld_ez; p.ecoef = ecoef;
+    return run_gemm_nt(p, n_img, out_f32, st);
 }
 
 /* 1x1 data-gradient GEMM of an identity XBlock, dx = dz1 W1^T + g (addend, added after rounding: the staged epilogue), whose statistics rows
@@ -3428,11 +3598,11 @@ extern "C" int hn_conv_gemm_nt_stat3(const void* x0, int ld0, long M, int C0, co
                                      float* psq, const void* addend, int ld_add, const void* ez, int ld_ez, const void* ey, int ld_ey,
                                      const float* ecoef, hipStream_t st) {
     HN_CHECK_ARG(psum && psq && ez && ey && ecoef && addend && (ld_ez & 7) == 0 && (ld_ey & 7) == 0);
-    g_next_stat = {3, (const bf16*)ez, ld_ez, ecoef, (const bf16*)ey, ld_ey};
-    const int rc = conv_gemm_nt_impl(x0, nullptr, 0, 1, 1, (int)(M < (1L << 30) ? M : 1), C0, 0, ld0, 0, 0, M, w, Nout, KP, 1, nullptr, HN_ACT_NONE, out, 0,
-                                     ldc, 0, 0, psum, psq, nullptr, nullptr, nullptr, 0, 0, addend, ld_add, 0, 0, 0, st);
-    g_next_stat = {0, nullptr, 0, nullptr, nullptr, 0};
-    return rc;
+    GemmNT p = nt_rows(x0, ld0, M, C0, w, Nout, KP, nullptr, HN_ACT_NONE, out, ldc);
+    p.psum = psum; p.psq = psq;
+    p.addend = (const bf16*)addend; p.ld_add = ld_add;
+    p.emode = 3; p.ez = (const bf16*)ez; p.ld_ez = ld_ez; p.ecoef = ecoef; p.ey = (const bf16*)ey; p.ld_ey = ld_ey;
+    return run_gemm_nt(p, 0, false, st);
 }
 
 /* Phase form of Conv3x3(ReflectionPad2d(1)(nearest_up2(x0))) on the low-resolution grid (head_seg/segmentation.py:92-104 decoder blocks
@@ -3447,211 +3617,25 @@ extern "C" int hn_conv3x3_out_argmax(const void* x0, int n_img, int H, int W, in
                                      long* mask, hipStream_t st) {
     HN_CHECK_ARG(mask && k >= 1 && 4 * k <= 32 && 32 * 32 * k * 4 <= 32768 && KP == 64 && C0 <= 64 && ((2 * W * k) & 3) == 0 && ((32 * k) & 3) == 0 &&
                  (reinterpret_cast<uintptr_t>(mask) & 15) == 0);
-    g_next_amax = mask;
     // (out is only used for its alignment test; nothing is written to it)
-    const int rc = conv_gemm_nt_impl(x0, nullptr, 4, n_img, H, W, C0, 0, ld0, 0, 0, (long)n_img * H * W, w, 4 * k, KP, 9, bias, HN_ACT_NONE,
-                                     (void*)mask, 1, 4 * k, 0, -(long)k, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0, 0, 0, st);
-    g_next_amax = nullptr;
-    return rc;
+    GemmNT p = nt_desc(make_xsrc(x0, nullptr, 4, H, W, C0, 0, ld0, 0, 0, (long)n_img * H * W), w, 4 * k, KP, 9, bias, HN_ACT_NONE, mask, 4 * k);
+    p.d2s = k;
+    p.amax = mask;
+    return run_gemm_nt(p, n_img, true, st);
 }
 
 extern "C" int hn_conv3x3_phase(const void* x0, int mode, int n_img, int H, int W, int C0, int ld0, const void* w, int Nout, int KP,
                                 const float* bias, int act, void* out, int ldc, int k, const void* addend, int ld_add, hipStream_t st) {
     HN_CHECK_ARG((mode == 4 || mode == 3) && k > 0 && (k & 3) == 0);
+    if (mode == 4) HN_CHECK_ARG(Nout == 4 * k && (k % 64 == 0) && (!addend || (ld_add > 0 && (ld_add & 3) == 0)));
+    else HN_CHECK_ARG(C0 == 4 * k && (k % 64 == 0) && !addend);
+    GemmNT p = nt_desc(make_xsrc(x0, nullptr, mode, H, W, C0, 0, ld0, 0, 0, (long)n_img * H * W), w, Nout, KP, 9, bias, act, out, ldc);
+    p.phase_mode = mode == 4 ? 1 : 2; p.phase_span = k;
     if (mode == 4) {
-        HN_CHECK_ARG(Nout == 4 * k && (k % 64 == 0) && (!addend || (ld_add & 3) == 0));
-        return conv_gemm_nt_impl(x0, nullptr, 4, n_img, H, W, C0, 0, ld0, 0, 0, (long)n_img * H * W, w, Nout, KP, 9, bias, act, out, 0, ldc, 0,
-                                 -(long)k, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, addend, -ld_add, 0, 1, k, st);
+        p.d2s = k;
+        if (addend) { p.addend = (const bf16*)addend; p.ld_add = ld_add; p.add_pre = 1; }
     }
-    HN_CHECK_ARG(C0 == 4 * k && (k % 64 == 0) && !addend);
-    return conv_gemm_nt_impl(x0, nullptr, 3, n_img, H, W, C0, 0, ld0, 0, 0, (long)n_img * H * W, w, Nout, KP, 9, bias, act, out, 0, ldc, 0, 0,
-                             nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0, 2, k, st);
-}
-
-static int conv_gemm_nt_impl(const void* x0, const void* x1, int mode, int n_img, int H, int W, int C0, int C1, int ld0, int ld1,
-                             int up, long M, const void* w, int Nout, int KP, int taps, const float* bias, int act, void* out,
-                             int out_f32, int ldc, long rpi, long img_stride, float* psum, float* psq, const float* xscale,
-                             const float* xshift, const float* xgate, long xhw, int xact, const void* addend, int ld_add, int add_mode,
-                             int phase_mode, int phase_span, hipStream_t st) {
-    HN_CHECK_ARG(x0 && w && out && M > 0 && Nout > 0 && KP > 0 && (KP & 31) == 0 && taps >= 1 && taps <= 9);
-    // operand transform: plain / stride-2 row gathers, bf16 output; addend: staged bf16 epilogue only (aligned rows, no per-image mapping)
-    HN_CHECK_ARG(!xscale || (xshift && mode <= 1 && !out_f32 && C1 == 0 && (!xgate || xhw > 0)));
-    // ld_add < 0: the addend (row stride -ld_add) is added BEFORE the activation (any epilogue form)
-    HN_CHECK_ARG(phase_mode == 0 || ((mode == 3 || mode == 4) && phase_span >= 64 && phase_span % 64 == 0 && !psum && !rpi));
-    HN_CHECK_ARG(!addend || ld_add < 0 || (!out_f32 && (Nout & 7) == 0 && (ldc & 7) == 0 && (ld_add & 7) == 0 && rpi == 0 && mode <= 1 &&
-                                           (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (reinterpret_cast<uintptr_t>(addend) & 15) == 0));
-    HN_CHECK_ARG(!addend || ld_add >= 0 || ((mode <= 1 || phase_mode == 1) && rpi == 0 && ((-ld_add) & 3) == 0));
-    HN_CHECK_ARG((C0 & 7) == 0 && (C1 & 7) == 0 && (ld0 & 7) == 0 && (C1 == 0 || (x1 && (ld1 & 7) == 0)));
-    HN_CHECK_ARG(mode >= 0 && mode <= 5 && (mode < 4 || (up == 0 && C1 == 0)));
-    HN_CHECK_ARG(mode == 5 ? (KP == 64 && Nout == C0 && !rpi) : C0 + C1 <= KP);
-    HN_CHECK_ARG(mode == 0 || (long)n_img * H * W == M);
-    HN_CHECK_ARG(mode < 2 ? taps == 1 : taps == 9);
-    HN_CHECK_ARG(mode != 2 || (H >= 2 && W >= 2));
-    GemmNT p;
-    p.x = make_xsrc(x0, x1, mode, n_img, H, W, C0, C1, ld0, ld1, up, M);
-    mode = p.x.mode;
-    p.w = (const bf16*)w; p.Nout = Nout; p.KP = KP; p.taps = taps;
-    p.bias = bias; p.act = act; p.out = out; p.ldc = ldc; p.psum = psum; p.psq = psq;
-    p.rpi = rpi; p.img_stride = img_stride;
-    p.d2s = 0;
-    p.xscale = xscale; p.xshift = xshift; p.xgate = xgate; p.xhw = xhw; p.xact = xact;
-    p.addend = (const bf16*)addend; p.ld_add = ld_add < 0 ? -ld_add : ld_add; p.add_pre = ld_add < 0 ? 1 : 0;
-    HN_CHECK_ARG(add_mode == 0 || (add_mode == 1 && addend && ld_add > 0 && mode == 0 && !(H & 1) && !(W & 1) && (long)n_img * H * W == M &&
-                                   M < (1L << 32)));
-    p.add_s2 = add_mode;
-    p.phase_mode = phase_mode; p.phase_span = phase_span;
-    p.amax = g_next_amax;
-    g_next_amax = nullptr;
-    p.w_img_stride = g_next_imgw.stride; p.w_rpi = (unsigned)g_next_imgw.rpi;
-    g_next_imgw = {0, 0};
-    p.lcoef = g_next_lvl.coef; p.ln = g_next_lvl.n;
-    for (int l = 0; l <= HN_MAX_LEVELS; ++l) p.lrow[l] = g_next_lvl.row[l];
-    p.lo_n = g_next_lvl.nimg;
-    for (int l = 0; l < HN_MAX_LEVELS; ++l) { p.lo_hw[l] = g_next_lvl.hw[l]; p.lo_pix[l] = g_next_lvl.pix[l]; }
-    g_next_lvl.coef = nullptr; g_next_lvl.nimg = 0;
-    HN_CHECK_ARG(!p.lcoef || (mode == 0 && taps == 1 && !psum && !xscale));
-    // level-mapped output: the generic (fp32) epilogue only, plain rows
-    HN_CHECK_ARG(!p.lo_n || (mode == 0 && taps == 1 && out_f32 && !psum && !xscale && rpi == 0 && !addend && M < (1L << 32)));
-    HN_CHECK_ARG(p.w_rpi == 0 || (mode == 0 && taps == 1 && !xscale && p.w_rpi % 128 == 0 && M < (1L << 32)));
-    p.emode = g_next_stat.mode; p.ez = g_next_stat.z; p.ld_ez = g_next_stat.ldz; p.ecoef = g_next_stat.coef; p.ey = g_next_stat.y; p.ld_ey = g_next_stat.ldy;
-    HN_CHECK_ARG(p.emode != 3 || (mode == 0 && taps == 1 && psum && psq && !out_f32 && addend && ld_add > 0 && !add_mode && (Nout & 7) == 0 &&
-                                   (ldc & 7) == 0 && rpi == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && small_tile(M, Nout)));
-    p.tile_major = g_hn_knob[11] == 1 ? 1 : 0;
-    p.wpre = 0;
-    p.dbg = (int)g_hn_knob[14];
-    p.dbg_buf = reinterpret_cast<unsigned long long*>(g_hn_knob[15]);          // (read by the kernels with -DHN_TUNING only)
-    p.fold = g_next_fold.ring ? g_next_fold.form : 0; p.fold_out2 = g_next_fold.out2; p.ld_fo2 = g_next_fold.ld2; p.ring = g_next_fold.ring; p.fold_y = g_next_fold.y; p.ld_fy = g_next_fold.ldy;
-    if (img_stride < 0) {                                            // mode 4: -img_stride = channels per depth-to-space output pixel
-        HN_CHECK_ARG(p.x.clamp == 1 && (out_f32 || phase_mode == 1) && rpi == 0 && !psum && Nout == 4 * (int)(-img_stride));
-        p.d2s = (int)(-img_stride);
-        p.img_stride = 0;
-    }
-    if (mode >= 2 && (!psum || p.x.diag) && !rpi) {      // statistics epilogue: grouped convs only (one partial row per 16x16 patch)
-        // the last decoder block's phase-form conv (64 -> 4 x 64): the persistent form, one phase per workgroup
-        if (p.x.clamp == 1 && !p.x.diag && !out_f32 && p.d2s == 64 && phase_mode == 1 && phase_span == 64 && taps == 9 && KP == 64 && C0 == 64 && C1 == 0 &&
-            Nout == 256 && !psum && !addend && (act == HN_ACT_ELU || act == HN_ACT_NONE) && (ld0 & 7) == 0 && (ldc & 7) == 0 && ldc >= 64 &&
-            (reinterpret_cast<uintptr_t>(out) & 15) == 0 && g_hn_knob[11] != 3) {
-            const long npatch = (long)cdiv(W, 16) * cdiv(H, 16) * n_img;
-            if (npatch >= 1024) {
-                SegPhase q;
-                q.x = (const bf16*)x0; q.ldx = ld0; q.N = n_img; q.H = H; q.W = W; q.w = (const bf16*)w; q.bias = bias; q.out = (bf16*)out; q.ldc = ldc;
-                q.act = act; q.npatch = (int)npatch;
-                q.ppw = cdiv(npatch, 64);                              // 64 patch ranges x 4 phases = 256 workgroups
-                const int grid = 4 * cdiv(npatch, q.ppw);
-                const size_t lds = 2 * (size_t)((18 * 18 * 8 + 63) / 64) * 1024 + 256 * 128;
-                static std::atomic<unsigned long long> optin_sp{0};
-                if (!lds_optin(optin_sp, {(const void*)seg_phase64_conv_kernel})) return HN_ERR_LAUNCH;
-                hipLaunchKernelGGL(seg_phase64_conv_kernel, dim3(grid), dim3(512), lds, st, q);
-                HN_LAUNCH_CHECK();
-            }
-        }
-        // the seg output conv on a map big enough to give every CU several patches: the persistent form with the weights in registers
-        if (p.x.clamp == 1 && !p.x.diag && out_f32 && p.d2s && taps == 9 && KP == 64 && C0 == 64 && C1 == 0 && Nout == 4 * p.d2s && Nout <= 32 &&
-            !psum && !addend && phase_mode == 0 && act == HN_ACT_NONE && (ld0 & 7) == 0 && ((32 * p.d2s) & 3) == 0 && ((2 * W * p.d2s) & 3) == 0 &&
-            (reinterpret_cast<uintptr_t>(out) & 15) == 0 && g_hn_knob[11] != 3) {
-            const long npatch = (long)cdiv(W, 16) * cdiv(H, 16) * n_img;
-            if (npatch >= 1024) {
-                SegOut q;
-                q.x = (const bf16*)x0; q.ldx = ld0; q.N = n_img; q.H = H; q.W = W; q.w = (const bf16*)w; q.Nout = Nout; q.k = p.d2s; q.bias = bias;
-                q.out = p.amax ? nullptr : (float*)out; q.amax = p.amax; q.npatch = (int)npatch;
-                q.ppw = cdiv(npatch, 256);
-                const int grid = cdiv(npatch, q.ppw);
-                const size_t lds = 2 * (size_t)((18 * 18 * 8 + 63) / 64) * 1024 + (size_t)32 * 32 * p.d2s * 4;
-                static std::atomic<unsigned long long> optin_so{0};
-                if (!lds_optin(optin_so, {(const void*)seg_out_conv_kernel<true>, (const void*)seg_out_conv_kernel<false>})) return HN_ERR_LAUNCH;
-                if (p.amax) hipLaunchKernelGGL(seg_out_conv_kernel<true>, dim3(grid), dim3(512), lds, st, q);
-                else hipLaunchKernelGGL(seg_out_conv_kernel<false>, dim3(grid), dim3(512), lds, st, q);
-                HN_LAUNCH_CHECK();
-            }
-        }
-        HN_CHECK_ARG(p.x.Wi < 8192 && p.x.Hi < 32768);  // packed patch coordinates of the direct kernel
-        int bc = p.x.diag ? 64 : (Nout <= 16 ? 16 : (Nout <= 32 ? 32 : (Nout <= 64 ? 64 : 128)));
-        if (phase_mode == 1 && phase_span < bc) bc = 64;            // a cout tile must lie inside one phase
-        // bf16 tiles of >= 64 couts leave through the LDS-staged epilogue only (whole 16-byte pieces of aligned rows)
-        const bool staged_ok = (ldc & 7) == 0 && (Nout & 7) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
-                               (!p.d2s || ((p.d2s & 7) == 0 && Nout % bc == 0));
-        if (bc >= 64 && !out_f32 && !staged_ok) {       // (odd channel counts / unaligned slices: the 32-cout tile keeps the generic epilogue)
-            if (p.x.diag) return HN_ERR_UNSUPPORTED;
-            bc = 32;
-        }
-        dim3 grid((unsigned)(cdiv(Nout, bc) * cdiv(W, 16) * cdiv(H, 16) * n_img));
-        // preloaded form: one chunk, all its tap tiles (<= 16) in at most 32 KB next to the patch (two or three workgroups per CU as before)
-        const int nsteps = phase_mode ? 4 : 9;
-        p.wpre = (!p.x.diag && KP <= 64 && (size_t)nsteps * bc * 128 <= 32768 && g_hn_knob[11] != 2) ? 1 : 0;
-        // software-pipelined variant (32-channel chunks, two patch buffers + ring of four weight tiles, counted waits; still two workgroups
-        // per CU): the multi-chunk bf16 launches with >= 64 couts per tile
-        // (the multi-chunk form measured slower on every seg-decoder shape: tools/bench_seg.py; tuning builds can force it)
-        // K <= 32 channels per tap in ONE chunk (the output layer's data gradient: 24 real channels of a 64-channel chunk): 32-channel
-        // chunks halve the MFMAs, LDS fragment reads and weight DMA of a tap step, and with a single patch buffer (24 KB) + the ring of
-        // four weight tiles (32 KB) two workgroups share a CU
-        const bool narrow = bc == 64 && !out_f32 && !p.x.diag && !p.wpre && KP <= 32 && nsteps == 9 && g_hn_knob[18] == 0;
-        if (narrow) p.wpre = 1;                                     // all nine 4 KB tap tiles next to the patch: no barrier in the tap loop
-#ifdef HN_TUNING
-        const bool pipe = narrow || (g_direct_pipe && bc >= 64 && !out_f32 && !p.x.diag && !p.wpre && KP > 64);
-#else
-        const bool pipe = narrow;
-#endif
-        const size_t lds = narrow ? (size_t)(((18 * 18 * 4 + 511) / 512) * 512 * 16) + 9 * (size_t)(64 * 64)
-                         : pipe ? (size_t)2 * (((18 * 18 * 4 + 511) / 512) * 512 * 16) + 4 * (size_t)(512 * 16)
-                                : (size_t)((18 * 18 * 128 + 1023) / 1024 * 1024) + (p.wpre ? nsteps : 2) * (size_t)bc * 128;
-        const size_t lds_bias = (size_t)bc * 4 + 36 * 4;            // the tile's bias values + the patch source table behind the operand buffers
-        // > 64 KiB of dynamic LDS needs an explicit opt-in, once per kernel (done on the first, un-captured call)
-        static std::atomic<unsigned long long> optin{0};
-        if (!lds_optin(optin, {(const void*)conv3x3_direct_kernel<16, true, false>, (const void*)conv3x3_direct_kernel<16, false, false>,
-                               (const void*)conv3x3_direct_kernel<32, true, false>, (const void*)conv3x3_direct_kernel<32, false, false>,
-                               (const void*)conv3x3_direct_kernel<64, true, false>, (const void*)conv3x3_direct_kernel<64, false, false>,
-                               (const void*)conv3x3_direct_kernel<128, true, false>, (const void*)conv3x3_direct_kernel<128, false, false>}))
-            return HN_ERR_LAUNCH;
-        if (narrow) {
-            hipLaunchKernelGGL((conv3x3_direct_kernel<64, false, true, 1>), grid, dim3(512), lds + lds_bias, st, p);
-            HN_LAUNCH_CHECK();
-        }
-#ifdef HN_TUNING
-        static std::atomic<unsigned long long> optin_pipe{0};
-        if (pipe) {
-            if (!lds_optin(optin_pipe, {(const void*)conv3x3_direct_kernel<64, false, true>, (const void*)conv3x3_direct_kernel<128, false, true>}))
-                return HN_ERR_LAUNCH;
-            if (bc == 64) hipLaunchKernelGGL((conv3x3_direct_kernel<64, false, true>), grid, dim3(512), lds + lds_bias, st, p);
-            else hipLaunchKernelGGL((conv3x3_direct_kernel<128, false, true>), grid, dim3(512), lds + lds_bias, st, p);
-            HN_LAUNCH_CHECK();
-        }
-#endif
-#define DIRECT_CASE(BC_) \
-        if (bc == BC_) { \
-            if (out_f32) hipLaunchKernelGGL((conv3x3_direct_kernel<BC_, true, false>), grid, dim3(512), lds + lds_bias, st, p); \
-            else hipLaunchKernelGGL((conv3x3_direct_kernel<BC_, false, false>), grid, dim3(512), lds + lds_bias, st, p); \
-        }
-        DIRECT_CASE(16) DIRECT_CASE(32) DIRECT_CASE(64) DIRECT_CASE(128)
-#undef DIRECT_CASE
-        HN_LAUNCH_CHECK();
-    }
-    if (xscale) {
-#ifdef HN_TUNING
-        if (small_tile(M, Nout)) return launch_nt_xf<64, 64, 2, 2>(p, st);
-        switch (pick_bc(Nout)) {
-            case 16: return launch_nt_xf<16, 128, 1, 4>(p, st);
-            case 32: return launch_nt_xf<32, 128, 1, 4>(p, st);
-            case 64: return launch_nt_xf<64, 128, 2, 2>(p, st);
-            default: return launch_nt_xf<128, 128, 2, 2>(p, st);
-        }
-#else
-        return HN_ERR_UNSUPPORTED;                                   // operand-transform loader: tuning builds only (see launch_nt_xf)
-#endif
-    }
-    if (small_tile(M, Nout)) {
-        // 1x1 convs of the deep stages: two K groups per workgroup when the K loop is long enough to split
-        // (K >= 512 only: at stage 3 -- K = 376, 8192 rows -- the 768 two-group workgroups of 64 KB LDS do not fit the chip's 512 slots in
-        // one round, the 256-thread form's 768 do: 775 -> 781 img/s; knob 6 = 1 turns the form off, > 1 sets the threshold)
-        if (mode <= 1 && taps == 1 && KP >= (g_hn_knob[6] > 1 ? g_hn_knob[6] : 512) && g_hn_knob[6] != 1 && !g_nt_force_r)
-            return launch_nt_r<64, 64, 2, 2, 2, 2>(p, out_f32, st);
-        return launch_nt<64, 64, 2, 2, 4>(p, out_f32, st);
-    }
-    switch (pick_bc(Nout)) {
-        case 16: return launch_nt<16, 128, 1, 4, 2>(p, out_f32, st);
-        case 32: return launch_nt<32, 128, 1, 4, 4>(p, out_f32, st);
-        case 64: return launch_nt<64, 128, 2, 2, 4>(p, out_f32, st);
-        default: return launch_nt<128, 128, 2, 2, 4>(p, out_f32, st);
-    }
+    return run_gemm_nt(p, n_img, false, st);
 }
 
 // Border fix-up of a folded data gradient (GemmNT::fold): the gradient of a reflection- (clamp = 0) or replicate-padded (clamp = 1) input
@@ -3731,11 +3715,12 @@ static int dgrad_fold_impl(const void* dz, int ldz, int Cz, int n_img, int H, in
     const int form = !out_s2d ? 1 : (out ? 3 : 2);
     void* o1 = out ? out : out_s2d;                                  // the tensor the conv epilogue / fix-up address first
     const int l1 = out ? ldo : ld_s2d;
-    g_next_fold = {(bf16*)ring, (const bf16*)yprev, ldy, form, form == 3 ? (bf16*)out_s2d : nullptr, ld_s2d};
-    const int rc = conv_gemm_nt_impl(dz, nullptr, 3, n_img, H + 2, W + 2, Cz, 0, ldz, 0, 0, (long)n_img * (H + 2) * (W + 2), wt, Nout, KP, 9,
-                                     nullptr, HN_ACT_NONE, o1, 0, l1, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0,
-                                     phase_k ? 2 : 0, phase_k, st);
-    g_next_fold = {nullptr, nullptr, 0, 0, nullptr, 0};
+    GemmNT p = nt_desc(make_xsrc(dz, nullptr, 3, H + 2, W + 2, Cz, 0, ldz, 0, 0, (long)n_img * (H + 2) * (W + 2)), wt, Nout, KP, 9, nullptr,
+                       HN_ACT_NONE, o1, l1);
+    p.phase_mode = phase_k ? 2 : 0; p.phase_span = phase_k;
+    p.fold = form; p.ring = (bf16*)ring; p.fold_y = (const bf16*)yprev; p.ld_fy = ldy;
+    p.fold_out2 = form == 3 ? (bf16*)out_s2d : nullptr; p.ld_fo2 = ld_s2d;
+    const int rc = run_gemm_nt(p, n_img, false, st);
     if (rc != HN_OK) return rc;
     const long total = (long)n_img * (2 * W + 2 * (H - 2)) * (Nout >> 3);
     hipLaunchKernelGGL(seg_ring_fix_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, (bf16*)o1, l1, (const bf16*)ring, (const bf16*)yprev, ldy,
@@ -3783,9 +3768,6 @@ static void tn_tiles(int Nout, int KP, int& bc, int& bn) {
     if (bc == 16 && bn < 64) bn = 64;                       // 4 waves need >= 16 columns each
 }
 
-// (KP = 32, the 24-channel skip operand of decoder.5: nine tap-parallel row-gather workgroups re-read dZ nine times -- 173 us; the
-// patch kernel reads it once: 95 us with half of a 64-channel patch zero-filled, 69 us with the 32-channel patch)
-static bool use_patch_wgrad(int mode, int Nout, int KP) { return mode == 2 && KP >= 32; }
 static void patch_tiles(int Nout, int KP, int& bc, int& ci, int& ksplit) {
     if (KP <= 32 && Nout > 64) { bc = 128; ci = 32; ksplit = 2; return; }
     if (Nout <= 16) { bc = 16; ci = 64; ksplit = 2; }
@@ -3794,77 +3776,80 @@ static void patch_tiles(int Nout, int KP, int& bc, int& ci, int& ksplit) {
     else { bc = 128; ci = 64; ksplit = 1; }
 }
 
-// plan the pixel split for wgrad: returns splits, rows per split (multiple of 64; patches per split for the 3x3 patch kernel) and the
-// fp32 workspace size in bytes
-static int wgrad_plan_impl(int mode, int n_img, int H, int W, long M, int Nout, int KP, int taps, int phase_span, int* splits,
-                           long* rows_per_split, long* ws_bytes);
-extern "C" int hn_wgrad_plan(int mode, int n_img, int H, int W, long M, int Nout, int KP, int taps, int* splits, long* rows_per_split,
-                             long* ws_bytes) {
-    return wgrad_plan_impl(mode, n_img, H, W, M, Nout, KP, taps, 0, splits, rows_per_split, ws_bytes);
-}
-/* plan of hn_conv_gemm_tn_phase (phase_span = couts per phase) */
-extern "C" int hn_wgrad_plan_phase(int n_img, int H, int W, int Nout, int KP, int phase_span, int* splits, long* rows_per_split, long* ws_bytes) {
-    return wgrad_plan_impl(4, n_img, H, W, (long)n_img * H * W, Nout, KP, 9, phase_span, splits, rows_per_split, ws_bytes);
-}
-static int wgrad_plan_impl(int mode, int n_img, int H, int W, long M, int Nout, int KP, int taps, int phase_span, int* splits,
-                           long* rows_per_split, long* ws_bytes) {
-    HN_CHECK_ARG(M > 0 && Nout > 0 && KP > 0 && taps > 0 && splits && rows_per_split && ws_bytes);
-    const int grouped = mode == 5;
-    if (mode == 4 || mode == 5) mode = 2;
-    if (use_patch_wgrad(mode, Nout, KP)) {
-        int bc, ci, ksplit;
-        patch_tiles(Nout, KP, bc, ci, ksplit);
-        if (grouped) { bc = 64; ci = 64; ksplit = 2; }
-        if (phase_span && phase_span < bc) { bc = 64; ci = 64; ksplit = 2; }      // a cout tile must lie inside one phase
-        const long tiles = (long)cdiv(Nout, bc) * cdiv(KP, ci);
-        const long patches = (long)n_img * cdiv(H, 8) * cdiv(W, 16);
+// The weight-gradient plan of one launch: hn_wgrad_plan / hn_wgrad_plan_phase size the workspace from it, run_gemm_tn launches it.
+struct WgradPlan {
+    bool patch;            // the 3x3 patch kernel (wgrad3x3_patch_kernel), else the row-gather GEMM (gemm_tn_kernel)
+    int bc, bn;            // cout tile, K tile (patch kernel: input channels per tile)
+    int ksplit;            // patch kernel: k-split wave groups per workgroup, one slab each
+    int splits;            // partial slabs
+    long rows_per_split;   // multiple of 64; patches per split for the patch kernel
+    long patches;          // patch kernel: 8 x 16 output patches in all
+    long ws_bytes;         // fp32 workspace: the slabs + the bias-gradient partial rows
+};
+// x: the pixel operand's shape (mode, grid, rows); phase_span: couts per phase of a phase-form conv (0: not one)
+static int wgrad_plan(WgradPlan& q, const XSrc& x, int n_img, int Nout, int KP, int taps, int phase_span) {
+    HN_CHECK_ARG(x.M > 0 && Nout > 0 && KP > 0 && taps > 0);
+    // (KP = 32, the 24-channel skip operand of decoder.5: nine tap-parallel row-gather workgroups re-read dZ nine times -- 173 us; the
+    // patch kernel reads it once: 95 us with half of a 64-channel patch zero-filled, 69 us with the 32-channel patch)
+    q.patch = x.mode == 2 && KP >= 32;
+    if (q.patch) {
+        patch_tiles(Nout, KP, q.bc, q.bn, q.ksplit);
+        if (x.diag || (phase_span && phase_span < q.bc)) { q.bc = 64; q.bn = 64; q.ksplit = 2; }    // (phase: a cout tile must lie inside one phase)
+        const long tiles = (long)cdiv(Nout, q.bc) * cdiv(KP, q.bn);
+        q.patches = (long)n_img * cdiv(x.H, 8) * cdiv(x.W, 16);
         long want = (g_hn_knob[12] + tiles - 1) / tiles;          // (knob 12 = 256) one workgroup per CU in total: every split costs a full fp32 slab of dW (write + reduce)
         // ... unless the slab is small: then two workgroups per CU (where their LDS fits) hide each other's DMA waits
-        if (bc <= 64 && 2 * want * ksplit * (long)Nout * taps * KP * 4 <= (64L << 20)) want *= 2;
-        if (want > patches / 2) want = patches / 2;
+        if (q.bc <= 64 && 2 * want * q.ksplit * (long)Nout * taps * KP * 4 <= (64L << 20)) want *= 2;
+        if (want > q.patches / 2) want = q.patches / 2;
         if (want < 1) want = 1;
-        const long pps = (patches + want - 1) / want;
-        *splits = (int)((patches + pps - 1) / pps) * ksplit;       // number of partial slabs
-        *rows_per_split = pps;
-        *ws_bytes = (long)(*splits) * Nout * taps * KP * 4 + (long)(*splits) * Nout * 4;     // + the bias-gradient partial rows
-        return HN_OK;
+        const long pps = (q.patches + want - 1) / want;
+        q.splits = (int)((q.patches + pps - 1) / pps) * q.ksplit;   // number of partial slabs
+        q.rows_per_split = pps;
+    } else {
+        q.ksplit = 1; q.patches = 0;
+        tn_tiles(Nout, KP, q.bc, q.bn);
+        const long tiles = (long)cdiv(Nout, q.bc) * cdiv(KP, q.bn) * taps;
+        long want = (g_hn_knob[0] + tiles - 1) / tiles;         // ~4 workgroups per CU in total
+        if (tiles <= 2) want = 512 / tiles;                     // one or two output tiles (the 112-channel convs of the neck / det towers): every split costs a
+                                                                // whole fp32 slab -- two workgroups per CU instead of four (+0.3 % on the step; 256 and 768 are worse)
+        const long max_splits = (x.M + g_hn_knob[1] - 1) / g_hn_knob[1];   // at least 256 rows per split
+        if (want > max_splits) want = max_splits;
+        if (g_tn_force_splits) want = g_tn_force_splits;
+        if (want < 1) want = 1;
+        const long rps = ((x.M + want - 1) / want + 63) / 64 * 64;
+        q.splits = (int)((x.M + rps - 1) / rps);
+        q.rows_per_split = rps;
     }
-    int bc, bn;
-    tn_tiles(Nout, KP, bc, bn);
-    const long tiles = (long)cdiv(Nout, bc) * cdiv(KP, bn) * taps;
-    long want = (g_hn_knob[0] + tiles - 1) / tiles;         // ~4 workgroups per CU in total
-    if (tiles <= 2) want = 512 / tiles;                     // one or two output tiles (the 112-channel convs of the neck / det towers): every split costs a
-                                                            // whole fp32 slab -- two workgroups per CU instead of four (+0.3 % on the step; 256 and 768 are worse)
-    const long max_splits = (M + g_hn_knob[1] - 1) / g_hn_knob[1];   // at least 256 rows per split
-    if (want > max_splits) want = max_splits;
-    if (g_tn_force_splits) want = g_tn_force_splits;
-    if (want < 1) want = 1;
-    long rps = ((M + want - 1) / want + 63) / 64 * 64;
-    *splits = (int)((M + rps - 1) / rps);
-    *rows_per_split = rps;
-    *ws_bytes = (long)(*splits) * Nout * taps * KP * 4 + (long)(*splits) * Nout * 4;         // + the bias-gradient partial rows
+    q.ws_bytes = (long)q.splits * Nout * taps * KP * 4 + (long)q.splits * Nout * 4;
     return HN_OK;
 }
 
-static int conv_gemm_tn_impl(const void* x0, const void* x1, int mode, int n_img, int H, int W, int C0, int C1, int ld0, int ld1,
-                             int up, long M, const void* dz, int ldz, int Nout, int KP, int taps, int phase_span, float* workspace, float* dw,
-                             float* dbias, hipStream_t st);
-extern "C" int hn_conv_gemm_tn(const void* x0, const void* x1, int mode, int n_img, int H, int W, int C0, int C1, int ld0, int ld1,
-                               int up, long M, const void* dz, int ldz, int Nout, int KP, int taps, float* workspace, float* dw,
-                               hipStream_t st) {
-    return conv_gemm_tn_impl(x0, x1, mode, n_img, H, W, C0, C1, ld0, ld1, up, M, dz, ldz, Nout, KP, taps, 0, workspace, dw, nullptr, st);
+// The slab reduce of a plan: -1 = wgrad_reduce9_kernel (3x3 patch plans with few slabs: launched by run_gemm_tn even when deferred), else
+// the hn_wgrad_reduce_jobs kind: 0 = wgrad_reduce4_kernel, 1 = wgrad_reduce_kernel, 2 = gconv_diag_extract_kernel (grouped)
+static int wgrad_reduce_kind(const WgradPlan& q, bool grouped, int Nout, int KP, int taps) {
+    if (grouped) return 2;
+    if (q.patch && taps == 9 && q.splits <= 64) return -1;
+    return (q.splits <= 128 && (long)Nout * taps * KP >= 65536) ? 0 : 1;
 }
-/* hn_conv_gemm_tn without its slab reduce: job [8] (host) receives {part, dw, splits, Nout, Cin, KP, taps, kind} for hn_wgrad_reduce_jobs,
- * which reduces up to four such jobs in one launch (kind -1: the reduce was launched here after all -- the transposing 3x3 form). */
-static thread_local long* g_defer_job = nullptr;
-extern "C" int hn_conv_gemm_tn_deferred(const void* x0, const void* x1, int mode, int n_img, int H, int W, int C0, int C1, int ld0, int ld1,
-                                        int up, long M, const void* dz, int ldz, int Nout, int KP, int taps, float* workspace, float* dw,
-                                        long* job, hipStream_t st) {
-    HN_CHECK_ARG(job);
-    g_defer_job = job;
-    const int rc = conv_gemm_tn_impl(x0, x1, mode, n_img, H, W, C0, C1, ld0, ld1, up, M, dz, ldz, Nout, KP, taps, 0, workspace, dw, nullptr, st);
-    g_defer_job = nullptr;
-    return rc;
+
+static int wgrad_plan_query(int mode, int n_img, int H, int W, long M, int Nout, int KP, int taps, int phase_span, int* splits,
+                            long* rows_per_split, long* ws_bytes) {
+    HN_CHECK_ARG(splits && rows_per_split && ws_bytes);
+    WgradPlan q;
+    const int rc = wgrad_plan(q, make_xsrc(nullptr, nullptr, mode, H, W, 0, 0, 0, 0, 0, M), n_img, Nout, KP, taps, phase_span);
+    if (rc != HN_OK) return rc;
+    *splits = q.splits; *rows_per_split = q.rows_per_split; *ws_bytes = q.ws_bytes;
+    return HN_OK;
+}
+// plan the pixel split for wgrad: returns splits, rows per split (multiple of 64; patches per split for the 3x3 patch kernel) and the
+// fp32 workspace size in bytes
+extern "C" int hn_wgrad_plan(int mode, int n_img, int H, int W, long M, int Nout, int KP, int taps, int* splits, long* rows_per_split,
+                             long* ws_bytes) {
+    return wgrad_plan_query(mode, n_img, H, W, M, Nout, KP, taps, 0, splits, rows_per_split, ws_bytes);
+}
+/* plan of hn_conv_gemm_tn_phase (phase_span = couts per phase) */
+extern "C" int hn_wgrad_plan_phase(int n_img, int H, int W, int Nout, int KP, int phase_span, int* splits, long* rows_per_split, long* ws_bytes) {
+    return wgrad_plan_query(4, n_img, H, W, (long)n_img * H * W, Nout, KP, 9, phase_span, splits, rows_per_split, ws_bytes);
 }
 extern "C" int hn_wgrad_reduce_jobs(const long* jobs, int njobs, hipStream_t st) {
     HN_CHECK_ARG(jobs && njobs >= 0 && njobs <= 4);
@@ -4112,6 +4097,98 @@ extern "C" int hn_gconv_wgrad_group(const long* jobs, int njobs, float* workspac
     HN_LAUNCH_CHECK();
 }
 
+// Every TN (weight-gradient) launch.  job (hn_conv_gemm_tn_deferred, else null) receives {part, dw, splits, Nout, Cin, KP, taps, kind}
+// for hn_wgrad_reduce_jobs instead of the slab reduce being launched here (kind -1: it was launched here after all).
+static int run_gemm_tn(GemmTN& p, int n_img, float* workspace, float* dw, float* dbias, long* job, hipStream_t st) {
+    const XSrc& x = p.x;
+    const int Nout = p.Nout, KP = p.KP, taps = p.taps, cin = x.C0 + x.C1;
+    HN_CHECK_ARG(x.x0 && p.dz && workspace && dw && x.M > 0 && (KP & 31) == 0 && (p.ldz & 7) == 0 && p.ldz >= ((Nout + 7) & ~7));
+    HN_CHECK_ARG((x.C0 & 7) == 0 && (x.C1 & 7) == 0 && (x.ld0 & 7) == 0 && x.mode >= 0 && x.mode <= 2 && (!x.clamp || (x.up == 0 && x.C1 == 0)));
+    HN_CHECK_ARG(!x.diag || (KP == 64 && Nout == x.C0 && taps == 9));
+    HN_CHECK_ARG(x.mode == 0 || (long)n_img * x.H * x.W == x.M);
+    WgradPlan q;
+    int rc = wgrad_plan(q, x, n_img, Nout, KP, taps, p.phase_span);
+    if (rc != HN_OK) return rc;
+    const int reduce = wgrad_reduce_kind(q, x.diag, Nout, KP, taps);
+    if (job) {
+        job[0] = (long)workspace; job[1] = (long)dw; job[2] = q.splits; job[3] = Nout; job[4] = cin; job[5] = KP; job[6] = taps; job[7] = reduce;
+    }
+    if (dbias && (x.diag || job)) return HN_ERR_UNSUPPORTED;
+    p.part = workspace; p.rows_per_split = q.rows_per_split;
+    if (dbias) p.bias_part = workspace + (long)q.splits * Nout * taps * KP;
+    if (q.patch) {
+        static std::atomic<unsigned long long> optin{0};
+        if (!lds_optin(optin, {(const void*)wgrad3x3_patch_kernel<128, 64>, (const void*)wgrad3x3_patch_kernel<16, 64>,
+                               (const void*)wgrad3x3_patch_kernel<64, 64>, (const void*)wgrad3x3_patch_kernel<32, 64>,
+                               (const void*)wgrad3x3_patch_kernel<128, 32>, (const void*)wgrad3x3_patch_kernel<128, 64, 1>,
+                               (const void*)wgrad3x3_patch_kernel<64, 64, 1>, (const void*)wgrad3x3_patch_kernel<128, 32, 1>}))
+            return HN_ERR_LAUNCH;
+        const int pbc = q.bc, pci = q.bn, rps = (int)q.rows_per_split, patches = (int)q.patches;
+        const bool phase = p.phase_span != 0;
+        p.gy = cdiv(Nout, pbc);
+        dim3 grid((unsigned)(cdiv(KP, pci) * p.gy * (q.splits / q.ksplit)));
+        const size_t xb = (size_t)((180 * (pci / 8) + 511) / 512) * 512 * 16;
+        const size_t lds = 2 * ((size_t)((128 * pbc * 2 + 1023) / 1024 * 1024) + xb) + 2 * 56 * sizeof(int);   // + the two patch source tables
+        if (x.diag) hipLaunchKernelGGL((wgrad3x3_patch_kernel<64, 64>), grid, dim3(512), lds, st, p, rps, patches);
+        else if (phase && pbc == 128 && pci == 32) hipLaunchKernelGGL((wgrad3x3_patch_kernel<128, 32, 1>), grid, dim3(512), lds, st, p, rps, patches);
+        else if (phase && pbc == 128) hipLaunchKernelGGL((wgrad3x3_patch_kernel<128, 64, 1>), grid, dim3(512), lds, st, p, rps, patches);
+        else if (phase) hipLaunchKernelGGL((wgrad3x3_patch_kernel<64, 64, 1>), grid, dim3(512), lds, st, p, rps, patches);   // (phase_span >= 64)
+        else if (pbc == 128 && pci == 32) hipLaunchKernelGGL((wgrad3x3_patch_kernel<128, 32>), grid, dim3(512), lds, st, p, rps, patches);
+        else if (pbc == 128) hipLaunchKernelGGL((wgrad3x3_patch_kernel<128, 64>), grid, dim3(512), lds, st, p, rps, patches);
+        else if (pbc == 64) hipLaunchKernelGGL((wgrad3x3_patch_kernel<64, 64>), grid, dim3(512), lds, st, p, rps, patches);
+        else if (pbc == 32) hipLaunchKernelGGL((wgrad3x3_patch_kernel<32, 64>), grid, dim3(512), lds, st, p, rps, patches);
+        else hipLaunchKernelGGL((wgrad3x3_patch_kernel<16, 64>), grid, dim3(512), lds, st, p, rps, patches);
+        if (hipGetLastError() != hipSuccess) return HN_ERR_LAUNCH;
+    } else {
+        const int bc = q.bc, bn = q.bn;
+#define TN_CASE(BC_, BN_, A_, B_) if (bc == BC_ && bn == BN_) rc = launch_tn<BC_, BN_, A_, B_>(p, q.splits, st); else
+        TN_CASE(128, 128, 2, 2) TN_CASE(128, 64, 2, 2) TN_CASE(128, 32, 4, 1)
+        TN_CASE(64, 128, 2, 2) TN_CASE(64, 64, 2, 2) TN_CASE(64, 32, 4, 1)
+        TN_CASE(32, 128, 1, 4) TN_CASE(32, 64, 1, 4) TN_CASE(32, 32, 2, 2)
+        TN_CASE(16, 128, 1, 4) TN_CASE(16, 64, 1, 4)
+        rc = HN_ERR_UNSUPPORTED;
+#undef TN_CASE
+        if (rc != HN_OK) return rc;
+    }
+    if (job && reduce >= 0) return HN_OK;
+    const long cols = (long)Nout * taps * KP;
+    if (reduce == 2)
+        hipLaunchKernelGGL(gconv_diag_extract_kernel, dim3(cdiv(Nout * 72, 256)), dim3(256), 0, st, workspace, dw, q.splits, Nout);
+    else if (reduce == -1)
+        hipLaunchKernelGGL(wgrad_reduce9_kernel, dim3(cdiv(cin, 64), Nout), dim3(256), 0, st, workspace, dw, q.splits, Nout, cin, KP,
+                           p.bias_part, dbias);
+    else if (reduce == 0)
+        hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3(cdiv(cols / 4, 256)), dim3(256), 0, st, workspace, dw, q.splits, Nout, cin, KP, taps,
+                           p.bias_part, dbias);
+    else
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(cols, 32)), dim3(512), 0, st, workspace, dw, q.splits, Nout, cin, KP, taps,
+                           p.bias_part, dbias);
+    HN_LAUNCH_CHECK();
+}
+
+static GemmTN tn_desc(const void* x0, const void* x1, int mode, int H, int W, int C0, int C1, int ld0, int ld1, int up, long M,
+                      const void* dz, int ldz, int Nout, int KP, int taps) {
+    GemmTN p{};
+    p.x = make_xsrc(x0, x1, mode, H, W, C0, C1, ld0, ld1, up, M);
+    p.dz = (const bf16*)dz; p.ldz = ldz; p.Nout = Nout; p.KP = KP; p.taps = taps;
+    return p;
+}
+
+extern "C" int hn_conv_gemm_tn(const void* x0, const void* x1, int mode, int n_img, int H, int W, int C0, int C1, int ld0, int ld1,
+                               int up, long M, const void* dz, int ldz, int Nout, int KP, int taps, float* workspace, float* dw,
+                               hipStream_t st) {
+    GemmTN p = tn_desc(x0, x1, mode, H, W, C0, C1, ld0, ld1, up, M, dz, ldz, Nout, KP, taps);
+    return run_gemm_tn(p, n_img, workspace, dw, nullptr, nullptr, st);
+}
+/* hn_conv_gemm_tn without its slab reduce: job [8] (host) receives {part, dw, splits, Nout, Cin, KP, taps, kind} for hn_wgrad_reduce_jobs,
+ * which reduces up to four such jobs in one launch (kind -1: the reduce was launched here after all -- the transposing 3x3 form). */
+extern "C" int hn_conv_gemm_tn_deferred(const void* x0, const void* x1, int mode, int n_img, int H, int W, int C0, int C1, int ld0, int ld1,
+                                        int up, long M, const void* dz, int ldz, int Nout, int KP, int taps, float* workspace, float* dw,
+                                        long* job, hipStream_t st) {
+    HN_CHECK_ARG(job);
+    GemmTN p = tn_desc(x0, x1, mode, H, W, C0, C1, ld0, ld1, up, M, dz, ldz, Nout, KP, taps);
+    return run_gemm_tn(p, n_img, workspace, dw, nullptr, job, st);
+}
 /* hn_conv_gemm_tn that also returns the conv's bias gradient dbias [Nout] = column sums of dz -- accumulated by one extra MFMA per k-step
  * while the dz fragments are in registers, reduced by the launch that reduces the weight-gradient slabs: no column-statistics pass over
  * dz, no extra reduce launches (not for the grouped mode 5). */
@@ -4119,7 +4196,8 @@ extern "C" int hn_conv_gemm_tn_bias(const void* x0, const void* x1, int mode, in
                                     int up, long M, const void* dz, int ldz, int Nout, int KP, int taps, float* workspace, float* dw,
                                     float* dbias, hipStream_t st) {
     HN_CHECK_ARG(dbias);
-    return conv_gemm_tn_impl(x0, x1, mode, n_img, H, W, C0, C1, ld0, ld1, up, M, dz, ldz, Nout, KP, taps, 0, workspace, dw, dbias, st);
+    GemmTN p = tn_desc(x0, x1, mode, H, W, C0, C1, ld0, ld1, up, M, dz, ldz, Nout, KP, taps);
+    return run_gemm_tn(p, n_img, workspace, dw, dbias, nullptr, st);
 }
 /* weight gradient of the phase-form conv (hn_conv3x3_phase mode 4): x0 = low-resolution input [N][H][W][C0], dz = space-to-depth output
  * gradient [N][H][W][Nout = 4*k] (hn_space_to_depth_bf16), dw = gradient of the EFFECTIVE weights fp32 [4*k][C0][3][3] (zeros at the
@@ -4127,99 +4205,9 @@ extern "C" int hn_conv_gemm_tn_bias(const void* x0, const void* x1, int mode, in
 extern "C" int hn_conv_gemm_tn_phase(const void* x0, int n_img, int H, int W, int C0, int ld0, const void* dz, int ldz, int Nout, int KP,
                                      int phase_span, float* workspace, float* dw, float* dbias_eff, hipStream_t st) {
     HN_CHECK_ARG(phase_span >= 64 && phase_span % 64 == 0 && Nout == 4 * phase_span && KP >= 64);
-    return conv_gemm_tn_impl(x0, nullptr, 4, n_img, H, W, C0, 0, ld0, 0, 0, (long)n_img * H * W, dz, ldz, Nout, KP, 9, phase_span, workspace, dw,
-                             dbias_eff, st);
-}
-static int conv_gemm_tn_impl(const void* x0, const void* x1, int mode, int n_img, int H, int W, int C0, int C1, int ld0, int ld1,
-                             int up, long M, const void* dz, int ldz, int Nout, int KP, int taps, int phase_span, float* workspace, float* dw,
-                             float* dbias, hipStream_t st) {
-    HN_CHECK_ARG(x0 && dz && workspace && dw && M > 0 && (KP & 31) == 0 && (ldz & 7) == 0 && ldz >= ((Nout + 7) & ~7));
-    HN_CHECK_ARG((C0 & 7) == 0 && (C1 & 7) == 0 && (ld0 & 7) == 0 && ((mode >= 0 && mode <= 2) || ((mode == 4 || mode == 5) && up == 0 && C1 == 0)));
-    HN_CHECK_ARG(mode != 5 || (KP == 64 && Nout == C0 && taps == 9));
-    const int grouped = mode == 5;
-    HN_CHECK_ARG(mode == 0 || (long)n_img * H * W == M);
-    int splits; long rps, wsb;
-    wgrad_plan_impl(mode, n_img, H, W, M, Nout, KP, taps, phase_span, &splits, &rps, &wsb);
-    GemmTN p;
-    p.x = make_xsrc(x0, x1, mode, n_img, H, W, C0, C1, ld0, ld1, up, M);
-    mode = p.x.mode;
-    p.dz = (const bf16*)dz; p.ldz = ldz; p.Nout = Nout; p.KP = KP; p.taps = taps;
-    p.part = workspace; p.rows_per_split = rps; p.phase_span = phase_span;
-    p.bias_part = nullptr; p.out_ld = 0; p.cin_lim = 0; p.dbg = 0;
-    int bc, bn, rc;
-    long* defer = g_defer_job;
-    g_defer_job = nullptr;
-    if (defer) {
-        defer[0] = (long)workspace; defer[1] = (long)dw; defer[2] = splits; defer[3] = Nout; defer[4] = C0 + C1; defer[5] = KP; defer[6] = taps;
-        defer[7] = -1;
-    }
-    if (dbias && (grouped || defer)) return HN_ERR_UNSUPPORTED;
-    if (dbias) p.bias_part = workspace + (long)splits * Nout * taps * KP;
-    if (use_patch_wgrad(mode, Nout, KP)) {
-        static std::atomic<unsigned long long> optin{0};
-        if (!lds_optin(optin, {(const void*)wgrad3x3_patch_kernel<128, 64>, (const void*)wgrad3x3_patch_kernel<16, 64>,
-                               (const void*)wgrad3x3_patch_kernel<64, 64>, (const void*)wgrad3x3_patch_kernel<32, 64>,
-                               (const void*)wgrad3x3_patch_kernel<128, 32>, (const void*)wgrad3x3_patch_kernel<128, 64, 1>,
-                               (const void*)wgrad3x3_patch_kernel<64, 64, 1>, (const void*)wgrad3x3_patch_kernel<128, 32, 1>}))
-            return HN_ERR_LAUNCH;
-        int pbc, pci, ksplit;
-        patch_tiles(Nout, KP, pbc, pci, ksplit);
-        if (grouped) { pbc = 64; pci = 64; ksplit = 2; }
-        if (phase_span && phase_span < pbc) { pbc = 64; pci = 64; ksplit = 2; }
-        p.gy = cdiv(Nout, pbc);
-        const int patches = n_img * cdiv(H, 8) * cdiv(W, 16);
-        dim3 grid((unsigned)(cdiv(KP, pci) * p.gy * (splits / ksplit)));
-        const size_t xb = (size_t)((180 * (pci / 8) + 511) / 512) * 512 * 16;
-        const size_t lds = 2 * ((size_t)((128 * pbc * 2 + 1023) / 1024 * 1024) + xb) + 2 * 56 * sizeof(int);   // + the two patch source tables
-        if (grouped) hipLaunchKernelGGL((wgrad3x3_patch_kernel<64, 64>), grid, dim3(512), lds, st, p, (int)rps, patches);
-        else if (phase_span && pbc == 128 && pci == 32) hipLaunchKernelGGL((wgrad3x3_patch_kernel<128, 32, 1>), grid, dim3(512), lds, st, p, (int)rps, patches);
-        else if (phase_span && pbc == 128) hipLaunchKernelGGL((wgrad3x3_patch_kernel<128, 64, 1>), grid, dim3(512), lds, st, p, (int)rps, patches);
-        else if (phase_span) hipLaunchKernelGGL((wgrad3x3_patch_kernel<64, 64, 1>), grid, dim3(512), lds, st, p, (int)rps, patches);   // (phase_span >= 64)
-        else if (pbc == 128 && pci == 32) hipLaunchKernelGGL((wgrad3x3_patch_kernel<128, 32>), grid, dim3(512), lds, st, p, (int)rps, patches);
-        else if (pbc == 128) hipLaunchKernelGGL((wgrad3x3_patch_kernel<128, 64>), grid, dim3(512), lds, st, p, (int)rps, patches);
-        else if (pbc == 64) hipLaunchKernelGGL((wgrad3x3_patch_kernel<64, 64>), grid, dim3(512), lds, st, p, (int)rps, patches);
-        else if (pbc == 32) hipLaunchKernelGGL((wgrad3x3_patch_kernel<32, 64>), grid, dim3(512), lds, st, p, (int)rps, patches);
-        else hipLaunchKernelGGL((wgrad3x3_patch_kernel<16, 64>), grid, dim3(512), lds, st, p, (int)rps, patches);
-        if (hipGetLastError() != hipSuccess) return HN_ERR_LAUNCH;
-        const long cols = (long)Nout * taps * KP;
-        if (defer && (grouped || !(taps == 9 && splits <= 64))) {
-            defer[7] = grouped ? 2 : ((splits <= 128 && cols >= 65536) ? 0 : 1);
-            return HN_OK;
-        }
-        if (grouped)
-            hipLaunchKernelGGL(gconv_diag_extract_kernel, dim3(cdiv(Nout * 72, 256)), dim3(256), 0, st, workspace, dw, splits, Nout);
-        else if (taps == 9 && splits <= 64)
-            hipLaunchKernelGGL(wgrad_reduce9_kernel, dim3(cdiv(C0 + C1, 64), Nout), dim3(256), 0, st, workspace, dw, splits, Nout, C0 + C1, KP,
-                               p.bias_part, dbias);
-        else if (splits <= 128 && cols >= 65536)
-            hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3(cdiv(cols / 4, 256)), dim3(256), 0, st, workspace, dw, splits, Nout, C0 + C1, KP, taps,
-                               p.bias_part, dbias);
-        else
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(cols, 32)), dim3(512), 0, st, workspace, dw, splits, Nout, C0 + C1, KP, taps,
-                               p.bias_part, dbias);
-        HN_LAUNCH_CHECK();
-    }
-    tn_tiles(Nout, KP, bc, bn);
-#define TN_CASE(BC_, BN_, A_, B_) if (bc == BC_ && bn == BN_) rc = launch_tn<BC_, BN_, A_, B_>(p, splits, st); else
-    TN_CASE(128, 128, 2, 2) TN_CASE(128, 64, 2, 2) TN_CASE(128, 32, 4, 1)
-    TN_CASE(64, 128, 2, 2) TN_CASE(64, 64, 2, 2) TN_CASE(64, 32, 4, 1)
-    TN_CASE(32, 128, 1, 4) TN_CASE(32, 64, 1, 4) TN_CASE(32, 32, 2, 2)
-    TN_CASE(16, 128, 1, 4) TN_CASE(16, 64, 1, 4)
-    rc = HN_ERR_UNSUPPORTED;
-#undef TN_CASE
-    if (rc != HN_OK) return rc;
-    const long cols = (long)Nout * taps * KP;
-    if (defer) {
-        defer[7] = (splits <= 128 && cols >= 65536) ? 0 : 1;
-        return HN_OK;
-    }
-    if (splits <= 128 && cols >= 65536)
-        hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3(cdiv(cols / 4, 256)), dim3(256), 0, st, workspace, dw, splits, Nout, C0 + C1, KP, taps,
-                           p.bias_part, dbias);
-    else
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(cols, 32)), dim3(512), 0, st, workspace, dw, splits, Nout, C0 + C1, KP, taps,
-                           p.bias_part, dbias);
-    HN_LAUNCH_CHECK();
+    GemmTN p = tn_desc(x0, nullptr, 4, H, W, C0, 0, ld0, 0, 0, (long)n_img * H * W, dz, ldz, Nout, KP, 9);
+    p.phase_span = phase_span;
+    return run_gemm_tn(p, n_img, workspace, dw, dbias_eff, nullptr, st);
 }
 
 /* jobs: DEVICE table of njobs x 8 int64 {w, wp, wt, Cout, Cin, taps, first_block, ci_tiles}; job j owns blocks [first_block_j,

@@ -35,6 +35,25 @@ def test_library_exports_every_declared_symbol(built):
     assert l.query("hn_wgrad_plan", 0, 16, 512, 1024, 16 * 512 * 1024, 64, 64, 1, ctypes.addressof(s), ctypes.addressof(r), ctypes.addressof(w)) == 0
     assert s.value >= 1 and r.value % 64 == 0 and s.value * r.value >= 16 * 512 * 1024
     assert w.value == s.value * 64 * 1 * 64 * 4 + s.value * 64 * 4        # fp32 slabs + the bias-gradient partial rows
+    # the weight-gradient plans of the training step's shapes (16 x 512 x 1024), as the library has always made them:
+    # (mode, n, H, W, M, Nout, KP, taps) -> (splits, rows or patches per split, workspace bytes)
+    plans = {(0, 16, 16, 32, 8192, 936, 960, 1): (32, 256, 115135488),              # stage-4 1x1: row gather
+             (0, 16, 32, 64, 32768, 376, 384, 1): (128, 256, 74117120),             # stage-3 1x1
+             (2, 16, 128, 256, 16 * 128 * 256, 128, 32, 9): (512, 16, 75759616),     # 3x3 patch kernel, KP 32, Nout > 64 (128 x 32 tiles)
+             (2, 16, 256, 512, 16 * 256 * 512, 20, 64, 9): (1024, 32, 47267840),     # 3x3 patch kernel, Nout <= 32
+             (5, 16, 32, 64, 16 * 32 * 64, 376, 64, 9): (86, 6, 74631488)}           # grouped 3x3 (stage 3)
+    for args, want in plans.items():
+        assert l.query("hn_wgrad_plan", *args, ctypes.addressof(s), ctypes.addressof(r), ctypes.addressof(w)) == 0
+        assert (s.value, r.value, w.value) == want, args
+    # phase-form convs: (n, H, W, Nout, KP, phase_span); a 64-cout phase narrows the 128-cout tile
+    for args, want in {(16, 128, 256, 256, 64, 64): (128, 64, 75628544), (16, 64, 128, 512, 128, 128): (32, 32, 75563008)}.items():
+        assert l.query("hn_wgrad_plan_phase", *args, ctypes.addressof(s), ctypes.addressof(r), ctypes.addressof(w)) == 0
+        assert (s.value, r.value, w.value) == want, args
+    assert l.query("hn_wgrad_plan", 0, 16, 16, 32, 8192, 0, 960, 1, ctypes.addressof(s), ctypes.addressof(r), ctypes.addressof(w)) == 1
+    # statistics rows of the NT tiling on both sides of the small-tile choice, and of the direct kernel (one per 16 x 16 patch)
+    assert (l.query("hn_nt_stat_tile", 8192, 936), l.query("hn_nt_stat_rows", 8192, 936)) == (64, 128)      # stage 4: 64 x 64 tiles
+    assert (l.query("hn_nt_stat_tile", 32768, 376), l.query("hn_nt_stat_rows", 32768, 376)) == (128, 256)   # stage 3: 128-row tiles
+    assert l.query("hn_direct_stat_rows", 16, 32, 64) == 128 and l.query("hn_direct_stat_rows", 16, 33, 65) == 240
 
 
 def test_bad_arguments_are_rejected_without_a_gpu(built):
@@ -42,6 +61,19 @@ def test_bad_arguments_are_rejected_without_a_gpu(built):
     # null pointers / misaligned channel counts must come back as status 1 before any launch
     assert l.raw("hn_bn_act")(None, 8, None, None, None, 0, None, None, 0, None, 8, 4, 8, None) == 1
     assert l.raw("hn_dwconv_fwd")(1, 12, 1, 1, 12, 1, 4, 4, 12, None) == 1
+    # the conv GEMM entry points: every device pointer is null, so nothing could be launched even past the check under test
+    rows = np.array([128, 100], dtype=np.int64)                       # host table; a level of 100 rows is not a multiple of 128
+    hp = rows.ctypes.data
+    assert l.raw("hn_conv_gemm_nt")(None, None, 0, 1, 1, 8192, 64, 0, 64, 0, 0, 8192, None, 64, 64, 1, None, 0, None, 0, 64, 0, 0, None, None,
+                                    None) == 1
+    assert l.raw("hn_conv_gemm_nt_imgw")(None, 64, 8192, 64, None, 64 * 64, 100, 64, 64, None, 0, None, 64, None, 0, None) == 1
+    assert l.raw("hn_conv_gemm_nt_lvl")(None, 64, 228, 64, None, 64, 64, None, 0, None, 64, hp, 2, hp, None) == 1
+    assert l.raw("hn_conv_gemm_nt_lvl")(None, 64, 128, 64, None, 64, 64, None, 0, None, 64, None, 1, hp, None) == 1
+    assert l.raw("hn_conv_gemm_nt_stat3")(None, 64, 8192, 64, None, 64, 64, None, 64, None, None, None, 64, None, 64, None, 64, None, None) == 1
+    assert l.raw("hn_conv3x3_out_argmax")(None, 1, 16, 16, 64, 64, None, 9, 64, None, None, None) == 1
+    assert l.raw("hn_conv3x3_dgrad_fold")(None, 64, 64, 1, 16, 16, None, 64, 64, 0, 0, None, 64, None, 0, None, None) == 1
+    assert l.raw("hn_conv_gemm_tn_deferred")(None, None, 0, 1, 1, 8192, 64, 0, 64, 0, 0, 8192, None, 64, 64, 64, 1, None, None, None,
+                                             None) == 1
 
 
 def test_state_dict_contract_matches_reference(built):
