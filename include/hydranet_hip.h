@@ -602,6 +602,23 @@ int hn_adam_step(const long* jobs, const int* block_job, long total_blocks, doub
  * block; kind 0: fp32 -> fp32, 1: fp32 -> bf16 (reduced-precision payload), 2: bf16 -> fp32. */
 int hn_copy_many(const long* jobs, const int* block_job, long total_blocks, int kind, hipStream_t stream);
 
+/* COCO box mAP (pycocotools COCOeval(..., 'bbox') evaluate + accumulate; hn_coco.hip, parity rules in its header comment).
+ * hn_coco_match: one workgroup per (image, category) cell.  cells (DEVICE int32 [n_cells][4]) = {gt cell = image order * K + category,
+ * first detection, detection count, first output record}; dets fp64 [n][5] = x, y, w, h, score (an fp32 value); gt_off int32
+ * [images * K + 1] = CSR offsets of gt fp64 [G][5] = x, y, w, h, area (annotation order per cell); prm fp64 = T IoU thresholds
+ * (min(iouThr, 1 - 1e-10)) then the 4 area ranges [4][2]; T <= 16; gtm_ws: hn_coco_match_ws_bytes(G) bytes (matched flags of cells with
+ * more than 256 GTs).  Writes min(count, 100) records of 8 int32 per cell: {score fp32 bits, image order * 128 + rank, category, 0,
+ * per area range (matched bits 0..T-1 | ignored bits 16..16+T-1)}.
+ * hn_coco_accumulate: rec [N][8] (N < 2^31), iprm (DEVICE int32) = category starts [K + 1] of the records in category order, npig [K][4],
+ * maxDets [M]; rec_thrs fp64 [R <= 128]; seq_bits >= bit length of the largest record sequence; ws: hn_coco_accumulate_ws_bytes(N).
+ * precision fp64 [T][R][K][4][M], recall [T][K][4][M] (-1 where npig == 0). */
+long hn_coco_match_ws_bytes(long n_gt);
+int hn_coco_match(const int* cells, int n_cells, const double* dets, const int* gt_off, const double* gt, const double* prm, int K, int T,
+                  void* gtm_ws, int* rec, hipStream_t stream);
+long hn_coco_accumulate_ws_bytes(long N);
+int hn_coco_accumulate(const int* rec, long N, int K, int seq_bits, const int* iprm, const double* rec_thrs, int T, int R, int M, void* ws,
+                       double* precision, double* recall, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -303,13 +303,18 @@ class HydraTrainer:
               "  ".join("%s %.3f" % (k, float(v.detach())) for k, v in loss_dict.items()))
 
     @torch.no_grad()
-    def valid(self, epoch: int = 0, eval_dir: Optional[str] = None, lane_coder=None, det_conf_thres: float = 0.3, det_iou_thres: float = 0.3):
+    def valid(self, epoch: int = 0, eval_dir: Optional[str] = None, lane_coder=None, det_conf_thres: float = 0.3, det_iou_thres: float = 0.3,
+              coco_gt=None):
         """train.py:271-438 without the third-party evaluators: eval-mode forward + the six losses per batch, streaming mIoU on the device
         (train.py:293-306), detection results through the device post-process in COCO-json form (train.py:308-364; written to
         `eval_dir`/val_bbox_results.json like train.py:416-421 -- the file COCOeval reads), lane decode + NMS on the device and the
         prediction json of LaneHeader.scale_to_org (train.py:366-395) when a `lane_coder` (LaneCodec) is given, and -- when the batches carry
         the ground-truth lanes of train.py:393 as `gt_lane_json` (one {"Lines": [...], "Labels": [...]} dict per image) -- the lane F1 of
-        train.py:188,397,433 (LaneMetric, f1_measure, IoU 0.5, width 30, score threshold 0.5).  COCOeval needs pycocotools (out of scope).
+        train.py:188,397,433 (LaneMetric, f1_measure, IoU 0.5, width 30, score threshold 0.5).  With `coco_gt` (the GT dataset dict of
+        coco_json.coco_ground_truth or a path to gt_bbox_results.json) and detection trained, the COCO bbox mAP of train.py:416-426 on the
+        device (det_eval.CocoBoxEvaluator over the GT's first detection.max_images images, every batch's boxes as the json records them):
+        last_valid["det_eval"] = its compute() (dict(stats, precision, recall), None without any detection) and rank 0 prints the
+        "metric detection" block.  At world size > 1 only rank 0's images are evaluated, as only rank 0's records are written (no gather).
         Deliberate deviation: train.py:397 calls `self.lane_metric(output=lane_result)` inside the batch loop with the CUMULATIVE list, so the
         reference counts image k of a validation run (number of batches - batch index of k) times, and never resets the evaluator between
         epochs; here every image is scored exactly once per valid() call (for a single-batch validation the two agree).
@@ -323,6 +328,10 @@ class HydraTrainer:
         if self.train_seg:
             self.metric_evaluator_iou = IntersectionOverUnion(n_classes=self.metric_evaluator_iou.n_classes, device=self.device)
         detect_result, lane_result, losses = [], [], []
+        det_eval = None
+        if coco_gt is not None and self.train_detect and self.rank == 0:
+            from .det_eval import CocoBoxEvaluator
+            det_eval = CocoBoxEvaluator(coco_gt, max_images=self.cfgs["detection"].get("max_images", 10000), device=self.device)
         net_w, net_h = net.net_input_width, net.net_input_height
         for iter_idx, batch_data in enumerate(self.validloader):
             batch_data = self.to_gpu(batch_data)
@@ -347,7 +356,10 @@ class HydraTrainer:
                                                 iou_thres=det_iou_thres)
                 metas = [[net_w, net_h, sh["width"], sh["height"], 0, 0] for sh in shapes]
                 preds = net.detectheader.invert_affine(metas, preds)                                       # train.py:334-336
-                detect_result += detections_to_coco(preds, iter_idx * self.cfgs["train"].get("batch_size_valid", n) + 1)
+                first_id = iter_idx * self.cfgs["train"].get("batch_size_valid", n) + 1
+                detect_result += detections_to_coco(preds, first_id)
+                if det_eval is not None:
+                    det_eval.update(preds, first_id)
             if self.train_lane and lane_coder is not None:
                 l = self.cfgs["lane"]
                 lanes = net.laneheader.decode_batch(outputs["lane"]["predict_cls"], outputs["lane"]["predict_loc"], lane_coder,
@@ -369,6 +381,13 @@ class HydraTrainer:
                 print("=========================== metric lane %i ===========================" % epoch)
                 print(lane_f1)
         self.last_valid = dict(losses=losses, detect_result=detect_result, detect_json=path, lane_result=lane_result, iou=scores, lane_f1=lane_f1)
+        if coco_gt is not None and self.train_detect:
+            res = det_eval.compute() if det_eval is not None else None
+            if self.rank == 0:
+                print("=========================== metric detection %i ===========================" % epoch)         # train.py:414
+                if res is not None:
+                    print("\n".join(det_eval.summary()))
+            self.last_valid["det_eval"] = res
         return scores
 
     def save(self, path: str):
