@@ -25,7 +25,9 @@
 //
 // Synchronisation.  In-image exchanges (bg, out, SE partials): plain stores, every storing wave's vmcnt(0), workgroup barrier, one arrival
 // on a per-image counter; consumers poll it and then read through the XCD's L2 (activation tensors are written once per launch, so no CU's
-// L1 can hold an older copy; the small vectors are read with sc1 loads).  LOCAL = true: the counters are L2-resident (workgroup-scope
+// L1 can hold an older copy: the L1 starts the launch empty, every plain or LDS-DMA load of a handed-off tile comes behind the wait for it,
+// and the only earlier accesses -- touch_tile's warming reads of tiles not yet written -- are sc1 loads, which leave nothing in the L1;
+// the small vectors are read with sc1 loads).  LOCAL = true: the counters are L2-resident (workgroup-scope
 // read-modify-writes execute in the shared L2: 1.0 us per round measured, profiles/r05_xcd_sync_probe.txt) -- valid because co-location was
 // READ from the hardware, not assumed; LOCAL = false: agent-scope counters, release / acquire fences around the payload (placement
 // independent, slower; kept as the checked fallback form).  Cross-XCD: granules only.  Every spin is bounded (XS_TIMEOUT_TICKS of the 100 MHz
@@ -433,13 +435,16 @@ struct XsWg {
     }
     // Lines whose FIRST touch is a write are not served from the L2 afterwards (tools/xstage/feed_probe.hip: the image's 240 KB stream in
     // 6.3 us from a tile written to untouched lines, in 3.7 us when the lines had been read before): the tile a GEMM of the other workgroups
-    // will stream is touched (one dword per 64 bytes, waves 4-7) a few microseconds before it is written.
-    __device__ __forceinline__ void touch_tile(const bf16* dst) {
+    // will stream is touched (one dword per 64 bytes, waves 4-7) a few microseconds before it is written.  The touch loads are sc1 (agent-scope
+    // relaxed atomic loads, as xs_peek): the lines straddle the neighbouring slices, which other workgroups have not written yet, and a plain
+    // load would leave that stale copy in this CU's L1 for the GEMM's global_load_lds to hit once the image's counter says the tile is there.
+    __device__ __forceinline__ void touch_tile(bf16* dst) {
         const int t2 = tid & 255;
         if (wave < 4) return;
         for (int r = t2 >> 1; r < HW; r += 128) {
             const int off = (t2 & 1) * 32;
-            if (off < SLv) touched += *reinterpret_cast<const unsigned*>(dst + ((long)img * HW + r) * C + c0 + off);
+            if (off < SLv)
+                touched += __hip_atomic_load((gu32*)(dst + ((long)img * HW + r) * C + c0 + off), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
     // Statistics of the slice over ALL images, in two steps so that other trips run under the wait: publish (this workgroup's two sums per

@@ -59,9 +59,15 @@ def xstage_ok(x, w1, cs) -> bool:
     return w1.shape[0] == c and w1.shape[1] == c and lib().query("hn_xstage_supported", n, h, w, c, cs) != 0
 
 
-def xstage_forward_raw(x, params, eps, momentum, stamps=None, mode=None):
+def _out(shape, dev, dtype, fill):
+    """an output buffer of a persistent launch: torch.empty, or (tests) filled with `fill` so that an element the launch leaves unwritten, or
+    a stale line read before its write, cannot pass for the previous step's data"""
+    return torch.empty(shape, device=dev, dtype=dtype) if fill is None else torch.full(shape, fill, device=dev, dtype=dtype)
+
+
+def xstage_forward_raw(x, params, eps, momentum, stamps=None, mode=None, *, fill=None):
     """-> dict of the run's tensors.  params: nb * PER_BLOCK tensors (w1, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2, sw1, sb1, sw2, sb2, w3, g3,
-    b3, rm3, rv3 per block)."""
+    b3, rm3, rv3 per block).  fill: see _out."""
     nb = len(params) // PER_BLOCK
     n, h, w, c = x.shape
     dev = x.device
@@ -75,11 +81,11 @@ def xstage_forward_raw(x, params, eps, momentum, stamps=None, mode=None):
         wp3, wt3 = pack_conv_weight(w3)
         packs.append((wt1, wd2, wt3, None))
         tab[19 * b:19 * b + 19] = [t.data_ptr() for t in (wp1, wk2, wp3, sw1, sb1, sw2, sb2, g1, b1, rm1, rv1, g2, b2, rm2, rv2, g3, b3, rm3, rv3)]
-    acts = {k: torch.empty((nb, n, h, w, c), device=dev, dtype=BF16) for k in ("z1", "a", "z2", "bg", "z3", "out")}
-    coef = torch.empty((nb, 3, 4, c), device=dev, dtype=F32)
-    pooled = torch.empty((nb, n, c), device=dev, dtype=F32)
-    hid = torch.empty((nb, n, cs), device=dev, dtype=F32)
-    gate = torch.empty((nb, n, c), device=dev, dtype=F32)
+    acts = {k: _out((nb, n, h, w, c), dev, BF16, fill) for k in ("z1", "a", "z2", "bg", "z3", "out")}
+    coef = _out((nb, 3, 4, c), dev, F32, fill)
+    pooled = _out((nb, n, c), dev, F32, fill)
+    hid = _out((nb, n, cs), dev, F32, fill)
+    gate = _out((nb, n, c), dev, F32, fill)
     ws, status = xstage_ws(dev)
     lib().call("hn_xstage_fwd", ctypes.addressof(tab), nb, ptr(x), ptr(acts["z1"]), ptr(acts["a"]), ptr(acts["z2"]), ptr(acts["bg"]),
                ptr(acts["z3"]), ptr(acts["out"]), ptr(coef), ptr(pooled), ptr(hid), ptr(gate), n, h, w, c, cs, float(eps), float(momentum),
@@ -99,9 +105,10 @@ def xstage_forward_raw(x, params, eps, momentum, stamps=None, mode=None):
 XSTAGE_BWD = policy("HN_XSTAGE_BWD", "1") != "0"  # the run's backward as one persistent launch too (0: XBlockFn.backward per block)
 
 
-def xstage_backward_raw(dout, r_or_saved, packs, sws, stamps=None, mode=None):
+def xstage_backward_raw(dout, r_or_saved, packs, sws, stamps=None, mode=None, *, fill=None):
     """hn_xstage_bwd on the stacked forward tensors -> dict(dz1, dz2, dz3 [nb, n, h, w, c], dx, dgb [nb, 3, 2, c], dpre2, dpre1).
-    r_or_saved: dict with z1, z2, z3, out, coef, hid, gate; packs: per block (wt1, wd2, wt3, ...); sws: per block (se.1.weight, se.3.weight)."""
+    r_or_saved: dict with z1, z2, z3, out, coef, hid, gate; packs: per block (wt1, wd2, wt3, ...); sws: per block (se.1.weight, se.3.weight).
+    fill: see _out."""
     z1, z2, z3, out, coef, hid, gate = (r_or_saved[k] for k in ("z1", "z2", "z3", "out", "coef", "hid", "gate"))
     nb, n, h, w, c = z1.shape
     cs = hid.shape[2]
@@ -109,11 +116,11 @@ def xstage_backward_raw(dout, r_or_saved, packs, sws, stamps=None, mode=None):
     tab = (ctypes.c_long * (5 * nb))()
     for b in range(nb):
         tab[5 * b:5 * b + 5] = [packs[b][0].data_ptr(), packs[b][1].data_ptr(), packs[b][2].data_ptr(), sws[b][0].data_ptr(), sws[b][1].data_ptr()]
-    dz = {k: torch.empty((nb, n, h, w, c), device=dev, dtype=BF16) for k in ("dz1", "dz2", "dz3")}
-    dx = torch.empty((n, h, w, c), device=dev, dtype=BF16)
-    dgb = torch.empty((nb, 3, 2, c), device=dev, dtype=F32)
-    dpre2 = torch.empty((nb, n, c), device=dev, dtype=F32)
-    dpre1 = torch.empty((nb, n, cs), device=dev, dtype=F32)
+    dz = {k: _out((nb, n, h, w, c), dev, BF16, fill) for k in ("dz1", "dz2", "dz3")}
+    dx = _out((n, h, w, c), dev, BF16, fill)
+    dgb = _out((nb, 3, 2, c), dev, F32, fill)
+    dpre2 = _out((nb, n, c), dev, F32, fill)
+    dpre1 = _out((nb, n, cs), dev, F32, fill)
     ws, status = xstage_ws(dev)
     lib().call("hn_xstage_bwd", ctypes.addressof(tab), nb, ptr(dout), ptr(z1), ptr(z2), ptr(z3), ptr(out), ptr(coef), ptr(hid), ptr(gate),
                ptr(dz["dz1"]), ptr(dz["dz2"]), ptr(dz["dz3"]), ptr(dx), ptr(dgb), ptr(dpre2), ptr(dpre1), n, h, w, c, cs, ptr(ws), ptr(stamps),

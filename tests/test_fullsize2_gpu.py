@@ -111,7 +111,36 @@ def test_default_resolution_backbone_deep_stage(big, stage):
     assert len(calls) == big[0].depths[stage], (len(calls), big[0].depths[stage])
 
 
-def _deep_stage(big, stage, H, W, n, tag):
+DEEP_CONFIGS = {"512x1024_n8": (H, W, 8), "512x1024_n16": (H, W, 16), "640_n16": (640, 640, 16)}
+
+
+@pytest.mark.parametrize("stage,config,path", [(s, c, "persistent") for s in (3, 4) for c in DEEP_CONFIGS] +
+                         [(s, "512x1024_n16", "chain") for s in (3, 4)])
+def test_backbone_deep_stage_paths(big, stage, config, path):
+    """the teacher-forced blocks of stages 3 / 4 through the PRODUCT's path at the training step's shapes (the chain cases at N = 8 and at
+    640 x 640 are the two tests above).  persistent: block 0 (stride 2) on the chain; every block i >= 1 as the training step runs it --
+    K.DeferredGrads on the block input with a fresh K.WgradGroup, then ONE K.xstage_apply (hn_xstage_fwd / hn_xstage_bwd), so the weight
+    gradients come from the deferred grouped launches.  Same bounds as the chain, plus the three BatchNorms' running statistics."""
+    from multitask_hydranet_amd import ops as K
+    import multitask_hydranet_amd.ops.xstage as XS
+    h, w, n = DEEP_CONFIGS[config]
+    calls = []
+    orig = K.XStageFn.apply
+    try:
+        K.XStageFn.apply = staticmethod(lambda *a, **k: (calls.append(1), orig(*a, **k))[1])
+        _deep_stage(big, stage, h, w, n, f"stage{stage}_{config}_{path}", path)
+    finally:
+        del K.XStageFn.apply                      # back to torch.autograd.Function's own classmethod
+    assert len(calls) == (big[0].depths[stage] - 1 if path == "persistent" else 0), len(calls)
+    assert XS.xstage_status(torch.device("cuda:0")) == 0
+
+
+STAT_TOL = 5e-3                       # running statistics after the block, against the oracle's (max-norm relative per tensor)
+_DEFERRED = ("conv_block_1.0.weight", "conv_block_2.0.weight", "conv_block_3.0.weight", "se.1.weight", "se.1.bias", "se.3.weight", "se.3.bias")
+
+
+def _deep_stage(big, stage, H, W, n, tag, path="chain"):
+    from multitask_hydranet_amd import ops as K
     net, cfgs, O = big
     p = "backbone.net."
     b = cfgs["backbone"]
@@ -131,17 +160,25 @@ def _deep_stage(big, stage, H, W, n, tag):
         t.backward(up)
         net.zero_grad(set_to_none=True)
         a = cur.detach().clone().requires_grad_(True)
-        o = net._xblock(q + ".", a, 2 if i == 0 else 1)
+        if path == "persistent" and i > 0:
+            group = K.WgradGroup()
+            t0 = K.DeferredGrads.apply(a, group, *[net._idx[f"{q}.{k}"] for k in _DEFERRED])
+            assert net._xstage_run(q + ".", t0, group)
+            o = K.xstage_apply(t0, group, O.BN_BACKBONE["eps"], O.BN_BACKBONE["momentum"], net._xblock_params(q + "."))
+        else:
+            o = net._xblock(q + ".", a, 2 if i == 0 else 1)
         o.backward(up.permute(0, 2, 3, 1).contiguous().to(torch.bfloat16))
         wc, we, bad = param_grad_report(net, sd, q + ".")
         dc, dl = cos_l2(nchw(a.grad), xin.grad)
+        run = max(rel(net._idx[k], sd[k]) for k in sd if "running_" in k)
         res[f"block_{i}"] = dict(out=rel(nchw(o), t), din_cos=dc, din_rel_l2=dl, din_maxnorm=rel(nchw(a.grad), xin.grad),
-                                 worst_param_cos=wc, worst_param_err=we)
+                                 worst_param_cos=wc, worst_param_err=we, running_stats=run)
         bad_all += bad
         cur = o.detach()
     dump(tag, res)
     for k, v in res.items():
         assert v["out"] <= ACT_TOL and v["din_cos"] >= DIN_COS and v["din_rel_l2"] <= DIN_L2, (k, v)
+        assert v["running_stats"] <= STAT_TOL, (k, v)
     assert not bad_all, bad_all
 
 

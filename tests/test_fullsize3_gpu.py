@@ -97,14 +97,14 @@ def _grad_norm_report(names, ghip, gref):
     gerr = np.abs(ghip - gref) / np.maximum(gref, 1e-30)
     fus = np.array([_is_fusion_weight(k) for k in names])
     skip = (gref < 1e-6 * gref.max()) | fus                            # biases in front of BatchNorm: mathematically zero gradients
-    fscale = float(gref[fus].max())
+    fscale = float(gref[fus].max()) if fus.any() else 1.0                 # (no fusion weights among backbone-only gradients)
     se0 = np.array([".block_0.se.1." in k for k in names]) & ~skip
     rest = ~skip & ~se0
     order = np.argsort(-np.where(skip, 0, gerr))[:6]
     return dict(max=float(gerr[rest].max()), max_se_squeeze_first_blocks=float(gerr[se0].max()) if se0.any() else 0.0,
                 median=float(np.median(gerr[~skip])), p90=float(np.quantile(gerr[~skip], 0.9)), n=int((~skip).sum()),
                 worst=[(names[i], round(float(gerr[i]), 4)) for i in order],
-                fusion_weights_abs_err_over_largest=float(np.abs(ghip[fus] - gref[fus]).max() / fscale))
+                fusion_weights_abs_err_over_largest=float(np.abs(ghip[fus] - gref[fus]).max() / fscale) if fus.any() else 0.0)
 
 
 def _check_grad_norms(r):
@@ -283,3 +283,78 @@ def test_conditioned_state_elementwise_vs_fp32_oracle_512x1024(training):
             assert abs(a - b) <= TOL_LOSS * abs(b), (k, a, b)
         _check_grad_norms(res["grad_norm_rel_err"])
         assert min(res["grad_cosine"].values()) >= GRAD_COS, res["grad_cosine"]
+
+
+@pytest.mark.parametrize("n", [8, 16])
+def test_conditioned_state_backbone_training_vs_fp32_oracle(n):
+    """The backbone alone, training mode, at BASELINE's 3x512x1024 with N = 8 (config 2) and N = 16 (the training step's batch), where stages
+    3 and 4 run their identity blocks as single persistent launches (nb = 9 and 13: hn_xstage_fwd / hn_xstage_bwd), against the UNMIRRORED
+    fp32 oracle on the conditioned state.  Every feature map under the file's rule (HIP-vs-fp32 relative L2 <= MIRROR_FACTOR x the oracle's
+    own bf16-mirror-vs-fp32 distance + MIRROR_FLOOR) and its absolute ceilings TOL_L2 / TOL_MAX; the backbone gradient norms under
+    _check_grad_norms; gradient cosine >= GRAD_COS on the conv weights of the first and last block of stages 3 and 4.  Loss: the sum of the
+    five feature means (bench.py --backbone-only).  The same case runs once more on the launch chain (K.XSTAGE = False); both are recorded
+    and held to the same bounds."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs the MI355X")
+    from multitask_hydranet_amd import ops as K
+    import multitask_hydranet_amd.ops.xstage as XS
+    from oracle import hydranet_oracle as O
+    dev = torch.device("cuda:0")
+    net, cfgs = _net(H, W)
+    _, sd0 = _state(net)
+    bsd = {k: v for k, v in sd0.items() if k.startswith("backbone.")}
+    x = torch.randn(n, 3, H, W, device=dev, generator=torch.Generator(device=dev).manual_seed(70 + n))
+    with torch.no_grad(), O.bf16_mirror():
+        mir = O.backbone_forward({k: v.to(dev) for k, v in bsd.items()}, cfgs, x, True)
+    osd = {k: v.to(dev) for k, v in bsd.items()}
+    for k, v in osd.items():
+        if v.is_floating_point() and "running" not in k:
+            v.requires_grad_(True)
+    ref = O.backbone_forward(osd, cfgs, x, True)                                   # UNMIRRORED fp32
+    sum(f.mean() for f in ref).backward()
+    net.load_state_dict(sd0)
+    net = net.to(dev).train()
+    depths = net.depths
+    watch = [f"backbone.net.stage_{s}.blocks.block_{i}.conv_block_{j}.0.weight" for s in (3, 4) for i in (0, depths[s] - 1) for j in (1, 2, 3)]
+    l2 = lambda a, b: float((a.detach().float() - b.detach().float()).norm() / b.detach().float().norm().clamp(min=1e-20))
+    out = {}
+    try:
+        for path in ("persistent", "chain"):
+            K.XSTAGE = path == "persistent"
+            net.load_state_dict(sd0)
+            net.zero_grad(set_to_none=True)
+            calls = []
+            orig = K.XStageFn.apply
+            try:
+                K.XStageFn.apply = staticmethod(lambda *a, **k: (calls.append(1), orig(*a, **k))[1])
+                feats = net._backbone(x)
+                net._flush_nbt()
+                sum(f.float().mean() for f in feats).backward()
+            finally:
+                del K.XStageFn.apply
+            torch.cuda.synchronize()
+            P = dict(net.named_parameters())
+            names = [k for k, p in P.items() if k.startswith("backbone.") and p.grad is not None]
+            assert len(names) > 0 and all(osd[k].grad is not None for k in names)
+            assert {k for k in osd if osd[k].grad is not None} == set(names)
+            gref = np.array([float(osd[k].grad.double().norm()) for k in names])
+            ghip = np.array([float(P[k].grad.double().norm()) for k in names])
+            res = {"xstage_launches": len(calls)}
+            res["tensors"] = {f"feat{i}": dict(max=rel(nchw(f), r), l2=l2(nchw(f), r), mirror_l2=l2(m, r), mirror_max=rel(m, r))
+                              for i, (f, r, m) in enumerate(zip(feats, ref, mir))}
+            res["grad_norm_rel_err"] = _grad_norm_report(names, ghip, gref)
+            res["grad_cosine"] = {k: float(torch.nn.functional.cosine_similarity(P[k].grad.flatten().double(), osd[k].grad.flatten().double(),
+                                                                                 dim=0)) for k in watch}
+            out[path] = res
+    finally:
+        K.XSTAGE = True
+        net.load_state_dict(sd0)
+    dump(f"backbone_train_n{n}", out)
+    assert out["persistent"]["xstage_launches"] == 2 and out["chain"]["xstage_launches"] == 0      # stages 3 and 4, one launch each
+    assert XS.xstage_status(dev) == 0
+    for path, res in out.items():
+        for k, v in res["tensors"].items():
+            assert v["l2"] <= MIRROR_FACTOR * v["mirror_l2"] + MIRROR_FLOOR, (path, k, v)
+            assert v["l2"] <= TOL_L2[k] and v["max"] <= TOL_MAX[k], (path, k, v)
+        _check_grad_norms(res["grad_norm_rel_err"])
+        assert min(res["grad_cosine"].values()) >= GRAD_COS, (path, res["grad_cosine"])

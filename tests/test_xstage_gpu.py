@@ -40,6 +40,53 @@ def test_shape_envelope_and_abi():
     assert 1 << 20 <= L.query("hn_xstage_ws_bytes") <= 1 << 22
 
 
+@pytest.mark.parametrize("n,h,w,c,cs", [(4, 3, 5, 24, 6), (8, 1, 1, 16, 4)])
+def test_xblock_restatement_equals_oracle(n, h, w, c, cs):
+    """CPU: tests/xblock_ref.py (the float64 reference of tests/test_xstage_oracle_gpu.py) against oracle.xblock under bf16_mirror, both in
+    float64: the output and the six running statistics within 1e-6, and the input and parameter gradients equal to autograd through the
+    oracle.  (8, 1, 1): a 1 x 1 map -- the grouped conv's centre tap only, BatchNorm over 8 values (unbiased factor 8 / 7)."""
+    from oracle import hydranet_oracle as O
+    from tests import xblock_ref as R
+    ps = [t.double() for t in _params(1, c, "cpu", 5 + n)]
+    assert ps[10].shape[0] == cs
+    g = torch.Generator().manual_seed(n)
+    x = torch.randn(n, h, w, c, generator=g, dtype=torch.float64).to(torch.bfloat16).double().relu()
+    dout = torch.randn(n, h, w, c, generator=g, dtype=torch.float64)
+    r = R.forward(x, ps, EPS, MOM)
+    gr = R.backward(r, dout)
+    q = "blk"
+    keys = ("conv_block_1.0.weight", "conv_block_1.1.weight", "conv_block_1.1.bias", "conv_block_1.1.running_mean", "conv_block_1.1.running_var",
+            "conv_block_2.0.weight", "conv_block_2.1.weight", "conv_block_2.1.bias", "conv_block_2.1.running_mean", "conv_block_2.1.running_var",
+            "se.1.weight", "se.1.bias", "se.3.weight", "se.3.bias",
+            "conv_block_3.0.weight", "conv_block_3.1.weight", "conv_block_3.1.bias", "conv_block_3.1.running_mean", "conv_block_3.1.running_var")
+    sd = {f"{q}.{k}": t.clone().requires_grad_("running" not in k) for k, t in zip(keys, ps)}
+    xin = x.permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+    with O.bf16_mirror():
+        out = O.xblock(sd, q, xin, 1, c // 8, True)
+    out.backward(dout.permute(0, 3, 1, 2))
+    rel = lambda a, b: float((a - b).abs().max() / b.abs().max().clamp(min=1e-300))
+    assert rel(r["out"], out.detach().permute(0, 2, 3, 1)) <= 1e-6
+    for i, k in enumerate(keys):
+        nm = R.NAMES[i]
+        if nm in R.RUNNING:
+            assert rel(r["running"][nm], sd[f"{q}.{k}"]) <= 1e-6, (k, rel(r["running"][nm], sd[f"{q}.{k}"]))
+            assert rel(r["running"][nm], ps[i]) > 1e-3, k                  # the update happened (momentum 0.1 of a different value)
+        else:
+            ref = sd[f"{q}.{k}"].grad
+            assert ref is not None and rel(gr[R.GRADS[nm]], ref) <= 1e-6, (k, rel(gr[R.GRADS[nm]], ref))
+    assert rel(gr["dx"], xin.grad.permute(0, 2, 3, 1)) <= 1e-6
+    # the unbiased factor is live: the running variance is not the one the biased variance would give
+    cnt = n * h * w
+    biased = (1 - MOM) * ps[4] + MOM * r["var"][0]
+    assert rel(r["running"]["rv1"], (1 - MOM) * ps[4] + MOM * r["var"][0] * cnt / (cnt - 1)) <= 1e-12
+    assert rel(r["running"]["rv1"], biased) > 1e-6
+    # the layouts hn_xstage_bwd writes: dgb [3, 2, C] = (dgamma, dbeta) per BatchNorm; the SE pre-activation gradients
+    assert gr["dgb"].shape == (3, 2, c) and rel(gr["dgb"][2, 1], sd[f"{q}.conv_block_3.1.bias"].grad) <= 1e-6
+    assert gr["dpre2"].shape == (n, c) and gr["dpre1"].shape == (n, cs)
+    assert rel(gr["dpre2"].sum(0), sd[f"{q}.se.3.bias"].grad) <= 1e-12 and rel(gr["dpre1"].sum(0), sd[f"{q}.se.1.bias"].grad) <= 1e-12
+    assert rel(gr["dpre2"].t() @ r["hid"], sd[f"{q}.se.3.weight"].grad.flatten(1)) <= 1e-12
+
+
 def _params(nb, c, dev, seed):
     g = torch.Generator(device="cpu").manual_seed(seed)
     cs = c // 4
