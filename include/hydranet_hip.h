@@ -619,6 +619,17 @@ long hn_coco_accumulate_ws_bytes(long N);
 int hn_coco_accumulate(const int* rec, long N, int K, int seq_bits, const int* iprm, const double* rec_thrs, int T, int R, int M, void* ws,
                        double* precision, double* recall, hipStream_t stream);
 
+/* Lane ground-truth encoding (head_lane/lane_codec.py LaneCodec.encode_lane + dataset/dataloader.py:343-352's scale-invariance division;
+ * hn_lane_encode.hip, parity rules in its header comment and DESIGN.md 4e).  pts (DEVICE fp64 [n_points][2] = x, y) = every lane's points
+ * scaled to the W x H input, deduplicated on y, y descending (>= 2 per lane); lane_off int32 [n_lanes + 1] = CSR offsets of the lanes' points;
+ * img_lane int32 [N + 1] = CSR offsets of every image's lanes (annotation order).  Geometry: anchor grid fw x fh = int(W / stride) x
+ * int(H / stride), F = fw * fh, P points per line, interval = H / P; div_interval = the dataset's divisor for columns [0, P) and
+ * [P + 2, 2P + 2) when scale_invariance.  Writes gt_cls fp32 [N][F][2] and gt_loc fp32 [N][F][2P + 2] completely (background rows
+ * included).  ws: hn_lane_encode_ws_bytes(n_lanes, n_points, W, H, stride, P) bytes.  Two launches. */
+long hn_lane_encode_ws_bytes(int n_lanes, long n_points, int W, int H, int stride, int P);
+int hn_lane_encode(const double* pts, const int* lane_off, const int* img_lane, int N, int n_lanes, long n_points, int W, int H, int stride,
+                   int P, int interpolate, int scale_invariance, float div_interval, void* ws, float* gt_cls, float* gt_loc, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

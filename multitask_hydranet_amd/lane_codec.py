@@ -1,4 +1,4 @@
-"""Lane decode + lane NMS on the device (reference: head_lane/lanedetect.py:103-125 LaneHeader.decode / scale_to_org,
+"""Lane ground-truth encoding, lane decode + lane NMS on the device (reference: head_lane/lanedetect.py:103-125 LaneHeader.decode / scale_to_org,
 head_lane/lane_codec.py:25-51,116-219 LaneCodec.decode_lane, head_lane/lane_codec_utils.py:6-64,185-282,487-543).
 
 `decode(predict_cls, predict_loc, pointlane, conf_thres, nms_line_thres, use_mean)` keeps the reference's signature and return type (a list
@@ -6,9 +6,14 @@ of Lane objects in descending-probability order); the per-anchor point walk, the
 in ONE kernel launch for the whole batch (hn_lane_decode_nms, one workgroup per image).  `pointlane` may be the reference's own LaneCodec
 object or this module's LaneCodec (only the geometry fields are read).  scale_to_org / order_lane_x_axis / convert_lane_to_dict are the
 host-side bookkeeping on the handful of surviving lanes, restated.
+
+`LaneCodec.encode_lane` / `encode_lanes` (reference: head_lane/lane_codec.py:53-114,221-366, lane_spline_interp.py, and the dataset's
+division, dataset/dataloader.py:343-352): the host parses and packs the annotations (`pack_lanes`), hn_lane_encode does the rest for the
+whole batch.
 """
 from __future__ import annotations
 
+import json
 from typing import List
 
 import numpy as np
@@ -36,8 +41,8 @@ class Lane:
 
 
 class LaneCodec:
-    """geometry of the reference's LaneCodec (lane_codec.py:25-51); encode_lane (ground-truth generation, scipy splines) is data-pipeline
-    work outside the hot path"""
+    """the reference's LaneCodec (lane_codec.py:25-51): its geometry, encode_lane / encode_lanes (ground-truth generation on the device,
+    hn_lane_encode) and decode_lane"""
 
     def __init__(self, input_width, input_height, anchor_stride, points_per_line, do_interpolate=False, anchor_lane_num=1,
                  scale_invariance=True):
@@ -51,10 +56,148 @@ class LaneCodec:
         self.step_w = self.step_h = anchor_stride
         self.anchor_lane_num, self.interpolation, self.scale_invariance = anchor_lane_num, do_interpolate, scale_invariance
 
+    def encode_lane(self, lane_object, org_width, org_height):
+        """LaneCodec.encode_lane (lane_codec.py:53-114) for ONE image: numpy fp32 (gt_type [F, 2], gt_loc [F, 2P+2]) BEFORE the dataset's
+        scale-invariance division; (None, None) when anchor_lane_num != 1, as the reference"""
+        if self.anchor_lane_num != 1:
+            return None, None
+        cls, loc = self.encode_lanes([lane_object], [(org_width, org_height)], divide=False)
+        return cls[0].cpu().numpy(), loc[0].cpu().numpy()
+
+    def encode_lanes(self, lane_objects, org_sizes, device=None, div_interval=None, divide=True):
+        """the batched device encoder: torch fp32 (gt_cls [N, F, 2], gt_loc [N, F, 2P+2]) on `device` in the dataset's final form
+        (dataloader.py:343-352: columns [0, P) and [P+2, 2P+2) divided by `div_interval` (default: the codec's interval) when
+        scale_invariance).  lane_objects: JSON strings or {"Lines": ...} dicts; org_sizes: (width, height) pairs or {"width", "height"}
+        dicts / JSON strings.  The host only parses and packs; everything after the parse is one call (two launches), no synchronisation."""
+        if self.anchor_lane_num != 1:
+            raise ValueError("lane ground-truth encoding exists for anchor_lane_num == 1 only (the reference encodes no other)")
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        W, H, stride, P = int(self.input_width), int(self.input_height), int(self.stride), int(self.points_per_line)
+        pts, ints, n_lanes = pack_lanes(lane_objects, org_sizes, W, H, self.interval, self.interpolation, P)
+        n = len(lane_objects)
+        pts_d = torch.from_numpy(pts).pin_memory().to(dev, non_blocking=True)
+        ints_d = torch.from_numpy(ints).pin_memory().to(dev, non_blocking=True)
+        F = self.feature_size
+        cls = torch.empty((n, F, 2), device=dev, dtype=torch.float32)
+        loc = torch.empty((n, F, 2 * P + 2), device=dev, dtype=torch.float32)
+        ws = torch.empty((lib().query("hn_lane_encode_ws_bytes", n_lanes, len(pts), W, H, stride, P),), device=dev, dtype=torch.uint8)
+        si = bool(self.scale_invariance) and divide
+        div = float(div_interval if div_interval is not None else self.interval)
+        with torch.cuda.device(dev):
+            lib().call("hn_lane_encode", pts_d.data_ptr() if len(pts) else 0, ints_d.data_ptr(), ints_d.data_ptr() + 4 * (n_lanes + 1), n,
+                       n_lanes, len(pts), W, H, stride, P, int(bool(self.interpolation)), int(si), div, ws.data_ptr(), cls.data_ptr(),
+                       loc.data_ptr())
+        return cls, loc
+
     def decode_lane(self, predict_type, predict_loc, exist_threshold=0.5, margin_width=100.0):
         """candidates before NMS (LaneCodec.decode_lane takes POST-softmax probabilities): runs the device kernel with the NMS disabled"""
         logits = torch.log(predict_type.clamp_min(1e-38))
         return _decode_batch(logits[None], predict_loc[None], self, exist_threshold, -1.0, False, margin_width, keep_all=True)[0]
+
+
+# ---- the host half of encode_lane: get_lane_list + trans_to_lane_with_type + delete_repeat_y (lane_codec_utils.py:127-183,285-320) ----
+_MAX_SAMPLES = 1 << 24
+_MAX_COORD = float(1 << 24)
+
+
+def _raw_lines(lane_object, sx, sy, xs, ys, counts):
+    """append one annotation's points ("nan" skipped, duplicate RAW y dropped, reversed when the first two go upward once scaled) to the
+    flat lists, UNSCALED (the caller scales: the same fp64 product); the point count of every lane with >= 2 points to `counts`"""
+    if isinstance(lane_object, (str, bytes)):
+        lane_object = json.loads(lane_object)
+    for line in lane_object["Lines"]:
+        xr = [p["x"] for p in line]
+        yr = [p["y"] for p in line]
+        if "nan" in xr or "nan" in yr or len(set(yr)) != len(yr):
+            raw_y, kx, ky = set(), [], []
+            for px, py in zip(xr, yr):
+                if px == "nan" or py == "nan" or py in raw_y:
+                    continue
+                raw_y.add(py)
+                kx.append(px)
+                ky.append(py)
+            xr, yr = kx, ky
+        if len(xr) < 2:
+            continue
+        lx, ly = list(map(float, xr)), list(map(float, yr))
+        if ly[0] * sy < ly[1] * sy:
+            lx.reverse()
+            ly.reverse()
+        xs += lx
+        ys += ly
+        counts.append(len(lx))
+
+
+def _scale_sort_dedupe(xs, ys, counts, scales):
+    """scale, then per lane: stable sort by descending y, the first x of every float y; lanes left with < 2 points dropped.
+    -> x, y, lane id (dense over the input lanes)"""
+    counts = np.array(counts, np.int64)
+    lid = np.repeat(np.arange(len(counts)), counts)
+    sc = np.array(scales, np.float64).reshape(-1, 2)
+    x = np.array(xs, np.float64) * sc[lid, 0]
+    y = np.array(ys, np.float64) * sc[lid, 1]
+    inner = lid[1:] == lid[:-1]
+    if not np.all(y[1:][inner] < y[:-1][inner]):                      # (already strictly descending: nothing to sort or drop)
+        order = np.lexsort((np.arange(len(y)), -y, lid))
+        x, y, lid = x[order], y[order], lid[order]
+        keep = np.ones(len(y), bool)
+        keep[1:] = (y[1:] != y[:-1]) | (lid[1:] != lid[:-1])
+        x, y, lid = x[keep], y[keep], lid[keep]
+        ok = np.bincount(lid, minlength=len(counts))[lid] >= 2
+        x, y, lid = x[ok], y[ok], lid[ok]
+    return x, y, lid
+
+
+def parse_lane_object(lane_object, W, H, org_w, org_h):
+    """one annotation -> [(x, y)] fp64 arrays per lane, y descending: "nan" points skipped, duplicate y dropped on the RAW value,
+    scaled by W / org_w, H / org_h; the first two points decide whether the list is reversed (bottom first), then a stable sort by
+    descending y keeps the first x of every float y; lanes with fewer than 2 points left are dropped"""
+    xs, ys, counts = [], [], []
+    sx, sy = W * 1.0 / org_w, H * 1.0 / org_h
+    _raw_lines(lane_object, sx, sy, xs, ys, counts)
+    x, y, lid = _scale_sort_dedupe(xs, ys, counts, [(sx, sy)] * len(counts))
+    return [(x[lid == l], y[lid == l]) for l in np.unique(lid)]
+
+
+def _org_size(s):
+    if isinstance(s, (str, bytes)):
+        s = json.loads(s)
+    if isinstance(s, dict):
+        return float(s["width"]), float(s["height"])
+    return float(s[0]), float(s[1])
+
+
+def pack_lanes(lane_objects, org_sizes, W, H, interval, interpolate, P):
+    """a batch of annotations -> (pts fp64 [n_points, 2], ints int32 = lane offsets [n_lanes + 1] ++ image lane offsets [N + 1], n_lanes).
+    Raises ValueError on lanes the encoder cannot take: non-finite or absurd coordinates, more than 2^24 spline samples in the batch (the
+    reference would spin on them), and without `interpolate` a lane starting more than P + 1 intervals below the image (its loc rows
+    would not fit the 2P + 2 columns: the reference fails on them)."""
+    if len(lane_objects) != len(org_sizes):
+        raise ValueError("lane_objects and org_sizes differ in length: %d vs %d" % (len(lane_objects), len(org_sizes)))
+    xs, ys, counts, scales, first_lane = [], [], [], [], [0]
+    for obj, sz in zip(lane_objects, org_sizes):
+        ow, oh = _org_size(sz)
+        sx, sy = W * 1.0 / ow, H * 1.0 / oh
+        _raw_lines(obj, sx, sy, xs, ys, counts)
+        scales += [(sx, sy)] * (len(counts) - first_lane[-1])
+        first_lane.append(len(counts))
+    x, y, lid = _scale_sort_dedupe(xs, ys, counts, scales)
+    if not (np.all(np.abs(x) < _MAX_COORD) and np.all(np.abs(y) < _MAX_COORD)):
+        raise ValueError("lane coordinates outside +-2^24 or not finite after scaling")
+    lanes, starts = np.unique(lid, return_index=True)                # surviving lanes in order, their first point
+    same = lid[1:] == lid[:-1]
+    dx, dy = (x[:-1] - x[1:])[same], (y[:-1] - y[1:])[same]
+    if int(np.ceil(np.sqrt(dx * dx + dy * dy)).sum()) + len(lanes) > _MAX_SAMPLES:
+        raise ValueError("lane annotations of more than 2^24 spline samples in one batch")
+    if not interpolate and len(lanes):
+        yb = y[starts]
+        if np.any(np.trunc((H - 1 - yb) / interval + 1) < -(P + 1)):
+            raise ValueError("a lane starts %.1f px below the %d px input: beyond what the loc rows can hold" % (yb.max() - H, H))
+    lane_off = np.zeros(len(lanes) + 1, np.int64)
+    lane_off[1:] = np.cumsum(np.diff(np.append(starts, len(lid))))
+    img_lane = np.searchsorted(lanes, np.array(first_lane, np.int64))  # surviving lanes before every image's first lane id
+    pts = np.ascontiguousarray(np.stack([x, y], 1))
+    return pts, np.concatenate([lane_off, img_lane]).astype(np.int32), len(lanes)
 
 
 def _decode_batch(cls, loc, codec, conf_thres, nms_thres, use_mean, margin=100.0, keep_all=False) -> List[List[Lane]]:

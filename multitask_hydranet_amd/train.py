@@ -81,6 +81,7 @@ class HydraTrainer:
         self.capture_step = capture_step
         self._cap = None                       # (shape key, graph, static batch, static loss dict)
         self._eager_iters = 0
+        self._lane_coder = None                # LaneCodec of the cfg's geometry, built when a batch needs its lane targets encoded
         self._stream = None                    # data-parallel captured steps: ONE stream for the eager iterations and the capture (ddp.py)
         t = cfgs["train"]
         self.train_detect, self.train_seg, self.train_lane = t["train_detect"], t["train_seg"], t["train_lane"]
@@ -181,6 +182,8 @@ class HydraTrainer:
         """train.py:228-239"""
         batch_data["image"] = batch_data["image"].to(self.device).float()
         if self.train_lane:
+            if batch_data.get("gt_loc") is None or batch_data.get("gt_cls") is None:
+                batch_data["gt_cls"], batch_data["gt_loc"] = self._encode_lane_targets(batch_data)
             batch_data["gt_loc"] = batch_data["gt_loc"].to(self.device).float()
             batch_data["gt_cls"] = batch_data["gt_cls"].to(self.device).float()
         if self.train_seg:
@@ -188,6 +191,24 @@ class HydraTrainer:
         if self.train_detect:
             batch_data["gt_det"] = batch_data["gt_det"].to(self.device).float()
         return batch_data
+
+    def _encode_lane_targets(self, batch_data: dict):
+        """lane targets of a batch without gt_loc / gt_cls, encoded on the device from the raw annotations the reference's Collater hands
+        over (annot_lane: JSON per image, src_image_shape: source width / height per image; dataloader.py:343-352,367-377,620-625) with the
+        cfg's geometry (points_per_line = input height // lane.interval, dataloader.py:202).  No host synchronisation."""
+        if "annot_lane" not in batch_data or "src_image_shape" not in batch_data:
+            raise KeyError("train_lane: the batch carries neither gt_loc / gt_cls nor annot_lane + src_image_shape to encode them from")
+        if self._lane_coder is None:
+            from .lane_codec import LaneCodec
+            dl, ln = self.cfgs["dataloader"], self.cfgs["lane"]
+            if ln["anchor_lane_num"] != 1:
+                raise ValueError("lane.anchor_lane_num = %r: lane targets are encoded for anchor_lane_num == 1 only" % (ln["anchor_lane_num"],))
+            W, H = dl["network_input_width"], dl["network_input_height"]
+            self._lane_coder = LaneCodec(input_width=W, input_height=H, anchor_stride=ln["anchor_stride"],
+                                         points_per_line=int(H / ln["interval"]), do_interpolate=ln["interpolate"],
+                                         anchor_lane_num=ln["anchor_lane_num"], scale_invariance=ln["scale_invariance"])
+        return self._lane_coder.encode_lanes(list(batch_data["annot_lane"]), list(batch_data["src_image_shape"]), device=self.device,
+                                             div_interval=self.cfgs["lane"]["interval"])
 
     @staticmethod
     def _batch_sig(batch_data: dict):
