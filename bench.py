@@ -11,13 +11,19 @@ batch (weak scaling) and the gradients are averaged with the bucketed RCCL all-r
 Rank 0 prints ONE JSON line:
   * value / ms_per_step: the K timed steps bracketed by barrier + device sync on both sides (wall clock, max over ranks);
     ms_per_step_median: median of the per-step HIP-event durations recorded on the launch stream inside the same timed loop;
-  * roofline: the dominant launch (largest seg-decoder conv), timed live with HIP events;
+  * env_overrides: every HN_* environment variable that was set (tools/ hooks change what runs; none of them skips work in the timed region).
+A plain run does only that: it sets up, warms up, times the K steps, writes --dump-outputs and prints the line.  --full adds everything
+that takes runs of its own (each one after the timed steps, except the traffic passes, which run before this process touches the GPU):
+  * roofline: the dominant launch (largest seg-decoder conv), timed live with HIP events, its traffic from two rocprofv3 --pmc child
+    passes; dominant_by_time: the persistent stage launches;
+  * ms_optimizer_step: the Adam step, timed on its own;
   * segments: {backbone, neck, seg, det, lane, losses}: {ms, floor_ms, frac} -- each segment's forward + backward as its own captured
     hipGraph (ablation: backbone, backbone + neck, forward-only, head-only backward phases), floors from accounting.segment_floors_ms;
   * extra_configs (N=1 only): the other BASELINE configurations on the same device, ~0.5 s each: backbone-only N=8, the repo-default
     640x640, inference 1152x1920 N=32, the gradient exchange at world size 1, the three head-only fine-tuning phases;
-  * cpu_baseline: the fp32 oracle (a port, oracle/hydranet_oracle.py) timed on this box's host cores on a bounded sample;
-  * env_overrides: every HN_* environment variable that was set (tools/ hooks change what runs; none of them skips work in the timed region).
+  * cpu_baseline (N=1 only): the fp32 oracle (a port, oracle/hydranet_oracle.py) timed on this box's host cores on a bounded sample;
+  * exchange_exposed (N>1 or --ddp-world1): the same step captured and timed without the gradient exchange.
+The --no-* switches leave single parts out of a --full run.
 --dump-outputs DIR writes what the last timed step computed (dump_outputs / step_outputs) and lists it in the line as dumped_outputs: the
 inputs and the initial weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
@@ -528,10 +534,11 @@ def infer_bench(args, net, cfgs, h, w, dev, rank, world):
            "model_tflops": round(value * FWD_GFLOP_PER_IMG_512x1024 * scale / 1e3, 2), "env_overrides": env_overrides()}
     if dumped is not None:
         res["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
-    try:
-        res["roofline"] = dominant_launch_roofline(net, args.batch, h, w)
-    except Exception as e:      # noqa: BLE001
-        res["roofline"] = {"error": repr(e)}
+    if args.full:
+        try:
+            res["roofline"] = dominant_launch_roofline(net, args.batch, h, w)
+        except Exception as e:      # noqa: BLE001
+            res["roofline"] = {"error": repr(e)}
     emit(res)
 
 
@@ -931,11 +938,13 @@ def main():
     ap.add_argument("--res", default="512x1024")
     ap.add_argument("--cfg", default=os.path.join(ROOT, "cfgs", "hydranet_big.yml"))
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of one captured hipGraph per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra_configs and segments measurements (profiling runs)")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the dominant-launch timing loop (counter passes: only the step's own launches)")
-    ap.add_argument("--no-optimizer", action="store_true", help="skip the separate Adam-step timing (profiling runs: keeps the optimizer's "
-                    "state initialisation and multi-tensor kernels out of the kernel statistics)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure what takes runs of its own: the dominant-launch "
+                    "roofline and its live traffic passes, the Adam step, the per-segment table, the other BASELINE configurations, the CPU "
+                    "oracle baseline and, with a gradient exchange, its exposed time (off: the line carries the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the extra_configs and segments measurements")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the dominant-launch timing loop and its traffic passes")
+    ap.add_argument("--no-optimizer", action="store_true", help="--full without the separate Adam-step timing")
     ap.add_argument("--backbone-only", action="store_true", help="BASELINE config[1]: backbone fwd+bwd, loss = sum of feature means")
     ap.add_argument("--dominant-only", action="store_true", help="launch only the dominant kernel (for rocprofv3 --pmc passes) and exit")
     ap.add_argument("--no-live-traffic", action="store_true", help="roofline.traffic from the committed profile instead of two rocprofv3 --pmc "
@@ -969,9 +978,9 @@ def main():
               % (args.gpus, world), file=sys.stderr)
         sys.exit(2)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    # roofline.traffic of the headline line, sampled in this run (children under rocprofv3, started before this process uses the GPU)
-    if (world == 1 and rank == 0 and not (args.dominant_only or args.no_roofline or args.no_live_traffic or args.infer or args.backbone_only
-                                          or args.phase or args.ddp_world1)
+    # --full: roofline.traffic of the headline line, sampled in this run (children under rocprofv3, started before this process uses the GPU)
+    if (args.full and world == 1 and rank == 0 and not (args.dominant_only or args.no_roofline or args.no_live_traffic or args.infer
+                                                        or args.backbone_only or args.phase or args.ddp_world1)
             and args.batch == 16 and args.res == "512x1024" and os.environ.get("HN_BENCH_LIVE_TRAFFIC", "1") != "0"
             and not any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) and "rocprof" not in os.environ.get("LD_PRELOAD", "")):   # (not nested)
         import __graft_entry__ as ge0
@@ -1054,12 +1063,12 @@ def main():
     both_forms = exchange and backend == "nccl" and run.in_graph_exchange and args.both_exchange_forms
     if both_forms and rank != 0:
         other_exchange_form(run, net, cfgs, batch, dev, rank, world, payload, args, dt)
-    # What the exchange costs on the step's critical path: the same step captured WITHOUT the exchange (no collective inside
-    # this second capture, so it is safe in-process) and timed on every rank; exposed = step with - step without, max over ranks.  The
-    # reducer's default form is in line on the capture stream; when the exposed time exceeds 3 % of the step the line says so
+    # --full: what the exchange costs on the step's critical path: the same step captured WITHOUT the exchange (no
+    # collective inside this second capture, so it is safe in-process) and timed on every rank; exposed = step with - step without, max over
+    # ranks.  The reducer's default form is in line on the capture stream; when the exposed time exceeds 3 % of the step the line says so
     # (`exchange_advice`): the forked side-stream form (HN_DDP_GRAPH_OVERLAP=1) and the bf16 payload (--grad-payload bf16) are the two knobs.
     exposed = None
-    if exchange and run.graph is not None and run.in_graph_exchange and not os.environ.get("HN_BENCH_GRAD_NORM"):
+    if args.full and exchange and run.graph is not None and run.in_graph_exchange and not os.environ.get("HN_BENCH_GRAD_NORM"):
         try:
             from multitask_hydranet_amd.ddp import settle_collectives
             settle_collectives(dev)
@@ -1095,9 +1104,9 @@ def main():
         # is not a measurement (checked here, after the timed region's synchronisation)
         from multitask_hydranet_amd.ops import xstage_assert_ok
         xstage_assert_ok(torch.device("cuda", torch.cuda.current_device()))
-        # optimizer step, reported separately (Adam as in model/train.py:147)
+        # --full: optimizer step, reported separately (Adam as in model/train.py:147)
         ms_opt = None
-        if not args.no_optimizer:
+        if args.full and not args.no_optimizer:
             from multitask_hydranet_amd.optim import Adam       # torch.optim.Adam's rule, all tensors in one launch (HN_TORCH_ADAM=1: torch's)
             opt = (torch.optim.Adam if os.environ.get("HN_TORCH_ADAM") else Adam)([p for p in net.parameters() if p.grad is not None], 1e-5,
                                                                                   weight_decay=1e-8)
@@ -1133,7 +1142,7 @@ def main():
         }
         if dumped is not None:
             res["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             try:
                 # top-level fields = the dominant kernel by FLOPs (the contract's single entry); the same object again as
                 # `dominant_by_flops`, and the family that takes the most time in the step as `dominant_by_time`
@@ -1145,14 +1154,14 @@ def main():
                     res["roofline"]["dominant_by_time"] = {"error": repr(e)[:300]}
             except Exception as e:      # noqa: BLE001
                 res["roofline"] = {"error": repr(e)}
-        plain = world == 1 and not (args.backbone_only or args.phase or args.ddp_world1 or args.no_graph or args.no_extras)
-        if plain:
+        extras = args.full and world == 1 and not (args.backbone_only or args.phase or args.ddp_world1 or args.no_graph or args.no_extras)
+        if extras:
             try:
                 res["segments"] = segment_table(net, cfgs, batch, args.batch, h, w, median(per))
             except Exception as e:  # noqa: BLE001
                 res["segments"] = {"error": repr(e)[:300]}
             res["extra_configs"] = extra_configs(args, dev, net, cfgs)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(yaml.safe_load(open(args.cfg)) | {"dataloader": cfgs["dataloader"]}, h, w)
             except Exception as e:  # noqa: BLE001

@@ -187,6 +187,31 @@ def test_bench_dump_outputs_are_what_the_last_timed_step_computed():
     assert oi["dumped_outputs"]["arrays"]["classification"]["shape"] == [32, anchors, 9]
 
 
+def test_bench_plain_run_is_the_headline_only():
+    """a plain bench.py run times the step and prints the headline; the roofline, the Adam step and the other measurements that take runs
+    of their own come with --full (here without the extra configurations and the CPU baseline, which have fixed sizes of their own)"""
+    import json
+    import subprocess
+    import sys
+    if not torch.cuda.is_available():
+        pytest.skip("needs the MI355X")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "2", "--res", "256x512"]
+    outs = []
+    for extra in ([], ["--full", "--no-extras", "--no-cpu-baseline"]):
+        r = subprocess.run(base + extra, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        outs.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    plain, full = outs
+    for o in outs:
+        assert o["unit"] == "images/sec" and o["higher_is_better"] is True and o["dtype"] == "bf16" and o["steps"] == 2
+        assert abs(o["value"] * o["ms_per_step"] / 1e3 - 2) <= 0.02
+    assert not {"roofline", "segments", "extra_configs", "cpu_baseline", "exchange_exposed"} & set(plain)
+    assert plain["ms_optimizer_step"] is None
+    assert full["ms_optimizer_step"] > 0 and "error" not in full["roofline"] and "dominant_by_time" in full["roofline"]
+    assert full["loss"] == plain["loss"] and full["metric"] == plain["metric"]
+
+
 def test_two_rank_control_flow_on_one_gpu():
     """the N > 1 launch contract of bench.py (torch.distributed.run, one process per rank, barrier + max-over-ranks timing, rank 0 prints
     the JSON line) with the two test hooks that make it runnable on a 1-GPU box: both ranks on cuda:0, gloo instead of RCCL (which refuses
