@@ -64,7 +64,8 @@ int hn_pack_small_batched(const long* jobs, const int* block_job, long total_blo
  *           (64 couts = 8 groups) contracts only over input channels [64t, 64t+64) with block-diagonal weights from
  *           hn_gconv_pack_diag (w = wk for the forward, wd for the data gradient); Nout == C0, KP == 64, no statistics.
  * (n_img, H, W) describe the OUTPUT pixel grid, M = n_img*H*W rows.  psum/psq (optional) receive per-wave partial sums / sums of
- * squares of the bf16-rounded outputs, [hn_nt_stat_rows(M, Nout)][Nout], for training-mode BatchNorm (F.batch_norm statistics).
+ * squares of the bf16-rounded outputs, [hn_nt_stat_rows(M, Nout)][Nout], for training-mode BatchNorm (F.batch_norm statistics); with
+ * act != 0 they are taken before the activation (of bf16(bias + sum), fp32 outputs unrounded).
  * rpi/img_stride (optional, 0 = off): out offset(pixel) = (pixel / rpi) * img_stride + (pixel % rpi) * ldc, which writes a pyramid
  * level straight into the per-image concatenation of head_detect/detection.py:37-44,74-83. */
 int hn_conv_gemm_nt(const void* x0, const void* x1, int mode, int n_img, int H, int W, int C0, int C1, int ld0, int ld1, int up, long M,
