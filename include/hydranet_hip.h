@@ -631,6 +631,16 @@ long hn_lane_encode_ws_bytes(int n_lanes, long n_points, int W, int H, int strid
 int hn_lane_encode(const double* pts, const int* lane_off, const int* img_lane, int N, int n_lanes, long n_points, int W, int H, int stride,
                    int P, int interpolate, int scale_invariance, float div_interval, void* ws, float* gt_cls, float* gt_loc, hipStream_t stream);
 
+/* Training-batch augmentation (augment.py; hn_augment.hip, semantics in augment.py's docstring and DESIGN.md 4f).  src: uint8 BGR source
+ * frames packed back to back (ragged: every image's byte offset, Hs, Ws in its descriptor); desc: DEVICE array of N 176-byte AugDesc
+ * (F^-1, photometric op + parameters, noise key, blur weights, offsets; layout in hn_augment.hip and augment.py DESC_DTYPE).
+ * hn_augment_photometric writes the photometric result of every image with ws_off >= 0 into ws at that offset (Hs * Ws * 3 bytes each);
+ * the grid covers max_hs x max_ws.  hn_augment_image: warp + INTER_AREA resize + BGR->RGB + ImageNet normalisation -> fp32 [N][3][Hd][Wd]
+ * (it samples ws for images with ws_off >= 0, src otherwise).  hn_augment_seg: uint8 label maps (packed, seg_off) -> uint8 [N][Hd][Wd]. */
+int hn_augment_photometric(const void* src, const void* desc, int N, int max_hs, int max_ws, void* ws, hipStream_t stream);
+int hn_augment_image(const void* src, const void* ws, const void* desc, int N, int Hd, int Wd, float* dst, hipStream_t stream);
+int hn_augment_seg(const void* seg, const void* desc, int N, int Hd, int Wd, void* dst, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,149 @@
+"""The reference's MultitaskData over its data-list layout (model/dataset/dataloader.py:164-426, dataset/utility.py:235-257), split for
+device augmentation: a DataLoader worker only decodes the files (PIL, swapped to BGR as cv2.imread delivers), parses the labels, samples the
+image's augmentation plan (augment.sample_plan) and packs the batch's host buffers.  The batch carries `src_frames` / `src_segs` (packed
+uint8), the parsed labels and `aug_plans` instead of `image`; HydraTrainer.to_gpu runs augment.augment_batch on it, which returns the
+Collater contract.  Workers never touch the GPU.
+
+    ds = MultitaskData(cfgs, "train")
+    loader = DataLoader(ds, batch_size=16, shuffle=True, num_workers=8, collate_fn=ds.collate_fn, pin_memory=True)
+    for epoch in ...: ds.set_epoch(epoch); trainer.train_one_epoch(epoch)
+"""
+from __future__ import annotations
+
+import json
+import os
+
+import numpy as np
+
+from .augment import identity_plan, pack, sample_plan
+
+
+def load_img_list(path):
+    with open(path) as f:
+        return list(map(str.strip, f))
+
+
+def create_subset(data_list, with_lane=False, with_seg=False, with_detect=False):
+    """utility.py:235-257: every image path of the list and its label files (images -> labels_lane / labels_segmentation / labels_object)"""
+    pairs = []
+    for p in load_img_list(data_list):
+        if not p:
+            continue
+        d = dict(image_path=p)
+        if with_lane:
+            d["annot_path_lane"] = p.replace(".jpg", ".json").replace("images", "labels_lane")
+        if with_seg:
+            d["annot_path_seg"] = p.replace(".jpg", ".png").replace("images", "labels_segmentation")
+        if with_detect:
+            d["annot_path_detect"] = p.replace(".jpg", ".txt").replace("images", "labels_object")
+        pairs.append(d)
+    return pairs
+
+
+def parse_own_label(labels):
+    """labelme json -> {"Lines": [[{"x", "y"}, ...]], "Labels": [...]} (dataloader.py:383-393)"""
+    out = {"Lines": [], "Labels": []}
+    for shape in labels["shapes"]:
+        out["Lines"].append([{"x": pt[0], "y": pt[1]} for pt in shape["points"]])
+        out["Labels"].append(shape["label"])
+    return out
+
+
+def load_detect_annot(path):
+    """x1,y1,x2,y2,id lines -> [k, 5] x1, y1, x2, y2, id - 1 (float64); boxes narrower or lower than 1 px dropped (dataloader.py:395-426)"""
+    rows = []
+    with open(path) as f:
+        for line in f.readlines():
+            v = line.strip("\n").split(",")
+            if len(v) < 5:
+                continue
+            x1, y1, x2, y2, cid = (int(v[i]) for i in range(5))
+            if x2 - x1 < 1 or y2 - y1 < 1:
+                continue
+            rows.append([x1, y1, x2, y2, cid - 1])
+    return np.array(rows, dtype=np.float64).reshape(-1, 5)
+
+
+def imread_bgr(path):
+    from PIL import Image
+    if not os.path.exists(path):
+        raise FileNotFoundError(path)
+    with Image.open(path) as im:
+        rgb = np.asarray(im.convert("RGB"))
+    return np.ascontiguousarray(rgb[..., ::-1])
+
+
+def imread_label(path):
+    from PIL import Image
+    with Image.open(path) as im:
+        a = np.asarray(im)
+    if a.ndim == 3:                                   # cv2.IMREAD_UNCHANGED of a colour png: the reference keeps channel 0 after imgaug
+        a = a[..., 0]
+    return np.ascontiguousarray(a.astype(np.uint8))
+
+
+class MultitaskData:
+    """torch Dataset (map style) of the reference's layout; items are host-side only"""
+
+    def __init__(self, cfgs, mode, base_seed: int = 0):
+        dl = cfgs["dataloader"]
+        self.cfgs, self.mode, self.base_seed, self.epoch = cfgs, mode, int(base_seed), 0
+        self.network_input_width, self.network_input_height = dl["network_input_width"], dl["network_input_height"]
+        self.with_aug = bool(dl.get("with_aug", False)) and mode != "val"
+        self.do_flip = bool(dl.get("do_flip", False))
+        if dl.get("do_split", False) and self.with_aug:
+            raise NotImplementedError("dataloader.do_split: the split crop (MultitaskData.cal_split) is not supported by the device augmentation")
+        t = cfgs["train"]
+        self.train_lane, self.train_seg, self.train_detect = t["train_lane"], t["train_seg"], t["train_detect"]
+        if not (self.train_lane or self.train_seg or self.train_detect):
+            raise ValueError("must train at least one header")
+        if mode not in ("train", "val"):
+            raise NotImplementedError("mode should be one of ('train', 'val')")
+        lst = os.path.join(dl["data_list"], "train.txt" if mode == "train" else "valid.txt")
+        self.image_annot_path_pairs = create_subset(lst, with_lane=self.train_lane, with_seg=self.train_seg, with_detect=self.train_detect)
+
+    def set_epoch(self, epoch: int):
+        """plans are seeded from (base_seed, epoch, index): call before every epoch's iteration"""
+        self.epoch = int(epoch)
+
+    def __len__(self):
+        return len(self.image_annot_path_pairs)
+
+    def __getitem__(self, idx):
+        pair = self.image_annot_path_pairs[idx]
+        img = imread_bgr(pair["image_path"])
+        h, w = img.shape[:2]
+        if h < self.network_input_height or w < self.network_input_width:
+            raise ValueError("%s: %dx%d is smaller than the network input %dx%d (INTER_AREA does not upscale)"
+                             % (pair["image_path"], w, h, self.network_input_width, self.network_input_height))
+        item = dict(src_frame=img, src_image_shape=dict(width=w, height=h, channel=3), src_image_path=pair["image_path"],
+                    aug_plan=sample_plan(self.base_seed, self.epoch, idx, do_flip=self.do_flip) if self.with_aug else identity_plan())
+        if self.train_lane:
+            with open(pair["annot_path_lane"]) as f:
+                item["lane_raw"] = parse_own_label(json.load(f))
+            item["annot_lane_path"] = pair["annot_path_lane"]
+        if self.train_seg:
+            item["src_seg"] = imread_label(pair["annot_path_seg"])
+            if item["src_seg"].shape != (h, w):
+                raise ValueError("%s: label map %s does not match the frame %s" % (pair["annot_path_seg"], item["src_seg"].shape, (h, w)))
+        if self.train_detect:
+            item["det_raw"] = load_detect_annot(pair["annot_path_detect"])
+        return item
+
+    def collate_fn(self, batch):
+        return collate(batch, self.network_input_height, self.network_input_width)
+
+
+def collate(batch, net_h, net_w):
+    """host half of the Collater: the frames (and label maps) packed into one uint8 buffer each; labels and plans as lists"""
+    out = dict(src_frames=pack([b["src_frame"] for b in batch]), aug_plans=[b["aug_plan"] for b in batch],
+               src_image_shape=[b["src_image_shape"] for b in batch], src_image_path=[b["src_image_path"] for b in batch],
+               net_input_image_shape=[json.dumps(dict(width=net_w, height=net_h, channel=3))] * len(batch), net_input_hw=(net_h, net_w))
+    if "lane_raw" in batch[0]:
+        out["lane_raw"] = [b["lane_raw"] for b in batch]
+        out["annot_lane_path"] = [b["annot_lane_path"] for b in batch]
+    if "src_seg" in batch[0]:
+        out["src_segs"] = pack([b["src_seg"] for b in batch])
+    if "det_raw" in batch[0]:
+        out["det_raw"] = [b["det_raw"] for b in batch]
+    return out

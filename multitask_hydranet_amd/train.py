@@ -6,9 +6,8 @@ GPU over RCCL), Adam + per-iteration CosineAnnealingLR (train.py:147-150), `cal_
 `train_one_epoch` (train.py:241-269), `valid` (train.py:271-438: losses, streaming mIoU on the device, detection results in COCO json form
 from the device post-process, lane decode on the device) and `main`'s head-wise fine-tuning schedule (train.py:441-515: run_training /
 tuning_phase / HydraTrainer.set_phase), the lane F1 metric of train.py:188,397,433 (lane_metric.LaneMetric: rasterisation + IoU counts on the
-device).  The dataset / augmentation pipeline (cv2 + imgaug) and COCOeval (pycocotools) stay outside (out of scope); any
-iterable of batch dicts with the Collater contract
-(dataset/dataloader.py:557-633) drives the loop.
+device).  COCOeval (pycocotools) stays outside (out of scope); any iterable of batch dicts with the Collater contract
+(dataset/dataloader.py:557-633) drives the loop, or raw batches of dataset.MultitaskData, which to_gpu augments on the device (augment.py).
 
 Launch for N GPUs of one node:  python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 your_script.py
 (the trainer reads RANK / LOCAL_RANK / WORLD_SIZE; world size 1 needs no launcher).
@@ -179,7 +178,11 @@ class HydraTrainer:
         return self.hydranet.total_loss(loss_dict)
 
     def to_gpu(self, batch_data: dict) -> dict:
-        """train.py:228-239"""
+        """train.py:228-239.  A raw batch (dataset.MultitaskData: `src_frames` + `aug_plans`, no `image`) is first assembled and augmented on
+        the device (augment.augment_batch) into the Collater contract; lane targets are then encoded from its annot_lane as for any batch
+        without gt_loc / gt_cls."""
+        if "image" not in batch_data and "src_frames" in batch_data:
+            batch_data = self._augment(batch_data)
         batch_data["image"] = batch_data["image"].to(self.device).float()
         if self.train_lane:
             if batch_data.get("gt_loc") is None or batch_data.get("gt_cls") is None:
@@ -191,6 +194,16 @@ class HydraTrainer:
         if self.train_detect:
             batch_data["gt_det"] = batch_data["gt_det"].to(self.device).float()
         return batch_data
+
+    def _augment(self, batch_data: dict) -> dict:
+        from .augment import augment_batch
+        dl = self.cfgs["dataloader"]
+        out = augment_batch(batch_data["src_frames"], batch_data.get("lane_raw") if self.train_lane else None,
+                            batch_data.get("det_raw") if self.train_detect else None, batch_data.get("src_segs") if self.train_seg else None,
+                            batch_data["aug_plans"], (dl["network_input_height"], dl["network_input_width"]), device=self.device)
+        rest = {k: v for k, v in batch_data.items() if k not in ("src_frames", "src_segs", "lane_raw", "det_raw", "aug_plans")}
+        rest.update(out)
+        return rest
 
     def _encode_lane_targets(self, batch_data: dict):
         """lane targets of a batch without gt_loc / gt_cls, encoded on the device from the raw annotations the reference's Collater hands
