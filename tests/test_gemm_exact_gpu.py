@@ -14,13 +14,11 @@ import pytest
 import torch
 
 from tests import gemm_plans as P
+from tests.guards import BAND, Guarded, dev
 
 pytestmark = pytest.mark.gpu
 
 BF16, F32, F64 = torch.bfloat16, torch.float32, torch.float64
-SENT32 = 0x7FC00001            # NaN bit pattern no kernel produces
-SENT16 = 0x7FC1
-BAND = 256                     # guard elements before and after every output
 EXACT_LIMIT = 1 << 24
 RAND_TOL = 2e-5
 
@@ -33,10 +31,6 @@ def K():
     g.build()
     from multitask_hydranet_amd import ops
     return ops
-
-
-def dev():
-    return torch.device("cuda:0")
 
 
 def seed_of(name):
@@ -64,35 +58,6 @@ def randn(shape, g, width=None):
     full = tuple(shape[:-1]) + ((width or shape[-1]),)
     v = torch.randn(full, generator=g, device=dev()).to(BF16)
     return v[..., :shape[-1]] if width else v
-
-
-# ---- guard bands ---------------------------------------------------------------------------------------------------------------------
-class Guarded:
-    """an output tensor [rows, cols] with row stride ld >= cols inside a sentinel-filled buffer: BAND elements before and after, and
-    the ld - cols columns between rows"""
-
-    def __init__(self, rows, cols, ld=None, dtype=F32):
-        self.rows, self.cols, self.ld = rows, cols, ld or cols
-        self.dtype = dtype
-        n = 2 * BAND + rows * self.ld
-        idt = torch.int32 if dtype == F32 else torch.int16
-        self.buf = torch.full((n,), SENT32 if dtype == F32 else SENT16, dtype=idt, device=dev()).view(dtype)
-        self.view = self.buf[BAND:BAND + rows * self.ld].view(rows, self.ld)[:, :cols]
-
-    def ptr(self):
-        return self.view.data_ptr()
-
-    def check(self, name):
-        idt = torch.int32 if self.dtype == F32 else torch.int16
-        bits = self.buf.view(idt)
-        mask = torch.ones(bits.numel(), dtype=torch.bool, device=dev())
-        mask[BAND:BAND + self.rows * self.ld].view(self.rows, self.ld)[:, :self.cols] = False
-        bad = (bits != (SENT32 if self.dtype == F32 else SENT16)) & mask
-        nb = int(bad.sum())
-        if nb:
-            first = [int(i) - BAND for i in bad.nonzero()[:4, 0]]
-            pytest.fail(f"{name}: {nb} guard-band elements overwritten (first at offsets {first} from the output's start, "
-                        f"rows {self.rows} x cols {self.cols}, ld {self.ld})")
 
 
 # ---- exact comparison ----------------------------------------------------------------------------------------------------------------

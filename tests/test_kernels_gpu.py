@@ -119,6 +119,13 @@ def test_conv1x1_bn_act(K, cin, cout, stride, act, res, bias, n, h, w):
         close(nchw(rk.grad), rr.grad, GRAD_TOL, "dres")
     close(rm_k, rm_r, 1e-2, "running_mean")
     close(rv_k, rv_r, 1e-2, "running_var")
+    # the update itself (it is of the size of the tolerance above at momentum 0.01): (new - (1 - m) old) / m must be the batch mean and
+    # the UNBIASED batch variance of z
+    zd = z.detach().double()
+    upd_m = (rm_k.double() - (1 - 0.01) * rm.double()) / 0.01
+    upd_v = (rv_k.double() - (1 - 0.01) * rv.double()) / 0.01
+    close(upd_m, zd.mean((0, 2, 3)), 1e-3, "running_mean update vs batch mean")
+    close(upd_v, zd.var((0, 2, 3), unbiased=True), 1e-3, "running_var update vs unbiased batch variance")
     assert int(nbt) == 1
     g.grad = b.grad = None
 
