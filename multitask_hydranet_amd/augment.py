@@ -13,13 +13,22 @@ of _lane_argue with do_split=False (a tuple is a uniform range, a list a choice)
     HSV channel 0 x U(0.7, 1.3); channel 1 x U(0.1, 2); channel 2 x U(0.5, 1.5).
   * Sometimes(0.6) geometry: 4 of [flip left-right, translate x by an integer in [-16, 16] px, shear x U(-15, 15) deg, rotate U(-15, 15)
     deg, (flip up-down when dataloader.do_flip), crop-and-keep-size (top {0, 0.2}, right {0, 0.15}, bottom 0, left {0, 0.15})], applied in
-    list order.  with_aug False and mode "val" give the identity plan; do_split raises NotImplementedError.
+    list order.  with_aug False and mode "val" give the identity plan.
+With dataloader.do_split and a split ratio r (cal_split; a ratio of None takes the structure above, draw for draw; no ratio given at all
+raises NotImplementedError), the structure of _lane_argue with do_split=True:
+  * the photometric op as above;
+  * Sometimes(0.6) split: one of two keep-size crops (1/2 each), as (T, R, B, L) fractions: split_one (top {0, 0.2}, right 1 - r,
+    bottom 0, left {0, 0.15}); split_two (top {0, 0.2}, right {0, 0.15}, bottom 0, left r);
+  * Sometimes(0.6) position: 4 of [flip left-right, translate x, shear x, rotate, (flip up-down when do_flip)], no crop, in list order;
+  * one uniform draw (made whether or not the blocks apply) of whether the split comes before or after the position block.
 
 Coordinates are continuous, pixel (i, j) covers [j, j+1) x [i, i+1).  The chosen ops compose into one forward affine F (source ->
 augmented frame, same size as the source).  Single ops, about the centre (cx, cy) = (W/2, H/2):
   flip lr x -> W - x;  flip ud y -> H - y;  translate x -> x + t;  shear x -> x + tan(a) (y - cy);
   rotate (x, y) -> c + R(a) (p - c) with R = [[cos a, -sin a], [sin a, cos a]] (positive a turns clockwise on screen, y pointing down);
   crop (T, R, B, L px = rint(fraction * size)) x -> (x - L) W / (W - L - R), y -> (y - T) H / (H - T - B).
+  crop clamp: a negative fraction is 0; if L + R >= W, L and R give back g = L + R - W + 1 px, ceil(g / 2) from L and floor(g / 2) from R,
+    a side that has too little giving all it has and the other the rest (T, B alike, T first), so 1 px remains (imgaug keeps 1 px too).
 
 Image:
   1. the photometric op at source resolution on the BGR buffer as loaded; the HSV ops read it as RGB (as the reference hands cv2's BGR array
@@ -45,6 +54,7 @@ An image whose plan is not augmented (val, with_aug False) keeps its boxes and l
 
 Deviations from the reference (imgaug), one line each:
   * imgaug runs the photometric and geometric blocks in random order; here the photometric op always comes first, at source resolution.
+  * with a split, imgaug's random_order over three blocks becomes one draw of the order of the split and position blocks.
   * imgaug resamples once per geometric op (the keep-size crop by its documented default cubic); here the ops compose into one bilinear warp.
   * the integer-factor INTER_AREA path rounds half to even everywhere (OpenCV's SIMD 2x2 specialisation rounds halves up).
   * the label map is resized with INTER_NEAREST; the reference's Collater passes the flag in cv2.resize's dst slot and so resizes bilinearly.
@@ -54,6 +64,7 @@ from __future__ import annotations
 
 import json
 import math
+import warnings
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -78,10 +89,69 @@ def identity_plan() -> dict:
     return {"augmented": False, "photo": None, "geom": [], "seed": 0}
 
 
-def sample_plan(base_seed: int, epoch: int, index: int, with_aug: bool = True, do_flip: bool = False, do_split: bool = False) -> dict:
-    """one image's plan, a function of (base_seed, epoch, index) alone"""
-    if do_split:
-        raise NotImplementedError("dataloader.do_split: the split crop (MultitaskData.cal_split) is not supported by the device augmentation")
+def cal_split(lanes: dict, width: int, height: int):
+    """MultitaskData.cal_split (dataloader.py:428-480) on a parsed lane dict ({"Lines": [[{"x", "y"}, ...]]}) of a width x height source
+    -> (split possible, split ratio or None), every quirk of the reference kept"""
+    k1, all_lines = [], []
+    for line in lanes["Lines"]:
+        # a point is (int(float(x)), height - int(float(y))): truncation toward zero, y flipped
+        pts = [(int(float(pt["x"])), height - int(float(pt["y"]))) for pt in line]
+        with warnings.catch_warnings():
+            # any warning (RankWarning of a vertical, one-point or degenerate lane) or exception of any lane: no split.  The reference's
+            # `except np.RankWarning` fails itself under numpy 2; this is its numpy-1 meaning
+            warnings.filterwarnings("error")
+            try:
+                coeff = np.polyfit([q[0] for q in pts], [q[1] for q in pts], 1)
+            except Exception:
+                return False, None
+        k1.append(coeff[0])
+        all_lines.append(pts)
+    k1 = np.array(k1)
+    sorted_k1 = np.sort(k1)
+    index = np.argsort(k1)
+    # the reference's misplaced parenthesis: np.all(sorted_k1) <= 0 is true exactly when some slope is exactly 0 (no lanes: the first term)
+    if np.all(sorted_k1 >= 0) or np.all(sorted_k1) <= 0:
+        return False, None
+    left = np.array(all_lines[index[np.where(sorted_k1 <= 0)[0][0]]])        # the most negative slope
+    right = np.array(all_lines[index[-1]])                                     # the largest slope
+    # each lane's points sorted by the flipped y (np.argsort, as the reference), the x of the first
+    left_x = left[np.argsort(left[:, 1], axis=0)][0, 0]
+    right_x = right[np.argsort(right[:, 1], axis=0)][0, 0]
+    return True, float((left_x + right_x) / 2.0 / width)
+
+
+_POSITION_OPS = ["fliplr", "translate_x", "shear_x", "rotate"]
+
+
+def _position_ops(rng, names: List[str]) -> list:
+    """4 of `names` (SomeOf(4)), in list order, with their parameters"""
+    ops = []
+    for i in np.sort(rng.choice(len(names), 4, replace=False)):
+        name = names[i]
+        if name == "translate_x":
+            ops.append((name, int(rng.integers(-16, 17))))
+        elif name in ("shear_x", "rotate"):
+            ops.append((name, float(rng.uniform(-15.0, 15.0))))
+        elif name == "crop":
+            ops.append((name, (float(rng.choice([0.0, 0.2])), float(rng.choice([0.0, 0.15])), 0.0, float(rng.choice([0.0, 0.15])))))
+        else:
+            ops.append((name, None))
+    return ops
+
+
+NO_RATIO = object()           # sample_plan's split_ratio when the caller gave none (None is an answer: the image's lanes give no split)
+
+
+def sample_plan(base_seed: int, epoch: int, index: int, with_aug: bool = True, do_flip: bool = False, do_split: bool = False,
+                split_ratio=NO_RATIO) -> dict:
+    """one image's plan, a function of (base_seed, epoch, index) (and the image's split ratio) alone.  do_split needs split_ratio, the
+    image's cal_split ratio or None when it has none.  A split plan (do_split with a ratio) also carries plan["split"] = {"ratio", "crop":
+    "one" / "two" / None (block not applied), "split_first"}; every other plan is drawn exactly as without do_split."""
+    if do_split and split_ratio is NO_RATIO:
+        raise NotImplementedError("sample_plan(do_split=True) without split_ratio: a split plan needs the image's split ratio "
+                                  "(augment.cal_split of its lanes; None when they give none)")
+    if split_ratio is NO_RATIO:
+        split_ratio = None
     if not with_aug:
         return identity_plan()
     rng = np.random.default_rng([int(base_seed), int(epoch), int(index)])
@@ -103,20 +173,45 @@ def sample_plan(base_seed: int, epoch: int, index: int, with_aug: bool = True, d
         else:
             lo, hi = HSV_RANGES[name]
             plan["photo"] = {"op": name, "factor": float(rng.uniform(lo, hi))}
+    names = _POSITION_OPS + (["flipud"] if do_flip else [])
+    if not (do_split and split_ratio is not None):
+        if rng.random() < 0.6:
+            plan["geom"] = _position_ops(rng, names + ["crop"])
+        return plan
+    r = float(split_ratio)
+    split = {"ratio": r, "crop": None, "split_first": False}
+    crop = []
     if rng.random() < 0.6:
-        names = ["fliplr", "translate_x", "shear_x", "rotate"] + (["flipud"] if do_flip else []) + ["crop"]
-        chosen = np.sort(rng.choice(len(names), 4, replace=False))
-        for i in chosen:
-            name = names[i]
-            if name == "translate_x":
-                plan["geom"].append((name, int(rng.integers(-16, 17))))
-            elif name in ("shear_x", "rotate"):
-                plan["geom"].append((name, float(rng.uniform(-15.0, 15.0))))
-            elif name == "crop":
-                plan["geom"].append((name, (float(rng.choice([0.0, 0.2])), float(rng.choice([0.0, 0.15])), 0.0, float(rng.choice([0.0, 0.15])))))
-            else:
-                plan["geom"].append((name, None))
+        split["crop"] = ("one", "two")[int(rng.integers(2))]
+        top, other = float(rng.choice([0.0, 0.2])), float(rng.choice([0.0, 0.15]))
+        crop = [("crop", (top, 1.0 - r, 0.0, other) if split["crop"] == "one" else (top, other, 0.0, r))]
+    position = _position_ops(rng, names) if rng.random() < 0.6 else []
+    split["split_first"] = bool(rng.random() < 0.5)
+    plan["geom"] = crop + position if split["split_first"] else position + crop
+    plan["split"] = split
     return plan
+
+
+def _keep_one(a: int, b: int, size: int):
+    """crop amounts a (top / left) and b (bottom / right) of one axis, reduced so that at least 1 px of `size` remains"""
+    g = a + b - size + 1
+    if g <= 0:
+        return a, b
+    ga, gb = (g + 1) // 2, g // 2
+    if ga > a:
+        ga, gb = a, g - a
+    elif gb > b:
+        ga, gb = g - b, b
+    return a - ga, b - gb
+
+
+def crop_pixels(param, W: int, H: int):
+    """(T, R, B, L) fractions -> pixels: rint(max(fraction, 0) * size), then the 1 px clamp of the module docstring"""
+    top, right, bottom, left = (max(float(v), 0.0) for v in param)
+    T, R, B, L = (int(np.rint(top * H)), int(np.rint(right * W)), int(np.rint(bottom * H)), int(np.rint(left * W)))
+    T, B = _keep_one(T, B, H)
+    L, R = _keep_one(L, R, W)
+    return T, R, B, L
 
 
 def op_matrix(name: str, param, W: int, H: int) -> np.ndarray:
@@ -139,8 +234,7 @@ def op_matrix(name: str, param, W: int, H: int) -> np.ndarray:
         M[0, 2] = cx - c * cx + s * cy
         M[1, 2] = cy - s * cx - c * cy
     elif name == "crop":
-        top, right, bottom, left = param
-        T, R, B, L = (int(np.rint(top * H)), int(np.rint(right * W)), int(np.rint(bottom * H)), int(np.rint(left * W)))
+        T, R, B, L = crop_pixels(param, W, H)
         sx, sy = W / float(W - L - R), H / float(H - T - B)
         M[0, 0], M[0, 2] = sx, -L * sx
         M[1, 1], M[1, 2] = sy, -T * sy

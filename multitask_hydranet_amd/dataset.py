@@ -1,10 +1,11 @@
 """The reference's MultitaskData over its data-list layout (model/dataset/dataloader.py:164-426, dataset/utility.py:235-257), split for
 device augmentation: a DataLoader worker only decodes the files (PIL, swapped to BGR as cv2.imread delivers), parses the labels, samples the
-image's augmentation plan (augment.sample_plan) and packs the batch's host buffers.  The batch carries `src_frames` / `src_segs` (packed
-uint8), the parsed labels and `aug_plans` instead of `image`; HydraTrainer.to_gpu runs augment.augment_batch on it, which returns the
-Collater contract.  Workers never touch the GPU.
+image's augmentation plan (augment.sample_plan; with dataloader.do_split from the split ratio of the source lanes, by the split rule given
+at construction, e.g. augment.cal_split) and packs the batch's host buffers.  The batch carries `src_frames` / `src_segs` (packed uint8),
+the parsed labels and `aug_plans` instead of `image`; HydraTrainer.to_gpu runs augment.augment_batch on it, which returns the Collater
+contract.  Workers never touch the GPU.
 
-    ds = MultitaskData(cfgs, "train")
+    ds = MultitaskData(cfgs, "train")                 # with dataloader.do_split: MultitaskData(cfgs, "train", split_rule=augment.cal_split)
     loader = DataLoader(ds, batch_size=16, shuffle=True, num_workers=8, collate_fn=ds.collate_fn, pin_memory=True)
     for epoch in ...: ds.set_epoch(epoch); trainer.train_one_epoch(epoch)
 """
@@ -12,6 +13,7 @@ from __future__ import annotations
 
 import json
 import os
+from typing import Callable, Optional
 
 import numpy as np
 
@@ -85,16 +87,24 @@ def imread_label(path):
 class MultitaskData:
     """torch Dataset (map style) of the reference's layout; items are host-side only"""
 
-    def __init__(self, cfgs, mode, base_seed: int = 0):
+    def __init__(self, cfgs, mode, base_seed: int = 0, split_rule: Optional[Callable] = None):
+        """split_rule: (parsed lanes, source width, source height) -> (split possible, ratio), the rule that dataloader.do_split draws
+        its split crops from; augment.cal_split is the reference's (MultitaskData.cal_split, its quirks kept).  A training set with
+        augmentation and do_split needs one, and lane labels to apply it to."""
         dl = cfgs["dataloader"]
         self.cfgs, self.mode, self.base_seed, self.epoch = cfgs, mode, int(base_seed), 0
         self.network_input_width, self.network_input_height = dl["network_input_width"], dl["network_input_height"]
         self.with_aug = bool(dl.get("with_aug", False)) and mode != "val"
         self.do_flip = bool(dl.get("do_flip", False))
-        if dl.get("do_split", False) and self.with_aug:
-            raise NotImplementedError("dataloader.do_split: the split crop (MultitaskData.cal_split) is not supported by the device augmentation")
+        self.do_split = bool(dl.get("do_split", False)) and self.with_aug
+        self.split_rule = split_rule
         t = cfgs["train"]
         self.train_lane, self.train_seg, self.train_detect = t["train_lane"], t["train_seg"], t["train_detect"]
+        if self.do_split and not self.train_lane:
+            raise ValueError("dataloader.do_split needs train.train_lane: the split ratio is computed from the lane labels")
+        if self.do_split and split_rule is None:
+            raise NotImplementedError("dataloader.do_split without a split rule: construct MultitaskData(..., split_rule=augment.cal_split) "
+                                      "for the reference's split ratio")
         if not (self.train_lane or self.train_seg or self.train_detect):
             raise ValueError("must train at least one header")
         if mode not in ("train", "val"):
@@ -116,12 +126,18 @@ class MultitaskData:
         if h < self.network_input_height or w < self.network_input_width:
             raise ValueError("%s: %dx%d is smaller than the network input %dx%d (INTER_AREA does not upscale)"
                              % (pair["image_path"], w, h, self.network_input_width, self.network_input_height))
-        item = dict(src_frame=img, src_image_shape=dict(width=w, height=h, channel=3), src_image_path=pair["image_path"],
-                    aug_plan=sample_plan(self.base_seed, self.epoch, idx, do_flip=self.do_flip) if self.with_aug else identity_plan())
+        item = dict(src_frame=img, src_image_shape=dict(width=w, height=h, channel=3), src_image_path=pair["image_path"])
         if self.train_lane:
             with open(pair["annot_path_lane"]) as f:
                 item["lane_raw"] = parse_own_label(json.load(f))
             item["annot_lane_path"] = pair["annot_path_lane"]
+        if not self.with_aug:
+            item["aug_plan"] = identity_plan()
+        elif self.do_split:                                   # dataloader.py:300-304: the ratio from the source lanes at source size
+            ok, ratio = self.split_rule(item["lane_raw"], w, h)
+            item["aug_plan"] = sample_plan(self.base_seed, self.epoch, idx, do_flip=self.do_flip, do_split=True, split_ratio=ratio if ok else None)
+        else:
+            item["aug_plan"] = sample_plan(self.base_seed, self.epoch, idx, do_flip=self.do_flip)
         if self.train_seg:
             item["src_seg"] = imread_label(pair["annot_path_seg"])
             if item["src_seg"].shape != (h, w):

@@ -1,9 +1,9 @@
 """Training-loop surface around the HIP hot path (reference: model/train.py:31-269 HydraTrainer).
 
 Same roles and names as the reference's trainer for the part that touches the hot path: model construction (+ `module.`-prefixed
-checkpoint loading, train.py:96-126), the data-parallel wrap (train.py:130-137 -> multitask_hydranet_amd.ddp.GradReducer, one process per
-GPU over RCCL), Adam + per-iteration CosineAnnealingLR (train.py:147-150), `cal_total_loss` (train.py:192-203), `to_gpu` (train.py:228-239),
-`train_one_epoch` (train.py:241-269), `valid` (train.py:271-438: losses, streaming mIoU on the device, detection results in COCO json form
+checkpoint loading and the joint warm start from three single-task checkpoints, train.py:90-126), the data-parallel wrap (train.py:130-137
+-> multitask_hydranet_amd.ddp.GradReducer, one process per GPU over RCCL), Adam + per-iteration CosineAnnealingLR (train.py:147-150),
+`cal_total_loss` (train.py:192-203), `to_gpu` (train.py:228-239), `train_one_epoch` (train.py:241-269), `valid` (train.py:271-438: losses, streaming mIoU on the device, detection results in COCO json form
 from the device post-process, lane decode on the device) and `main`'s head-wise fine-tuning schedule (train.py:441-515: run_training /
 tuning_phase / HydraTrainer.set_phase), the lane F1 metric of train.py:188,397,433 (lane_metric.LaneMetric: rasterisation + IoU counts on the
 device).  COCOeval (pycocotools) stays outside (out of scope); any iterable of batch dicts with the Collater contract
@@ -103,8 +103,18 @@ class HydraTrainer:
             dist.init_process_group("nccl", rank=self.rank, world_size=self.world, device_id=self.device)
 
         self.hydranet = HydraNet(cfgs=cfgs).to(self.device)
-        if t.get("continue_train") and t.get("weight_file"):
-            # files written from a DDP wrapper carry "module." prefixes (train.py:96-109 deparallel_model): load_state_dict strips them
+        # train.py:90-126; files written from a DDP wrapper carry "module." prefixes (deparallel_model): load_state_dict strips them
+        flag_joint = self.train_detect and self.train_seg and self.train_lane and t.get("weight_file", "") == ""
+        if t.get("continue_train") and flag_joint:
+            # the joint warm start: the three single-task checkpoints in turn, non-strict, each overriding the shared backbone and neck
+            for key in ("weight_file_lane", "weight_file_seg", "weight_file_det"):
+                path = t.get(key)
+                if not path:
+                    raise ValueError("train.continue_train with all three heads and weight_file \"\" loads train.%s, which is not set" % key)
+                if not os.path.isfile(path):
+                    raise FileNotFoundError("train.%s: no such checkpoint: %s" % (key, path))
+                self.hydranet.load_state_dict(torch.load(path, map_location=self.device), strict=False)
+        elif t.get("continue_train") and t.get("weight_file"):
             self.hydranet.load_state_dict(torch.load(t["weight_file"], map_location=self.device))
         broadcast_state(self.hydranet)                               # what DDP does at construction (train.py:137)
         self.use_distribute = self.world > 1 or self._force_distribute

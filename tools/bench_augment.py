@@ -2,7 +2,10 @@
 Reports the kernels' device-event time (photometric + warp/area/normalise + seg), the host time of collate (pack + plans + label
 transforms, no decode), the pinned H2D copy of the packed frames and, for scale, PIL's JPEG decode of one frame.
 
-    python tools/bench_augment.py [--iters 20]
+    python tools/bench_augment.py [--iters 20] [--split]
+
+--split: dataloader.do_split plans (split ratio 0.5; the photometric draws are those of the plain run) and the host cost of
+augment.cal_split on one 4-lane label.
 """
 import argparse
 import io
@@ -24,7 +27,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--n", type=int, default=16)
+    ap.add_argument("--split", action="store_true")
     a = ap.parse_args()
+    ratio = 0.5 if a.split else None
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(0)
     H, W = 1080, 1920
@@ -35,7 +40,7 @@ def main():
     res = {}
     # host collate (no decode): pack + plans
     items = [dict(src_frame=f, src_seg=s, det_raw=b, lane_raw=l, src_image_shape=dict(width=W, height=H, channel=3), src_image_path="", annot_lane_path="",
-                  aug_plan=A.sample_plan(0, 0, i)) for i, (f, s, b, l) in enumerate(zip(frames, segs, boxes, lanes))]
+                  aug_plan=A.sample_plan(0, 0, i, do_split=a.split, split_ratio=ratio)) for i, (f, s, b, l) in enumerate(zip(frames, segs, boxes, lanes))]
     t = time.perf_counter()
     for _ in range(3):
         batch = collate(items, 640, 640)
@@ -53,7 +58,7 @@ def main():
     res["h2d_ms"] = e0.elapsed_time(e1) / a.iters
     res["h2d_GBps"] = pinned.numel() / (res["h2d_ms"] * 1e-3) / 1e9
     for out_hw in ((640, 640), (512, 1024)):
-        plans = [A.sample_plan(0, 1, i) for i in range(a.n)]
+        plans = [A.sample_plan(0, 1, i, do_split=a.split, split_ratio=ratio) for i in range(a.n)]
         t = time.perf_counter()
         out = A.augment_batch(batch["src_frames"], lanes, boxes, batch["src_segs"], plans, out_hw, dev)   # labels + descriptors + launches
         torch.cuda.synchronize()
@@ -91,6 +96,16 @@ def main():
         torch.cuda.synchronize()
         res["kernels_ms_%dx%d" % out_hw[::-1]] = e0.elapsed_time(e1) / a.iters
         res["photometric_images_%dx%d" % out_hw[::-1]] = int((desc["op"] > 0).sum())
+        res["split_crops_%dx%d" % out_hw[::-1]] = sum(p.get("split", {}).get("crop") is not None for p in plans)
+    if a.split:
+        # two lanes leaning in, two leaning out, 20 points each: one image's cal_split on this core
+        split_lanes = {"Lines": [[{"x": x0 + dx * k, "y": 1079.0 - 25 * k} for k in range(20)]
+                                 for x0, dx in ((300.0, 20.0), (700.0, 8.0), (1200.0, -8.0), (1700.0, -20.0))]}
+        assert A.cal_split(split_lanes, W, H)[0]
+        t = time.perf_counter()
+        for _ in range(2000):
+            A.cal_split(split_lanes, W, H)
+        res["cal_split_us_per_item"] = (time.perf_counter() - t) / 2000 * 1e6
     from PIL import Image
     bio = io.BytesIO()
     Image.fromarray(frames[0]).save(bio, format="JPEG", quality=90)
