@@ -641,6 +641,24 @@ int hn_augment_photometric(const void* src, const void* desc, int N, int max_hs,
 int hn_augment_image(const void* src, const void* ws, const void* desc, int N, int Hd, int Wd, float* dst, hipStream_t stream);
 int hn_augment_seg(const void* seg, const void* desc, int N, int Hd, int Wd, void* dst, hipStream_t stream);
 
+/* Baseline JPEG decode, entropy stage on the host and the rest on the device (jpeg.py; hn_jpeg.hip, semantics in DESIGN.md 4g).
+ * Supported: 8-bit Huffman SOF0 / SOF1, one interleaved scan, 1 component or YCbCr with luma 1x1 / 2x1 / 2x2 and chroma 1x1, restart
+ * intervals.  hn_jpeg_parse and hn_jpeg_entropy_decode are HOST functions (no HIP runtime call, no allocation; they run without a GPU):
+ * status 3 = outside the supported set, 1 = not a well-formed JPEG (or a corrupt / truncated scan).  head: a 432-byte JpegHead record
+ * (width, height, components, sampling, MCU counts, restart interval, coef_bytes, quantisation tables in natural order; layout in
+ * hn_jpeg.hip and jpeg.py HEAD_DTYPE).  hn_jpeg_entropy_decode writes head.coef_bytes bytes of quantised int16 coefficients into the
+ * caller's buffer: one de-zigzagged 64-entry block per 8x8 block, component plane after component plane, blocks in raster order of the
+ * plane padded to whole MCUs; no read leaves [data, data + len) and no write leaves [coefs, coefs + coef_bytes). */
+int hn_jpeg_parse(const void* data, long len, void* head);
+int hn_jpeg_entropy_decode(const void* data, long len, const void* head, void* coefs, long coef_bytes);
+/* Device stage for a ragged batch: desc = DEVICE array of N 440-byte JpegDesc (offsets into coefs / planes / dst, geometry, quantisation
+ * tables).  Dequantise + libjpeg's accurate integer IDCT into uint8 sample planes (planes: scratch, 64 bytes per block, 16-byte aligned,
+ * as coefs), then libjpeg's fancy chroma up-sampling + YCbCr -> BGR uint8 H x W x 3 at dst + dst_off (augment.pack's frame layout).
+ * max_blocks / max_h / max_w: the largest block count / height / width of the batch (grid extents).  The three byte counts bound every
+ * access: an image whose descriptor does not fit them is left unwritten.  Two launches, no allocation, no synchronisation. */
+int hn_jpeg_decode(const void* coefs, long coef_bytes, const void* desc, int N, long max_blocks, int max_h, int max_w, void* planes,
+                   long plane_bytes, void* dst, long dst_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,8 @@ device augmentation: a DataLoader worker only decodes the files (PIL, swapped to
 image's augmentation plan (augment.sample_plan; with dataloader.do_split from the split ratio of the source lanes, by the split rule given
 at construction, e.g. augment.cal_split) and packs the batch's host buffers.  The batch carries `src_frames` / `src_segs` (packed uint8),
 the parsed labels and `aug_plans` instead of `image`; HydraTrainer.to_gpu runs augment.augment_batch on it, which returns the Collater
-contract.  Workers never touch the GPU.
+contract.  Workers never touch the GPU.  With decode="device" a worker stops after the JPEG's entropy stage (jpeg.py: host functions of the
+library) and the batch carries `src_coefs`, which to_gpu decodes on the device into the same packed frames.
 
     ds = MultitaskData(cfgs, "train")                 # with dataloader.do_split: MultitaskData(cfgs, "train", split_rule=augment.cal_split)
     loader = DataLoader(ds, batch_size=16, shuffle=True, num_workers=8, collate_fn=ds.collate_fn, pin_memory=True)
@@ -87,10 +88,16 @@ def imread_label(path):
 class MultitaskData:
     """torch Dataset (map style) of the reference's layout; items are host-side only"""
 
-    def __init__(self, cfgs, mode, base_seed: int = 0, split_rule: Optional[Callable] = None):
+    def __init__(self, cfgs, mode, base_seed: int = 0, split_rule: Optional[Callable] = None, decode: str = "host"):
         """split_rule: (parsed lanes, source width, source height) -> (split possible, ratio), the rule that dataloader.do_split draws
         its split crops from; augment.cal_split is the reference's (MultitaskData.cal_split, its quirks kept).  A training set with
-        augmentation and do_split needs one, and lane labels to apply it to."""
+        augmentation and do_split needs one, and lane labels to apply it to.
+        decode: "host" -- the worker decodes the JPEG with PIL (`src_frame`); "device" -- the worker runs only the entropy stage
+        (jpeg.parse + jpeg.entropy_decode: `src_coefs` + `jpeg_head`) and HydraTrainer.to_gpu finishes the decode on the device
+        (jpeg.decode_batch); a file outside jpeg.py's supported set is decoded with PIL as before, that image only."""
+        if decode not in ("host", "device"):
+            raise ValueError("decode should be one of ('host', 'device')")
+        self.decode = decode
         dl = cfgs["dataloader"]
         self.cfgs, self.mode, self.base_seed, self.epoch = cfgs, mode, int(base_seed), 0
         self.network_input_width, self.network_input_height = dl["network_input_width"], dl["network_input_height"]
@@ -121,12 +128,23 @@ class MultitaskData:
 
     def __getitem__(self, idx):
         pair = self.image_annot_path_pairs[idx]
-        img = imread_bgr(pair["image_path"])
-        h, w = img.shape[:2]
+        head = None
+        if self.decode == "device":
+            from . import jpeg
+            if not os.path.exists(pair["image_path"]):
+                raise FileNotFoundError(pair["image_path"])
+            head, img = jpeg.host_stage(jpeg.read_bytes(pair["image_path"]))       # (header, coefficients) or (None, PIL's frame)
+            h, w = (head["height"], head["width"]) if head is not None else img.shape[:2]
+        else:
+            img = imread_bgr(pair["image_path"])
+            h, w = img.shape[:2]
         if h < self.network_input_height or w < self.network_input_width:
             raise ValueError("%s: %dx%d is smaller than the network input %dx%d (INTER_AREA does not upscale)"
                              % (pair["image_path"], w, h, self.network_input_width, self.network_input_height))
-        item = dict(src_frame=img, src_image_shape=dict(width=w, height=h, channel=3), src_image_path=pair["image_path"])
+        if head is not None:
+            item = dict(src_coefs=img, jpeg_head=head, src_image_shape=dict(width=w, height=h, channel=3), src_image_path=pair["image_path"])
+        else:
+            item = dict(src_frame=img, src_image_shape=dict(width=w, height=h, channel=3), src_image_path=pair["image_path"])
         if self.train_lane:
             with open(pair["annot_path_lane"]) as f:
                 item["lane_raw"] = parse_own_label(json.load(f))
@@ -151,8 +169,15 @@ class MultitaskData:
 
 
 def collate(batch, net_h, net_w):
-    """host half of the Collater: the frames (and label maps) packed into one uint8 buffer each; labels and plans as lists"""
-    out = dict(src_frames=pack([b["src_frame"] for b in batch]), aug_plans=[b["aug_plan"] for b in batch],
+    """host half of the Collater: the frames (and label maps) packed into one uint8 buffer each; labels and plans as lists.  A batch with
+    entropy-decoded items (decode="device") carries `src_coefs` instead of `src_frames`: jpeg.pack_coefs' buffers, the PIL-decoded frames of
+    its unsupported files among them."""
+    if any("src_coefs" in b for b in batch):
+        from .jpeg import pack_coefs
+        src = dict(src_coefs=pack_coefs([(b["jpeg_head"], b["src_coefs"]) if "src_coefs" in b else (None, b["src_frame"]) for b in batch]))
+    else:
+        src = dict(src_frames=pack([b["src_frame"] for b in batch]))
+    out = dict(**src, aug_plans=[b["aug_plan"] for b in batch],
                src_image_shape=[b["src_image_shape"] for b in batch], src_image_path=[b["src_image_path"] for b in batch],
                net_input_image_shape=[json.dumps(dict(width=net_w, height=net_h, channel=3))] * len(batch), net_input_hw=(net_h, net_w))
     if "lane_raw" in batch[0]:
