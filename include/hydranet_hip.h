@@ -659,6 +659,29 @@ int hn_jpeg_entropy_decode(const void* data, long len, const void* head, void* c
 int hn_jpeg_decode(const void* coefs, long coef_bytes, const void* desc, int N, long max_blocks, int max_h, int max_w, void* planes,
                    long plane_bytes, void* dst, long dst_bytes, hipStream_t stream);
 
+/* Baseline JPEG encode, the mirror image (jpeg_encode.py; hn_jpeg_enc.hip, semantics in DESIGN.md 4h): libjpeg's default compressor, all
+ * integer.  Device stage for a ragged batch: desc = DEVICE array of N 432-byte JpegEncDesc (offsets into frames / coefs, geometry,
+ * quantisation tables in natural order).  frames: packed BGR uint8 H x W x 3 frames (augment.pack's layout; a 1-component image encodes
+ * channel 0); coefs: quantised int16 coefficients in hn_jpeg_entropy_decode's layout, blocks that only fill an MCU written as zeros.
+ * max_mcus_y / max_wpad: the largest MCU-row count and MCU-padded width of the batch (grid extents).  Both pointers 16-byte aligned.  The
+ * two byte counts bound every access: an image whose descriptor does not fit them is left unwritten.  One launch, no allocation, no
+ * synchronisation. */
+int hn_jpeg_encode(const void* frames, long frames_bytes, const void* desc, int N, int max_mcus_y, int max_wpad, void* coefs,
+                   long coef_bytes, hipStream_t stream);
+/* HOST function (no HIP runtime call, no allocation): coefficients + a 432-byte JpegHead record (restart_interval 0, 8-bit tables,
+ * qt[1] == qt[2]) -> a complete JFIF stream (SOI, APP0, DQT, SOF0, DHT with the Annex K tables, one interleaved SOS, EOI) in out.  Returns
+ * the stream's length; -4 when `capacity` is too small (nothing is written at or past out + capacity: call again with a larger buffer);
+ * -1 for a bad argument or a coefficient no baseline table can code.  The blocks that only fill an MCU are synthesised (AC zero, DC of
+ * the preceding block), whatever the buffer holds there. */
+long hn_jpeg_entropy_encode(const void* coefs, long coef_bytes, const void* head, void* out, long capacity);
+
+/* Drawing on packed BGR frames, in place (draw.py; hn_draw.hip): imgs = DEVICE array of N 24-byte DrawImage (frame offset, W, H, its range
+ * of the primitive list), prims = DEVICE array of 32-byte DrawPrim (kind 0 thick segment / 1 filled rectangle / 2 glyph bitmap, colour).  A
+ * pixel takes the colour of the LAST primitive of its image's range that covers it.  Coordinates within +-16384.  frames_bytes / nprims
+ * bound every access: an image whose record does not fit them is left untouched.  One launch, no allocation, no synchronisation. */
+int hn_draw(void* frames, long frames_bytes, const void* imgs, int N, int max_h, int max_w, const void* prims, int nprims,
+            hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

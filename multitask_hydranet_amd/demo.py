@@ -1,5 +1,6 @@
 """demo.py of the reference (model/demo.py:52-261) on the HIP path: frame -> pre-processing -> HydraNet forward -> the three decodes.
 
+    python -m multitask_hydranet_amd.demo [--cfg cfgs/hydranet_big.yml] [--weights ckpt.pth] --images DIR --out DIR_VIS
     python -m multitask_hydranet_amd.demo [--cfg cfgs/hydranet_big.yml] [--weights ckpt.pth] [--frames frames.npy] [--out demo_out]
 
 What is kept: the configuration handling (network input size, which heads run, lane codec geometry, colour table), `module.`-prefixed
@@ -7,9 +8,13 @@ checkpoints (deparallel_model, demo.py:33-50), the per-frame sequence BGR -> RGB
 laneheader.decode + scale_to_org, segheader.decode, detectheader.decode, and the thresholds demo.py hard-codes (lane 0.90 / 80, detection
 0.4 / 0.3).  Every stage runs on the device (hn_preprocess_bgr, the folded-BatchNorm inference forward, hn_lane_decode_nms,
 hn_seg_overlay, hn_det_postprocess).
-What is not: cv2 (absent from this image).  Frames come from a .npy array [T, H, W, 3] uint8 BGR or are synthesised; instead of a window
-/ video writer the blended frames are returned (and written as .npy by the command line); the line / box / text drawing of
-laneheader.visual and detectheader.display is visualisation outside SURVEY 8 -- the decoded lanes and boxes are returned as data."""
+--images is the reference's image-folder mode (demo.py:136-160, 260-261): every *.jpg / *.jpeg of DIR in sorted order is decoded onto the
+device (jpeg.imread_bgr_device), runs the sequence above, is DRAWN in the reference's order -- laneheader.visual, the seg overlay,
+detectheader.display (draw.py) -- and is written as a JPEG of the same name into --out (jpeg_encode); the frame stays on the device from
+decode to encode (Demo.process_device).
+What is not: cv2 (absent from this image), so no window and no video input / writer.  Without --images the frames come from a .npy array
+[T, H, W, 3] uint8 BGR or are synthesised, the blended frames are returned without drawing (and written as .npy by the command line) and
+the decoded lanes and boxes are returned as data (Demo.process)."""
 from __future__ import annotations
 
 import argparse
@@ -82,6 +87,67 @@ class Demo:
         return res
 
 
+    @torch.no_grad()
+    def process_device(self, frames: dict, quality: int = 95, subsampling: str = "4:2:0") -> Dict[str, object]:
+        """the same iteration for ONE frame that is already on the device in the packed layout of jpeg.imread_bgr_device, with the
+        reference's drawing (demo.py:230, 235, 244) and its cv2.imwrite (demo.py:261): "jpeg" holds the annotated frame's JFIF bytes,
+        "visual" the annotated frame in the packed device layout.  The frame is not copied to the host."""
+        from . import draw, jpeg_encode
+        from .preprocess import preprocess_bgr
+        from .visual import seg_decode_device
+        net = self.net
+        assert len(frames["shapes"]) == 1, "one frame per call"
+        org_h, org_w = (int(v) for v in frames["shapes"][0])
+        org_size = (org_w, org_h)
+        nbytes = org_h * org_w * 3
+        tic = time.time()
+        off = int(frames["offsets"][0])
+        frame = frames["data"][off:off + nbytes].view(1, org_h, org_w, 3)
+        img = preprocess_bgr(frame, (self.net_h, self.net_w), device=self.device)
+        outputs = net(img)
+        res: Dict[str, object] = {"org_size": org_size}
+        if self.train_lane:
+            cls_preds, loc_preds = outputs["lane"]["predict_cls"], outputs["lane"]["predict_loc"]
+            nms_set = net.laneheader.decode(cls_preds[0], loc_preds[0], self.lane_coder, self.lane_conf, self.lane_nms, False)
+            res["lanes"] = [net.laneheader.scale_to_org(nms_set, self.net_w, self.net_h, org_w, org_h)["Lines"]]
+            frames = net.laneheader.visual(frames, res["lanes"], org_w, filter_vertical=True)
+        if self.train_seg:
+            blended = seg_decode_device(frame, outputs["seg"], self.colors)
+            frames = {"data": blended.view(-1), "offsets": np.zeros(1, np.int64), "shapes": np.array([[org_h, org_w]], np.int64)}
+        if self.train_detect:
+            det = outputs["detection"]
+            res["detections"] = net.detectheader.decode(img, det["regression"], det["classification"], det["anchors"], conf_thres=self.det_conf,
+                                                        iou_thres=self.det_iou)
+            frames = net.detectheader.display(res["detections"], frames, self.obj_list, org_size, (self.net_w, self.net_h))
+        res["jpeg"] = jpeg_encode.encode_batch(frames, quality, subsampling)[0]
+        res["visual"] = frames
+        res["ms"] = 1000.0 * (time.time() - tic)
+        return res
+
+
+def list_images(folder: str) -> List[str]:
+    """the *.jpg / *.jpeg files of the folder, sorted by name"""
+    return [os.path.join(folder, f) for f in sorted(os.listdir(folder)) if f.lower().endswith((".jpg", ".jpeg"))]
+
+
+def run_images(demo: "Demo", folder: str, out_dir: str, quality: int = 95, subsampling: str = "4:2:0") -> List[dict]:
+    """--images: folder of JPEGs -> annotated JPEGs of the same names in out_dir, plus results.json"""
+    import json
+    from . import jpeg
+    os.makedirs(out_dir, exist_ok=True)
+    summary = []
+    for t, path in enumerate(list_images(folder)):
+        r = demo.process_device(jpeg.imread_bgr_device(path, device=demo.device), quality, subsampling)
+        with open(os.path.join(out_dir, os.path.basename(path)), "wb") as f:
+            f.write(r["jpeg"])
+        nd = sum(len(d["rois"]) for d in r.get("detections", []) or [])
+        nl = sum(len(l) for l in r.get("lanes", []))
+        print("frame %d (%s): total process time is %i ms, %d lanes, %d boxes" % (t, os.path.basename(path), r["ms"], nl, nd))
+        summary.append({"frame": t, "file": os.path.basename(path), "ms": r["ms"], "lanes": nl, "boxes": nd})
+    json.dump(summary, open(os.path.join(out_dir, "results.json"), "w"), indent=1)
+    return summary
+
+
 def synthetic_frames(n: int, h: int = 1080, w: int = 1920, seed: int = 0) -> np.ndarray:
     """road-like BGR frames: sky / ground gradient, two lane-ish bright bands, a few boxes, noise"""
     rs = np.random.RandomState(seed)
@@ -106,8 +172,10 @@ def main(argv=None):
     ap.add_argument("--cfg", default=os.path.join(root, "cfgs", "hydranet_big.yml"))
     ap.add_argument("--weights", default=None, help="checkpoint written by train.py (module.-prefixed keys are accepted); random init without")
     ap.add_argument("--frames", default=None, help=".npy uint8 [T, H, W, 3] BGR frames; synthetic 1080p frames without")
+    ap.add_argument("--images", default=None, help="folder of *.jpg / *.jpeg frames: each is annotated and written as a JPEG of the same name into --out")
+    ap.add_argument("--quality", type=int, default=95, help="JPEG quality of the annotated frames (--images)")
     ap.add_argument("--count", type=int, default=4)
-    ap.add_argument("--out", default=None, help="directory for frame_%%04d.npy (blended frames) and results.json")
+    ap.add_argument("--out", default=None, help="directory for the annotated JPEGs (--images) or frame_%%04d.npy (blended frames), and results.json")
     args = ap.parse_args(argv)
     cfgs = yaml.safe_load(open(args.cfg))
     torch.manual_seed(0)
@@ -116,6 +184,10 @@ def main(argv=None):
         # random initialisation: every anchor scores ~0.5, far more candidates than any real frame has (the device NMS holds 32 768)
         print("no --weights: random initialisation, detection threshold raised to 0.95 for this run")
         demo.det_conf = 0.95
+    if args.images:
+        if not args.out:
+            ap.error("--images needs --out")
+        return run_images(demo, args.images, args.out, args.quality)
     frames = np.load(args.frames) if args.frames else synthetic_frames(args.count)
     if args.out:
         os.makedirs(args.out, exist_ok=True)

@@ -264,14 +264,16 @@ class HydraNet(nn.Module):
             self.detectheader.decode = _det_decode
             from .coco_json import invert_affine       # DetectionHeader.invert_affine (head_detect/detection.py:217-230; train.py:334-336)
             self.detectheader.invert_affine = invert_affine
-            self.detectheader.display = _unavailable("detectheader.display (cv2 box / label drawing, head_detect/detection.py:247-252)")
+            from .draw import display                  # DetectionHeader.display (head_detect/display.py:49-84) on the device
+            self.detectheader.display = _drawing_helper(display, "detectheader.display")
         if self.train_lane:
             object.__setattr__(self.laneheader, "_fwd", lambda fused: flushed(me()._lane([K_to_nhwc(t) for t in fused])))
             from . import lane_codec as LC             # LaneHeader.decode / scale_to_org (head_lane/lanedetect.py:103-124) on the device
             self.laneheader.decode = LC.decode
             self.laneheader.decode_batch = LC.decode_batch
             self.laneheader.scale_to_org = LC.scale_to_org
-            self.laneheader.visual = _unavailable("laneheader.visual (cv2 visualisation)")
+            from .draw import visual                   # LaneHeader.visual (head_lane/lanedetect.py:126-178) on the device
+            self.laneheader.visual = _drawing_helper(visual, "laneheader.visual")
 
     def _reindex(self):
         self._idx = {k: v for k, v in itertools.chain(self.named_parameters(), self.named_buffers()) if not k.startswith("_")}
@@ -924,10 +926,15 @@ def K_to_nhwc(t):
     return t.permute(0, 2, 3, 1).contiguous().to(torch.bfloat16)
 
 
-def _unavailable(what):
-    def f(*a, **k):
-        raise NotImplementedError(what + " is outside the forward/backward hot path (SURVEY.md section 8f)")
-    return f
+def _drawing_helper(fn, what):
+    """a head's drawing helper (draw.py).  A call that hands over nothing to draw into keeps the answer this surface has always given
+    for it, NotImplementedError, instead of a TypeError about missing parameters; every other call is the helper's."""
+    def helper(*args, **kwargs):
+        if not args and not kwargs:
+            raise NotImplementedError(what + " draws into frames: call it with the reference's arguments (multitask_hydranet_amd/draw.py)")
+        return fn(*args, **kwargs)
+    helper.__doc__, helper.__wrapped__ = fn.__doc__, fn
+    return helper
 
 
 def _det_decode(imgs, regressions, classifications, anchors, conf_thres=0.6, iou_thres=0.3):

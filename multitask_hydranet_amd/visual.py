@@ -5,7 +5,7 @@ demo.py:232-235).  arg-max (hn_argmax / already fused into the deploy forward) -
 cv2 is absent from this image, so the two cv2 calls are restated from OpenCV's published arithmetic (parity UNPINNED, checked against the
 oracle's restatement): `cv2.resize(vis_seg, org_size, cv2.INTER_NEAREST)` passes the flag as the `dst` argument -- the effective
 interpolation is the default INTER_LINEAR in its 11-bit fixed-point form; `cv2.addWeighted` on uint8 = float32 arithmetic, round half to
-even, saturate.  LaneHeader.visual / DetectionHeader.display (cv2 line / box / text drawing) stay outside the scope."""
+even, saturate.  LaneHeader.visual / DetectionHeader.display (cv2 line / box / text drawing) are draw.py's."""
 from __future__ import annotations
 
 from typing import Dict, List, Sequence
@@ -35,6 +35,16 @@ def seg_overlay(frames: torch.Tensor, mask: torch.Tensor, lut: torch.Tensor) -> 
     lib().call("hn_seg_overlay", mask.data_ptr(), n, h, w, lut.data_ptr(), lut.shape[0], frames.data_ptr(), out.data_ptr(), frames.shape[1],
                frames.shape[2])
     return out
+
+
+def seg_decode_device(frames: torch.Tensor, masks: torch.Tensor, vis_color_id) -> torch.Tensor:
+    """seg_decode for frames that are already on the device: uint8 [N, Ho, Wo, 3] + seg logits [N, C, H, W] or an int64 class-id mask
+    [N, H, W] -> the blended frames, on the device (the same two launches as seg_decode, no host copy)"""
+    from . import ops as K
+    masks = masks.to(frames.device)
+    if masks.dim() == 4:
+        masks = K.argmax_channels(masks.detach().float())
+    return seg_overlay(frames, masks, colour_lut(vis_color_id, frames.device))
 
 
 def seg_decode(imgs, masks, org_size, vis_color_id) -> List[np.ndarray]:
