@@ -674,6 +674,25 @@ int hn_jpeg_encode(const void* frames, long frames_bytes, const void* desc, int 
  * -1 for a bad argument or a coefficient no baseline table can code.  The blocks that only fill an MCU are synthesised (AC zero, DC of
  * the preceding block), whatever the buffer holds there. */
 long hn_jpeg_entropy_encode(const void* coefs, long coef_bytes, const void* head, void* out, long capacity);
+/* HOST function (no HIP runtime call, no allocation): exactly the bytes hn_jpeg_entropy_encode writes before the first scan bit (SOI, APP0,
+ * DQT, SOF0, four DHT -- two for a 1-component image -- and SOS) for the same 432-byte JpegHead record.  Returns their count; -4 when
+ * `capacity` is too small (nothing is written at or past out + capacity); -1 for a bad argument. */
+long hn_jpeg_write_header(const void* head, void* out, long capacity);
+/* The entropy stage on the device (jpeg_encode.entropy_encode_device; hn_jpeg_huff.hip, semantics in DESIGN.md 4h): coefs in the layout
+ * hn_jpeg_encode writes -> every image's byte-stuffed scan, the last byte padded with one-bits, bit for bit what hn_jpeg_entropy_encode
+ * writes between its header and its EOI (neither of which is written here).  desc = DEVICE array of N 56-byte JpegHuffDesc {long coef_off
+ * (multiple of 16), out_off, out_cap; int W, H, ncomp, hs, vs, mcus_x, mcus_y, pad}: the image's scan goes to out + out_off and may use
+ * out_cap bytes.  result = DEVICE array of N 16-byte records {long scan_bytes; int status, pad}: status 0 and the scan's length; -4 when
+ * the stuffed scan is longer than out_cap; -1 for a descriptor that does not fit coef_bytes / out_bytes / max_blocks / max_cap or a
+ * coefficient no baseline table can code (a DC difference of more than 11 bits, an AC value of more than 10: what the host stage refuses).
+ * An image with a non-zero status has scan_bytes 0 and nothing written to out; no write ever lands at or past its out_cap, or outside
+ * [ws, ws + hn_jpeg_huff_ws_bytes(...)).  The blocks that only fill an MCU are not read.  max_blocks / max_cap: the largest block count
+ * (coefficient bytes / 128) and capacity of the batch; they size the grids and the workspace, whose size hn_jpeg_huff_ws_bytes returns
+ * (-1 for arguments out of range).  ws needs no clearing, before the first call or between calls.  coefs and ws 16-byte aligned, result
+ * 8-byte.  Six launches, no allocation, no synchronisation, no memset; no workgroup waits on another. */
+long hn_jpeg_huff_ws_bytes(int N, long max_blocks, long max_cap);
+int hn_jpeg_huff_encode(const void* coefs, long coef_bytes, const void* desc, int N, long max_blocks, long max_cap, void* ws, long ws_bytes,
+                        void* out, long out_bytes, void* result, hipStream_t stream);
 
 /* Drawing on packed BGR frames, in place (draw.py; hn_draw.hip): imgs = DEVICE array of N 24-byte DrawImage (frame offset, W, H, its range
  * of the primitive list), prims = DEVICE array of 32-byte DrawPrim (kind 0 thick segment / 1 filled rectangle / 2 glyph bitmap, colour).  A

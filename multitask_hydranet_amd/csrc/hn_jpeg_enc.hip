@@ -12,8 +12,11 @@
 //   hn_jpeg_entropy_encode  coefficients -> a complete JFIF stream (SOI, APP0, DQT, SOF0, DHT with the Annex K tables, one interleaved
 //                           SOS, byte stuffing, EOI) into a caller buffer of stated capacity.  The MCU-filling blocks are synthesised as
 //                           libjpeg's compress_data does: AC zero, DC of the preceding block.
+//   hn_jpeg_write_header    the same stream's bytes before the first scan bit, alone: the device entropy stage (hn_jpeg_huff.hip) writes
+//                           the scan, the host the header and EOI.
 // All arithmetic is integer and exact.
 #include "hn_common.h"
+#include "hn_jpeg_tables.h"
 #include <string.h>
 
 struct JpegEncHead {                   // the first 48 bytes + tables of hn_jpeg.hip's JpegHead (jpeg.py HEAD_DTYPE, 432 bytes)
@@ -40,32 +43,6 @@ static_assert(sizeof(JpegEncDesc) == 432, "JpegEncDesc layout is mirrored by jpe
 
 // ---- host: entropy stage -------------------------------------------------------------------------------------------------------------
 namespace {
-
-const unsigned char k_zz[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-// ITU-T T.81 Annex K.3: BITS and HUFFVAL of the four typical tables
-const unsigned char k_dc_bits[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
-const unsigned char k_dc_vals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
-const unsigned char k_ac_bits[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}};
-const unsigned char k_ac_vals[2][162] = {
-    {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1,
-     0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26,
-     0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56,
-     0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85,
-     0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa,
-     0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6,
-     0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
-     0xfa},
-    {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42,
-     0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19,
-     0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55,
-     0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83,
-     0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8,
-     0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4,
-     0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
-     0xfa}};
 
 struct EncTab {
     unsigned short code[256];
@@ -160,25 +137,26 @@ void put_dht(Sink& s, int tc_th, const unsigned char* bits, const unsigned char*
     for (int i = 0; i < n; ++i) s.byte(vals[i]);
 }
 
-}  // namespace
-
-extern "C" long hn_jpeg_entropy_encode(const void* coefs, long coef_bytes, const void* head, void* out, long capacity) {
-    if (!coefs || !head || !out || capacity < 0) return -(long)HN_ERR_ARG;
-    JpegEncHead h;
+// the header record as both host entry points accept it; false = a bad argument
+bool load_head(JpegEncHead& h, const void* head) {
     memcpy(&h, head, sizeof(h));
     const int nc = h.ncomp;
     if (h.width < 1 || h.width > 65535 || h.height < 1 || h.height > 65535 || (nc != 1 && nc != 3) || (h.hs != 1 && h.hs != 2) ||
         (h.vs != 1 && h.vs != 2) || (h.vs == 2 && h.hs != 2) || (nc == 1 && (h.hs != 1 || h.vs != 1)) || h.restart_interval != 0 ||
         h.mcus_x != (h.width + 8 * h.hs - 1) / (8 * h.hs) || h.mcus_y != (h.height + 8 * h.vs - 1) / (8 * h.vs))
-        return -(long)HN_ERR_ARG;
+        return false;
     const long nblocks = (long)h.mcus_x * h.mcus_y * (h.hs * h.vs + (nc == 3 ? 2 : 0));
-    if (h.coef_bytes != nblocks * 128 || coef_bytes < h.coef_bytes) return -(long)HN_ERR_ARG;
+    if (h.coef_bytes != nblocks * 128) return false;
     for (int c = 0; c < nc; ++c)
         for (int i = 0; i < 64; ++i)
-            if (h.qt[c][i] < 1 || h.qt[c][i] > 255) return -(long)HN_ERR_ARG;
-    if (nc == 3 && memcmp(h.qt[1], h.qt[2], sizeof(h.qt[1])) != 0) return -(long)HN_ERR_ARG;
+            if (h.qt[c][i] < 1 || h.qt[c][i] > 255) return false;
+    if (nc == 3 && memcmp(h.qt[1], h.qt[2], sizeof(h.qt[1])) != 0) return false;
+    return true;
+}
 
-    Sink s = {(unsigned char*)out, capacity, 0, false, 0ull, 0};
+// everything before the first scan bit: SOI, APP0, DQT, SOF0, DHT, SOS
+void put_header(Sink& s, const JpegEncHead& h) {
+    const int nc = h.ncomp;
     s.be16(0xFFD8);
     s.be16(0xFFE0);                                                      // APP0: JFIF 1.01, no units, 1:1, no thumbnail
     s.be16(16);
@@ -219,6 +197,27 @@ extern "C" long hn_jpeg_entropy_encode(const void* coefs, long coef_bytes, const
         s.byte(c ? 0x11 : 0x00);
     }
     s.byte(0); s.byte(63); s.byte(0);
+}
+
+}  // namespace
+
+extern "C" long hn_jpeg_write_header(const void* head, void* out, long capacity) {
+    if (!head || !out || capacity < 0) return -(long)HN_ERR_ARG;
+    JpegEncHead h;
+    if (!load_head(h, head)) return -(long)HN_ERR_ARG;
+    Sink s = {(unsigned char*)out, capacity, 0, false, 0ull, 0};
+    put_header(s, h);
+    return s.full ? HN_JPEG_ENC_FULL : s.pos;
+}
+
+extern "C" long hn_jpeg_entropy_encode(const void* coefs, long coef_bytes, const void* head, void* out, long capacity) {
+    if (!coefs || !head || !out || capacity < 0) return -(long)HN_ERR_ARG;
+    JpegEncHead h;
+    if (!load_head(h, head) || coef_bytes < h.coef_bytes) return -(long)HN_ERR_ARG;
+    const int nc = h.ncomp;
+
+    Sink s = {(unsigned char*)out, capacity, 0, false, 0ull, 0};
+    put_header(s, h);
     if (s.full) return HN_JPEG_ENC_FULL;
 
     EncTab dc[2], ac[2];

@@ -88,10 +88,11 @@ class Demo:
 
 
     @torch.no_grad()
-    def process_device(self, frames: dict, quality: int = 95, subsampling: str = "4:2:0") -> Dict[str, object]:
+    def process_device(self, frames: dict, quality: int = 95, subsampling: str = "4:2:0", entropy: str = "host") -> Dict[str, object]:
         """the same iteration for ONE frame that is already on the device in the packed layout of jpeg.imread_bgr_device, with the
         reference's drawing (demo.py:230, 235, 244) and its cv2.imwrite (demo.py:261): "jpeg" holds the annotated frame's JFIF bytes,
-        "visual" the annotated frame in the packed device layout.  The frame is not copied to the host."""
+        "visual" the annotated frame in the packed device layout.  The frame is not copied to the host.  entropy: "host" | "device", where
+        the Huffman stage of the encode runs (jpeg_encode.encode_batch); the bytes are the same."""
         from . import draw, jpeg_encode
         from .preprocess import preprocess_bgr
         from .visual import seg_decode_device
@@ -119,7 +120,7 @@ class Demo:
             res["detections"] = net.detectheader.decode(img, det["regression"], det["classification"], det["anchors"], conf_thres=self.det_conf,
                                                         iou_thres=self.det_iou)
             frames = net.detectheader.display(res["detections"], frames, self.obj_list, org_size, (self.net_w, self.net_h))
-        res["jpeg"] = jpeg_encode.encode_batch(frames, quality, subsampling)[0]
+        res["jpeg"] = jpeg_encode.encode_batch(frames, quality, subsampling, entropy)[0]
         res["visual"] = frames
         res["ms"] = 1000.0 * (time.time() - tic)
         return res
@@ -130,14 +131,14 @@ def list_images(folder: str) -> List[str]:
     return [os.path.join(folder, f) for f in sorted(os.listdir(folder)) if f.lower().endswith((".jpg", ".jpeg"))]
 
 
-def run_images(demo: "Demo", folder: str, out_dir: str, quality: int = 95, subsampling: str = "4:2:0") -> List[dict]:
+def run_images(demo: "Demo", folder: str, out_dir: str, quality: int = 95, subsampling: str = "4:2:0", entropy: str = "host") -> List[dict]:
     """--images: folder of JPEGs -> annotated JPEGs of the same names in out_dir, plus results.json"""
     import json
     from . import jpeg
     os.makedirs(out_dir, exist_ok=True)
     summary = []
     for t, path in enumerate(list_images(folder)):
-        r = demo.process_device(jpeg.imread_bgr_device(path, device=demo.device), quality, subsampling)
+        r = demo.process_device(jpeg.imread_bgr_device(path, device=demo.device), quality, subsampling, entropy)
         with open(os.path.join(out_dir, os.path.basename(path)), "wb") as f:
             f.write(r["jpeg"])
         nd = sum(len(d["rois"]) for d in r.get("detections", []) or [])
@@ -174,6 +175,7 @@ def main(argv=None):
     ap.add_argument("--frames", default=None, help=".npy uint8 [T, H, W, 3] BGR frames; synthetic 1080p frames without")
     ap.add_argument("--images", default=None, help="folder of *.jpg / *.jpeg frames: each is annotated and written as a JPEG of the same name into --out")
     ap.add_argument("--quality", type=int, default=95, help="JPEG quality of the annotated frames (--images)")
+    ap.add_argument("--entropy", choices=("host", "device"), default="host", help="where the Huffman stage of the JPEG encode runs (--images)")
     ap.add_argument("--count", type=int, default=4)
     ap.add_argument("--out", default=None, help="directory for the annotated JPEGs (--images) or frame_%%04d.npy (blended frames), and results.json")
     args = ap.parse_args(argv)
@@ -187,7 +189,7 @@ def main(argv=None):
     if args.images:
         if not args.out:
             ap.error("--images needs --out")
-        return run_images(demo, args.images, args.out, args.quality)
+        return run_images(demo, args.images, args.out, args.quality, entropy=args.entropy)
     frames = np.load(args.frames) if args.frames else synthetic_frames(args.count)
     if args.out:
         os.makedirs(args.out, exist_ok=True)

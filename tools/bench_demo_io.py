@@ -9,11 +9,16 @@ noise, as tools/bench_jpeg.py).  Per set, at quality 95 / 4:2:0:
                   windows, beside the HBM floor of the bytes it must move at 8 TB/s (frame in at 3 B/px, coefficients out at 2 B/sample)
   draw launch     hn_draw over the batch with a realistic list per frame (4 lanes of 40 points with their score text, 20 labelled boxes),
                   same windows; its floor is not stated: it reads no frame and writes only the painted pixels
+  huffman stage   hn_jpeg_huff_encode (six launches) over the batch's coefficients, same windows, beside the HBM floor of reading the
+                  coefficients once and writing the streams once; the pinned D2H copy of result records + scans at the capacity the scans
+                  need (and at jpeg_encode's first-guess capacity) against the pageable copy of the coefficients; encode_batch end to end
+                  per frame on frames already on the device, entropy="device" against entropy="host", alternated
   host, one core  hn_jpeg_entropy_encode per frame against PIL's Image.save of the same frame at the same settings (the only encoder a user
                   has without this path), and the D2H copy of the coefficients
   demo            frames per second over --frames files of the set, after 2 warm-up frames: Demo.process_device on
-                  jpeg.imread_bgr_device (decode -> ... -> JPEG bytes, the frame never on the host) against the path of the parent
-                  commit: PIL decode -> Demo.process -> PIL save of the blended frame (which draws nothing)
+                  jpeg.imread_bgr_device (decode -> ... -> JPEG bytes, the frame never on the host) with the Huffman stage on the host
+                  ("device") and on the device ("device_huff") against PIL decode -> Demo.process -> PIL save of the blended frame
+                  (which draws nothing)
 One JSON line per set.
 """
 import argparse
@@ -91,6 +96,7 @@ def device_times(frames, iters, dev):
     bgr_bytes, coef_bytes = int(sum(f.size for f in frames)), int(sum(h["coef_bytes"] for h in heads))
     floor = (bgr_bytes + coef_bytes) / HBM_BPS * 1e3
     d2h = window(lambda: coefs.cpu(), max(2, iters // 4))
+    huff = huffman_times(pk, heads, coefs, coff, iters, dev)
     lists = [realistic_primitives(*f.shape[:2]) for f in frames]
     scratch = {"data": pk["data"].clone(), "offsets": pk["offsets"], "shapes": pk["shapes"]}
     t = time.perf_counter()
@@ -109,7 +115,44 @@ def device_times(frames, iters, dev):
     drw = window(lambda: lib().call("hn_draw", *dargs), iters)
     return {"frames": n, "bgr_MB": round(bgr_bytes / 1e6, 2), "coef_MB": round(coef_bytes / 1e6, 2), "encode_kernel_ms": spread(enc),
             "hbm_floor_ms": round(floor, 4), "achieved_over_floor": round(spread(enc)["median"] / floor, 2), "coef_d2h_ms": spread(d2h),
-            "primitives_per_frame": len(lists[0]), "draw_launch_ms": spread(drw), "draw_call_with_host_side_ms": round(first, 3)}
+            "primitives_per_frame": len(lists[0]), "draw_launch_ms": spread(drw), "draw_call_with_host_side_ms": round(first, 3), "huffman": huff}
+
+
+def huffman_times(pk, heads, coefs, coff, iters, dev):
+    n = len(heads)
+    blobs = jpeg_encode.entropy_encode_device(heads, coefs, coff)      # (the coefficients are in place: device_times ran the encode kernel)
+    hdr = [len(jpeg_encode.write_header(h)) for h in heads]
+    scans = [len(b) - x - 2 for b, x in zip(blobs, hdr)]
+    out = {}
+    for label, caps in (("exact", scans), ("first_guess", [jpeg_encode.first_capacity(h) for h in heads])):
+        desc, ooff = jpeg_encode.huff_describe(heads, coff, caps)
+        max_blocks, max_cap = max(h["coef_bytes"] // 128 for h in heads), max(caps)
+        ws = torch.empty((jpeg_encode.huff_workspace_bytes(n, max_blocks, max_cap),), device=dev, dtype=torch.uint8)
+        desc_d = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
+        buf = torch.empty((16 * n + int(ooff[-1]),), device=dev, dtype=torch.uint8)
+        args = (coefs.data_ptr(), int(coefs.numel()) * 2, desc_d.data_ptr(), n, max_blocks, max_cap, ws.data_ptr(), int(ws.numel()),
+                buf.data_ptr() + 16 * n, int(ooff[-1]), buf.data_ptr())
+        ms = window(lambda: lib().call("hn_jpeg_huff_encode", *args), iters)
+        stage = torch.empty((int(buf.numel()),), dtype=torch.uint8, pin_memory=True)
+        copy = window(lambda: stage.copy_(buf, non_blocking=True), max(2, iters // 4))
+        status = stage[:16 * n].numpy().view(jpeg_encode.HUFF_RESULT_DTYPE)["status"]
+        out[label] = {"capacity_MB": round(int(ooff[-1]) / 1e6, 2), "launches_ms": spread(ms), "workspace_MB": round(int(ws.numel()) / 1e6, 1),
+                      "pinned_d2h_ms": spread(copy), "images_too_small": int((status == jpeg_encode.CAPACITY_TOO_SMALL).sum())}
+    coef_bytes = int(sum(h["coef_bytes"] for h in heads))
+    floor = (coef_bytes + sum(scans)) / HBM_BPS * 1e3
+    out["stream_MB"] = round(sum(scans) / 1e6, 3)
+    out["hbm_floor_ms"] = round(floor, 4)
+    out["achieved_over_floor"] = round(out["exact"]["launches_ms"]["median"] / floor, 1)
+    e2e = {"host": [], "device": []}
+    for _ in range(3):                                                   # alternated; the first round is the warm-up
+        for mode in ("host", "device"):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            got = jpeg_encode.encode_batch(pk, QUALITY, SUBSAMPLING, entropy=mode)
+            e2e[mode].append((time.perf_counter() - t) * 1e3 / n)
+            assert got == blobs
+    out["encode_batch_ms_per_frame"] = {m: spread(v[1:]) for m, v in e2e.items()}
+    return out
 
 
 def pil_save(bgr):
@@ -144,15 +187,16 @@ def demo_rates(frames, cfg, count, dev):
     files = [pil_save(f) for f in frames[:4]]
     warm = 2
     res = {}
-    for mode in ("device", "pil", "device", "pil"):                      # alternated: two windows per mode
+    for mode in ("device", "device_huff", "pil") * 2:                    # alternated: two windows per mode
         t0 = None
         for i in range(warm + count):
             if i == warm:
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
             data = files[i % len(files)]
-            if mode == "device":
-                out = demo.process_device(jpeg.imread_bgr_device(data, device=dev), QUALITY, SUBSAMPLING)["jpeg"]
+            if mode != "pil":
+                out = demo.process_device(jpeg.imread_bgr_device(data, device=dev), QUALITY, SUBSAMPLING,
+                                          entropy="device" if mode == "device_huff" else "host")["jpeg"]
             else:
                 out = pil_save(demo.process(jpeg.pil_bgr(data))["visual"])
             assert len(out) > 1000
