@@ -658,6 +658,21 @@ int hn_jpeg_entropy_decode(const void* data, long len, const void* head, void* c
  * access: an image whose descriptor does not fit them is left unwritten.  Two launches, no allocation, no synchronisation. */
 int hn_jpeg_decode(const void* coefs, long coef_bytes, const void* desc, int N, long max_blocks, int max_h, int max_w, void* planes,
                    long plane_bytes, void* dst, long dst_bytes, hipStream_t stream);
+/* The entropy stage on the device instead (jpeg.entropy_decode_device; hn_jpeg_scan.hip, semantics in DESIGN.md 4g).
+ * hn_jpeg_scan_prepare is a HOST function (no HIP runtime call, no allocation), statuses as hn_jpeg_parse, 1 also for a head that is not
+ * this stream's: it fills an 8576-byte JpegScanRec (layout in hn_jpeg_scan.h and jpeg.py SCAN_DTYPE) with the scan's offset and length,
+ * the geometry and the Huffman tables its components select; the caller adds stream_off / coef_off (multiples of 16) when it packs a batch.
+ * hn_jpeg_scan_decode: streams = the batch's files at their stream_off (stream_bytes a multiple of 4), desc = DEVICE array of N records
+ * -> coefs, exactly what hn_jpeg_entropy_decode writes for each image at its coef_off, and status: N int32, 0 or 1 (a corrupt or truncated
+ * scan, or a record that does not fit the buffers; that image's coefficients are then undefined, but inside its slot).  coefs
+ * [0, coef_bytes) is zeroed first.  Self-synchronising parallel Huffman decoding over subsequences of hn_jpeg_scan_subseq_bytes() raw bytes;
+ * max_scan_bytes / max_blocks: the batch's largest scan length and block count (grid extents and the workspace, hn_jpeg_scan_ws_bytes, -1
+ * for arguments out of range; ws 16-byte aligned).  Two memsets and three launches, no allocation, no synchronisation. */
+int hn_jpeg_scan_prepare(const void* data, long len, const void* head, void* rec);
+long hn_jpeg_scan_ws_bytes(int N, long max_scan_bytes, long max_blocks);
+int hn_jpeg_scan_subseq_bytes(void);
+int hn_jpeg_scan_decode(const void* streams, long stream_bytes, const void* desc, int N, long max_scan_bytes, long max_blocks, void* ws,
+                        long ws_bytes, void* coefs, long coef_bytes, void* status, hipStream_t stream);
 
 /* Baseline JPEG encode, the mirror image (jpeg_encode.py; hn_jpeg_enc.hip, semantics in DESIGN.md 4h): libjpeg's default compressor, all
  * integer.  Device stage for a ragged batch: desc = DEVICE array of N 432-byte JpegEncDesc (offsets into frames / coefs, geometry,

@@ -5,6 +5,8 @@
 //   hn_jpeg_entropy_decode  the Huffman stage of the one interleaved scan -> quantised int16 coefficients, de-zigzagged, one 64-entry block
 //                           per 8x8 block, component plane after component plane, blocks in raster order of the plane padded to whole MCUs.
 //                           Every stream read is checked against the given length and every block against the buffer size.
+//   hn_jpeg_scan_prepare    instead of that stage, for the scan decode on the device (hn_jpeg_scan.hip): where the scan lies and the Huffman
+//                           tables it selects -> JpegScanRec
 // Device (two launches over a ragged batch, one JpegDesc per image):
 //   jpeg_idct_kernel   one thread per 8x8 block: dequantise + libjpeg's accurate integer IDCT (jidctint "ISLOW": 13-bit constants, 2 pass-1
 //                      bits), +128, clamp -> uint8 sample planes (width = blocks * 8) in the caller's scratch.
@@ -13,6 +15,7 @@
 //                      H x W x 3 at the image's offset of the packed frame buffer (augment.pack's layout).
 // All arithmetic is integer and exact; dequantised coefficients are assumed to fit 16 bits (any 8-bit JPEG), so 32-bit sums cannot overflow.
 #include "hn_common.h"
+#include "hn_jpeg_scan.h"
 #include <string.h>
 
 // ---- records shared with jpeg.py ---------------------------------------------------------------------------------------------------
@@ -347,6 +350,54 @@ extern "C" int hn_jpeg_entropy_decode(const void* data, long len, const void* he
                     }
             ++since;
         }
+    return HN_OK;
+}
+
+// The scan of a supported stream, for hn_jpeg_scan_decode: its extent and the decode tables of its components.  The same statuses as
+// hn_jpeg_parse; a `head` that is not this stream's is refused.
+extern "C" int hn_jpeg_scan_prepare(const void* data, long len, const void* head, void* rec) {
+    HN_CHECK_ARG(data && head && rec && len > 0);
+    JpegState s;
+    const unsigned char* p = (const unsigned char*)data;
+    const int rc = parse_stream(p, len, s);
+    if (rc != HN_OK) return rc;
+    HN_CHECK_ARG(memcmp(head, &s.h, sizeof(JpegHead)) == 0);                                     // the header of this very stream
+    JpegScanRec& r = *(JpegScanRec*)rec;
+    memset(&r, 0, sizeof(r));
+    r.scan_offset = s.h.scan_offset;
+    // the scan ends with the first marker that is neither a stuffed 0xFF nor RSTn (EOI in a whole file), or with the data
+    long pos = s.h.scan_offset, end = len;
+    while (pos < len) {
+        const unsigned char* f = (const unsigned char*)memchr(p + pos, 0xFF, (size_t)(len - pos));
+        if (!f || f + 1 >= p + len) break;
+        pos = f - p;
+        const int m = p[pos + 1];
+        if (m == 0 || (m >= 0xD0 && m <= 0xD7)) { pos += 2; continue; }
+        if (m == 0xFF) { pos += 1; continue; }                                                   // a fill byte
+        end = pos + 2;
+        break;
+    }
+    r.scan_bytes = end - s.h.scan_offset;
+    r.ncomp = s.h.ncomp, r.hs = s.h.hs, r.vs = s.h.vs, r.mcus_x = s.h.mcus_x, r.mcus_y = s.h.mcus_y, r.restart_interval = s.h.restart_interval;
+    for (int kind = 0; kind < 2; ++kind) {
+        int used[3], n = 0;
+        for (int c = 0; c < s.h.ncomp; ++c) {
+            const int id = kind ? s.ta[c] : s.td[c];
+            int k = 0;
+            while (k < n && used[k] != id) ++k;
+            if (k == n) {
+                used[n++] = id;
+                const HuffTab& t = kind ? s.ac[id] : s.dc[id];
+                JpegScanHuff& d = kind ? r.ac[k] : r.dc[k];
+                memcpy(d.look_n, t.look_n, sizeof(d.look_n));
+                memcpy(d.look_v, t.look_v, sizeof(d.look_v));
+                memcpy(d.maxcode, t.maxcode, sizeof(d.maxcode));
+                memcpy(d.valoff, t.valoff, sizeof(d.valoff));
+                memcpy(d.vals, t.vals, sizeof(d.vals));
+            }
+            (kind ? r.ta : r.td)[c] = k;
+        }
+    }
     return HN_OK;
 }
 

@@ -4,7 +4,8 @@ image's augmentation plan (augment.sample_plan; with dataloader.do_split from th
 at construction, e.g. augment.cal_split) and packs the batch's host buffers.  The batch carries `src_frames` / `src_segs` (packed uint8),
 the parsed labels and `aug_plans` instead of `image`; HydraTrainer.to_gpu runs augment.augment_batch on it, which returns the Collater
 contract.  Workers never touch the GPU.  With decode="device" a worker stops after the JPEG's entropy stage (jpeg.py: host functions of the
-library) and the batch carries `src_coefs`, which to_gpu decodes on the device into the same packed frames.
+library) and the batch carries `src_coefs`, which to_gpu decodes on the device into the same packed frames.  With decode="device-entropy" a
+worker only reads the file and parses its header: the batch carries the files' bytes (`src_streams`) and the device decodes the scans too.
 
     ds = MultitaskData(cfgs, "train")                 # with dataloader.do_split: MultitaskData(cfgs, "train", split_rule=augment.cal_split)
     loader = DataLoader(ds, batch_size=16, shuffle=True, num_workers=8, collate_fn=ds.collate_fn, pin_memory=True)
@@ -94,9 +95,11 @@ class MultitaskData:
         augmentation and do_split needs one, and lane labels to apply it to.
         decode: "host" -- the worker decodes the JPEG with PIL (`src_frame`); "device" -- the worker runs only the entropy stage
         (jpeg.parse + jpeg.entropy_decode: `src_coefs` + `jpeg_head`) and HydraTrainer.to_gpu finishes the decode on the device
-        (jpeg.decode_batch); a file outside jpeg.py's supported set is decoded with PIL as before, that image only."""
-        if decode not in ("host", "device"):
-            raise ValueError("decode should be one of ('host', 'device')")
+        (jpeg.decode_batch); "device-entropy" -- the worker only reads the file, parses its header and prepares its scan (jpeg.parse +
+        jpeg.scan_prepare: `src_stream`, the file's bytes, + `jpeg_head` + `jpeg_scan`) and the device runs the Huffman stage too; a file
+        outside jpeg.py's supported set is decoded with PIL as before, that image only."""
+        if decode not in ("host", "device", "device-entropy"):
+            raise ValueError("decode should be one of ('host', 'device', 'device-entropy')")
         self.decode = decode
         dl = cfgs["dataloader"]
         self.cfgs, self.mode, self.base_seed, self.epoch = cfgs, mode, int(base_seed), 0
@@ -128,8 +131,19 @@ class MultitaskData:
 
     def __getitem__(self, idx):
         pair = self.image_annot_path_pairs[idx]
-        head = None
-        if self.decode == "device":
+        head = scan = None
+        if self.decode == "device-entropy":
+            from . import jpeg
+            if not os.path.exists(pair["image_path"]):
+                raise FileNotFoundError(pair["image_path"])
+            staged = jpeg.stream_stage(jpeg.read_bytes(pair["image_path"]))      # (header, scan record, bytes) or (None, PIL's frame)
+            head = staged[0]
+            if head is not None:
+                scan, img = staged[1], np.frombuffer(staged[2], dtype=np.uint8)
+            else:
+                img = staged[1]
+            h, w = (head["height"], head["width"]) if head is not None else img.shape[:2]
+        elif self.decode == "device":
             from . import jpeg
             if not os.path.exists(pair["image_path"]):
                 raise FileNotFoundError(pair["image_path"])
@@ -141,7 +155,10 @@ class MultitaskData:
         if h < self.network_input_height or w < self.network_input_width:
             raise ValueError("%s: %dx%d is smaller than the network input %dx%d (INTER_AREA does not upscale)"
                              % (pair["image_path"], w, h, self.network_input_width, self.network_input_height))
-        if head is not None:
+        if scan is not None:
+            item = dict(src_stream=img, jpeg_head=head, jpeg_scan=scan, src_image_shape=dict(width=w, height=h, channel=3),
+                        src_image_path=pair["image_path"])
+        elif head is not None:
             item = dict(src_coefs=img, jpeg_head=head, src_image_shape=dict(width=w, height=h, channel=3), src_image_path=pair["image_path"])
         else:
             item = dict(src_frame=img, src_image_shape=dict(width=w, height=h, channel=3), src_image_path=pair["image_path"])
@@ -171,8 +188,12 @@ class MultitaskData:
 def collate(batch, net_h, net_w):
     """host half of the Collater: the frames (and label maps) packed into one uint8 buffer each; labels and plans as lists.  A batch with
     entropy-decoded items (decode="device") carries `src_coefs` instead of `src_frames`: jpeg.pack_coefs' buffers, the PIL-decoded frames of
-    its unsupported files among them."""
-    if any("src_coefs" in b for b in batch):
+    its unsupported files among them; one with items of decode="device-entropy" carries `src_streams`, jpeg.pack_streams' buffers, likewise."""
+    if any("src_stream" in b for b in batch):
+        from .jpeg import pack_streams
+        src = dict(src_streams=pack_streams([(b["jpeg_head"], b["jpeg_scan"], b["src_stream"]) if "src_stream" in b else (None, b["src_frame"])
+                                             for b in batch]))
+    elif any("src_coefs" in b for b in batch):
         from .jpeg import pack_coefs
         src = dict(src_coefs=pack_coefs([(b["jpeg_head"], b["src_coefs"]) if "src_coefs" in b else (None, b["src_frame"]) for b in batch]))
     else:

@@ -131,14 +131,16 @@ def list_images(folder: str) -> List[str]:
     return [os.path.join(folder, f) for f in sorted(os.listdir(folder)) if f.lower().endswith((".jpg", ".jpeg"))]
 
 
-def run_images(demo: "Demo", folder: str, out_dir: str, quality: int = 95, subsampling: str = "4:2:0", entropy: str = "host") -> List[dict]:
-    """--images: folder of JPEGs -> annotated JPEGs of the same names in out_dir, plus results.json"""
+def run_images(demo: "Demo", folder: str, out_dir: str, quality: int = 95, subsampling: str = "4:2:0", entropy: str = "host",
+               decode_entropy: str = "host") -> List[dict]:
+    """--images: folder of JPEGs -> annotated JPEGs of the same names in out_dir, plus results.json.  entropy / decode_entropy: where the
+    Huffman stage of the encode / of the decode runs; the bytes written are the same."""
     import json
     from . import jpeg
     os.makedirs(out_dir, exist_ok=True)
     summary = []
     for t, path in enumerate(list_images(folder)):
-        r = demo.process_device(jpeg.imread_bgr_device(path, device=demo.device), quality, subsampling, entropy)
+        r = demo.process_device(jpeg.imread_bgr_device(path, device=demo.device, entropy=decode_entropy), quality, subsampling, entropy)
         with open(os.path.join(out_dir, os.path.basename(path)), "wb") as f:
             f.write(r["jpeg"])
         nd = sum(len(d["rois"]) for d in r.get("detections", []) or [])
@@ -176,6 +178,7 @@ def main(argv=None):
     ap.add_argument("--images", default=None, help="folder of *.jpg / *.jpeg frames: each is annotated and written as a JPEG of the same name into --out")
     ap.add_argument("--quality", type=int, default=95, help="JPEG quality of the annotated frames (--images)")
     ap.add_argument("--entropy", choices=("host", "device"), default="host", help="where the Huffman stage of the JPEG encode runs (--images)")
+    ap.add_argument("--decode-entropy", choices=("host", "device"), default="host", help="where the Huffman stage of the JPEG decode runs (--images)")
     ap.add_argument("--count", type=int, default=4)
     ap.add_argument("--out", default=None, help="directory for the annotated JPEGs (--images) or frame_%%04d.npy (blended frames), and results.json")
     args = ap.parse_args(argv)
@@ -189,7 +192,7 @@ def main(argv=None):
     if args.images:
         if not args.out:
             ap.error("--images needs --out")
-        return run_images(demo, args.images, args.out, args.quality, entropy=args.entropy)
+        return run_images(demo, args.images, args.out, args.quality, entropy=args.entropy, decode_entropy=args.decode_entropy)
     frames = np.load(args.frames) if args.frames else synthetic_frames(args.count)
     if args.out:
         os.makedirs(args.out, exist_ok=True)

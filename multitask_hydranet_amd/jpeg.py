@@ -8,6 +8,12 @@ PIL's bit for bit.
     coefs = jpeg.entropy_decode(data, head)      # host only: int16 [blocks, 64]
     frames = jpeg.decode_batch([(head, coefs), ...])        # {"data" (device uint8), "offsets", "shapes"}: pack()'s layout
 
+The Huffman stage runs on the device as well (hn_jpeg_scan.hip), opt-in: the file's bytes are uploaded as they are and the host only parses
+the header and prepares the scan's tables.  An image whose scan the device reports corrupt is decoded with PIL, that image only.
+
+    scan = jpeg.scan_prepare(data, head)         # host only: where the scan lies + its Huffman tables
+    frames = jpeg.decode_batch(jpeg.pack_streams([(head, scan, data), ...]))
+
 Supported: 8-bit Huffman SOF0 / SOF1, one interleaved scan, greyscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0 (luma 1x1 / 2x1 / 2x2, chroma 1x1),
 DHT / DQT anywhere before the scan, 8- and 16-bit DQT entries, restart intervals, APPn / COM skipped.  Coefficient layout: one de-zigzagged
 64-entry block per 8x8 block, component plane after component plane (Y, Cb, Cr), blocks in raster order of the plane padded to whole MCUs.
@@ -33,6 +39,20 @@ DESC_DTYPE = np.dtype({
     "formats": ["<i8", "<i8", "<i8", "<i4", "<i4", "<i4", "<i4", "<i4", "<i4", "<i4", ("<u2", (3, 64))],
     "offsets": [0, 8, 16, 24, 28, 32, 36, 40, 44, 48, 56],
     "itemsize": 440})
+
+# hn_jpeg_scan.h struct JpegScanHuff / JpegScanRec
+SCAN_HUFF_DTYPE = np.dtype({
+    "names": ["look_n", "look_v", "maxcode", "valoff", "vals"],
+    "formats": [("u1", 512), ("u1", 512), ("<i4", 17), ("<i4", 17), ("u1", 256)],
+    "offsets": [0, 512, 1024, 1092, 1160],
+    "itemsize": 1416})
+SCAN_DTYPE = np.dtype({
+    "names": ["scan_offset", "scan_bytes", "stream_off", "coef_off", "ncomp", "hs", "vs", "mcus_x", "mcus_y", "restart_interval", "td", "ta",
+              "dc", "ac"],
+    "formats": ["<i8", "<i8", "<i8", "<i8", "<i4", "<i4", "<i4", "<i4", "<i4", "<i4", ("<i4", 3), ("<i4", 3), (SCAN_HUFF_DTYPE, 3),
+                (SCAN_HUFF_DTYPE, 3)],
+    "offsets": [0, 8, 16, 24, 32, 36, 40, 44, 48, 52, 56, 68, 80, 80 + 3 * 1416],
+    "itemsize": 8576})
 
 UNSUPPORTED = 3
 
@@ -80,6 +100,73 @@ def entropy_decode(data, head: dict, out: Optional[np.ndarray] = None) -> np.nda
     if entropy_status(data, head, out) != 0:
         raise JpegError("corrupt or truncated entropy-coded segment")
     return out
+
+
+def scan_prepare(data, head: dict) -> np.ndarray:
+    """the scan of a parsed stream for the device's entropy stage: one SCAN_DTYPE record (scan_offset, scan_bytes, geometry, the Huffman
+    tables its components select; stream_off / coef_off are pack_streams' to fill).  Host only."""
+    data = _as_bytes(data)
+    rec = np.zeros(1, dtype=SCAN_DTYPE)
+    rc = lib().raw("hn_jpeg_scan_prepare")(data, len(data), head["rec"].ctypes.data, rec.ctypes.data)
+    if rc != 0:
+        raise JpegError("the header does not belong to this stream" if rc == 1 else "outside the supported set")
+    return rec
+
+
+def pack_streams(items: Sequence, pin: bool = False) -> dict:
+    """[(head, scan record, the file's bytes (bytes or a uint8 array)) | (None, BGR uint8 H x W x 3 frame decoded elsewhere)] -> the batch's
+    host buffers, as pack_coefs: "heads", one uint8 tensor "data" with every stream at "offsets" (bytes, multiples of 16; -1 for a frame),
+    "lengths" (of the streams), "scans" (the records of the streams, stream_off / coef_off filled in), "coef_bytes" (of the coefficient buffer
+    they index) and "frames"."""
+    import torch
+    offs, total, ctotal, scans = [], 0, 0, []
+    for it in items:
+        if it[0] is None:
+            offs.append(-1)
+            continue
+        head, scan, data = it
+        n = len(data)
+        assert int(scan["scan_offset"][0]) + int(scan["scan_bytes"][0]) <= n and int(scan["scan_offset"][0]) == head["scan_offset"]
+        rec = scan.copy()
+        rec["stream_off"], rec["coef_off"] = total, ctotal
+        scans.append(rec)
+        offs.append(total)
+        total += (n + 15) // 16 * 16
+        ctotal += (int(head["coef_bytes"]) + 15) // 16 * 16
+    buf = torch.zeros((max(16, total),), dtype=torch.uint8, pin_memory=pin)
+    view = buf.numpy()
+    for it, o in zip(items, offs):
+        if it[0] is not None:
+            view[o:o + len(it[2])] = np.frombuffer(it[2], dtype=np.uint8) if isinstance(it[2], (bytes, bytearray, memoryview)) else it[2]
+    return {"heads": [it[0] for it in items], "data": buf, "offsets": np.array(offs, dtype=np.int64),
+            "lengths": np.array([len(it[2]) if it[0] is not None else 0 for it in items], dtype=np.int64), "scans": np.concatenate(scans) if scans else np.zeros(0, dtype=SCAN_DTYPE), "coef_bytes": ctotal,
+            "frames": [None if it[0] is not None else np.ascontiguousarray(it[1]) for it in items]}
+
+
+def entropy_decode_device(pk: dict, device=None) -> dict:
+    """pack_streams' dict -> the Huffman stage on the device (hn_jpeg_scan_decode): {"data": int16 device tensor, every image's coefficients in
+    entropy_decode's layout at "offsets" (bytes; -1 for a frame), "heads", "status": int32 device tensor, one word per STREAM (in batch order,
+    frames left out): 0, or 1 for a scan that does not decode, whose coefficients mean nothing}.  No synchronisation."""
+    import torch
+    assert pk["data"].dtype == torch.uint8 and "scans" in pk
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    scans, heads = pk["scans"], pk["heads"]
+    n = len(scans)
+    coef_offs = np.full(len(heads), -1, dtype=np.int64)
+    coef_offs[[i for i, h in enumerate(heads) if h is not None]] = scans["coef_off"]
+    with torch.cuda.device(dev):
+        coefs = torch.empty((max(8, int(pk["coef_bytes"]) // 2),), device=dev, dtype=torch.int16)
+        status = torch.zeros((max(1, n),), device=dev, dtype=torch.int32)
+        if n:
+            streams = pk["data"].to(dev, non_blocking=pk["data"].is_pinned())
+            desc_d = torch.from_numpy(scans.view(np.uint8).copy()).to(dev)
+            max_scan, max_blocks = int(scans["scan_bytes"].max()), max(n_blocks(h) for h in heads if h is not None)
+            ws_bytes = int(lib().query("hn_jpeg_scan_ws_bytes", n, max_scan, max_blocks))
+            assert ws_bytes > 0, (n, max_scan, max_blocks)
+            ws = torch.empty((ws_bytes,), device=dev, dtype=torch.uint8)
+            lib().call("hn_jpeg_scan_decode", streams.data_ptr(), int(streams.numel()), desc_d.data_ptr(), n, max_scan, max_blocks, ws.data_ptr(),
+                       ws_bytes, coefs.data_ptr(), int(coefs.numel()) * 2, status.data_ptr())
+    return {"data": coefs, "offsets": coef_offs, "heads": heads, "status": status}
 
 
 def pack_coefs(items: Sequence, pin: bool = False) -> dict:
@@ -133,6 +220,11 @@ def decode_batch(items, device=None, out=None) -> dict:
     import torch
     pk = items if isinstance(items, dict) else pack_coefs(items)
     heads, frames = pk["heads"], pk["frames"]
+    status = None
+    if "scans" in pk:                                    # pack_streams' dict: the Huffman stage on the device first
+        ent = entropy_decode_device(pk, device=device)
+        status = ent["status"]
+        pk = {"heads": heads, "frames": frames, "data": ent["data"], "offsets": ent["offsets"], "streams": pk}
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     desc, idx, offs, shapes, plane_total = describe_batch(pk)
     if out is None:
@@ -146,12 +238,21 @@ def decode_batch(items, device=None, out=None) -> dict:
             dst[int(offs[i]):int(offs[i + 1])].copy_(torch.from_numpy(f).reshape(-1))
     if idx:
         assert pk["data"].dtype == torch.int16
-        coefs = pk["data"].to(dev, non_blocking=pk["data"].is_pinned())
+        coefs = pk["data"] if pk["data"].is_cuda else pk["data"].to(dev, non_blocking=pk["data"].is_pinned())
         desc_d = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
         with torch.cuda.device(dev):
             planes = torch.empty((plane_total,), device=dev, dtype=torch.uint8)
             lib().call("hn_jpeg_decode", coefs.data_ptr(), int(coefs.numel()) * 2, desc_d.data_ptr(), len(idx), max(n_blocks(heads[i]) for i in idx),
                        int(shapes[idx, 0].max()), int(shapes[idx, 1].max()), planes.data_ptr(), plane_total, dst.data_ptr(), int(dst.numel()))
+        if status is not None:
+            # the one read-back: an image whose scan the device could not decode is PIL's to decode, into its slot of the packed frames
+            src = pk["streams"]
+            for k in np.nonzero(status[:len(idx)].cpu().numpy())[0]:
+                i = idx[int(k)]
+                o, ln = int(src["offsets"][i]), int(src["lengths"][i])
+                f = pil_bgr(src["data"].numpy()[o:o + ln].tobytes())
+                assert f.shape == (int(shapes[i, 0]), int(shapes[i, 1]), 3), (f.shape, shapes[i])
+                dst[int(offs[i]):int(offs[i + 1])].copy_(torch.from_numpy(f).reshape(-1))
     return {"data": dst, "offsets": offs[:-1].copy(), "shapes": shapes}
 
 
@@ -185,11 +286,29 @@ def host_stage(data: bytes):
     return None, pil_bgr(data)
 
 
-def imread_bgr_device(paths_or_bytes, device=None) -> dict:
-    """files (paths) or encoded bytes, one or a list -> their BGR frames on the device, packed ({"data", "offsets", "shapes"})"""
+def stream_stage(data: bytes):
+    """one image's host share when the device runs the entropy stage: (head, scan record, bytes), or (None, PIL's BGR frame) when the
+    stream is outside the supported set"""
+    try:
+        head = parse(data)
+    except JpegError:
+        head = None
+    if head is None:
+        return None, pil_bgr(data)
+    return head, scan_prepare(data, head), data
+
+
+def imread_bgr_device(paths_or_bytes, device=None, entropy: str = "host") -> dict:
+    """files (paths) or encoded bytes, one or a list -> their BGR frames on the device, packed ({"data", "offsets", "shapes"}).  entropy:
+    where the Huffman stage runs, "host" or "device"; the frames are the same."""
+    if entropy not in ("host", "device"):
+        raise ValueError("entropy should be one of ('host', 'device')")
     if isinstance(paths_or_bytes, (str, bytes, bytearray, memoryview)) or hasattr(paths_or_bytes, "__fspath__"):
         paths_or_bytes = [paths_or_bytes]
+    if entropy == "device":
+        return decode_batch(pack_streams([stream_stage(read_bytes(s)) for s in paths_or_bytes]), device=device)
     return decode_batch([host_stage(read_bytes(s)) for s in paths_or_bytes], device=device)
 
 
-__all__ = ["parse", "entropy_decode", "decode_batch", "imread_bgr_device", "pack_coefs", "host_stage", "JpegError"]
+__all__ = ["parse", "entropy_decode", "decode_batch", "imread_bgr_device", "pack_coefs", "host_stage", "JpegError", "scan_prepare", "pack_streams",
+           "entropy_decode_device", "stream_stage"]

@@ -191,8 +191,9 @@ class HydraTrainer:
         """train.py:228-239.  A raw batch (dataset.MultitaskData: `src_frames` + `aug_plans`, no `image`) is first assembled and augmented on
         the device (augment.augment_batch) into the Collater contract; lane targets are then encoded from its annot_lane as for any batch
         without gt_loc / gt_cls.  A batch of MultitaskData(decode="device") carries `src_coefs` (entropy-decoded JPEG coefficients) instead
-        of `src_frames`: jpeg.decode_batch finishes the decode on the device into the same packed frames first."""
-        if "image" not in batch_data and ("src_frames" in batch_data or "src_coefs" in batch_data):
+        of `src_frames`, one of decode="device-entropy" `src_streams` (the files' bytes): jpeg.decode_batch finishes the decode on the device
+        into the same packed frames first."""
+        if "image" not in batch_data and ("src_frames" in batch_data or "src_coefs" in batch_data or "src_streams" in batch_data):
             batch_data = self._augment(batch_data)
         batch_data["image"] = batch_data["image"].to(self.device).float()
         if self.train_lane:
@@ -209,15 +210,15 @@ class HydraTrainer:
     def _augment(self, batch_data: dict) -> dict:
         from .augment import augment_batch
         dl = self.cfgs["dataloader"]
-        if "src_coefs" in batch_data:
+        if "src_coefs" in batch_data or "src_streams" in batch_data:
             from .jpeg import decode_batch
-            frames = decode_batch(batch_data["src_coefs"], device=self.device)
+            frames = decode_batch(batch_data.get("src_coefs", batch_data.get("src_streams")), device=self.device)
         else:
             frames = batch_data["src_frames"]
         out = augment_batch(frames, batch_data.get("lane_raw") if self.train_lane else None,
                             batch_data.get("det_raw") if self.train_detect else None, batch_data.get("src_segs") if self.train_seg else None,
                             batch_data["aug_plans"], (dl["network_input_height"], dl["network_input_width"]), device=self.device)
-        rest = {k: v for k, v in batch_data.items() if k not in ("src_frames", "src_coefs", "src_segs", "lane_raw", "det_raw", "aug_plans")}
+        rest = {k: v for k, v in batch_data.items() if k not in ("src_frames", "src_coefs", "src_streams", "src_segs", "lane_raw", "det_raw", "aug_plans")}
         rest.update(out)
         return rest
 

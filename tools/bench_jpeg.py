@@ -1,15 +1,17 @@
 """JPEG decode split: what the host entropy stage costs against PIL's full decode, what the device stage costs against
-its HBM floor, and what a DataLoader -> HydraTrainer.to_gpu pipeline delivers with decode="host" and decode="device".
+its HBM floor, what the scan decode on the device costs, and what a DataLoader -> HydraTrainer.to_gpu pipeline delivers with decode="host",
+decode="device" and decode="device-entropy".
 
-    python tools/bench_jpeg.py [--files DIR] [--n 16] [--iters 20] [--workers 8] [--batches 96] [--out-hw 512x1024]
+    python tools/bench_jpeg.py [--files DIR] [--set NAME] [--scan-only] [--n 16] [--iters 20] [--workers 8] [--batches 96] [--out-hw 512x1024]
 
 Frame sets: the committed 2560x1440 sample frame (tests/golden/jpeg) and, as tools/bench_augment.py, synthetic 1920x1080 frames (smooth
 gradients + noise, quality 90, 4:2:0); --files DIR adds every *.jpg of a directory as a third set.  Per set, on ONE core (this process):
 PIL's full decode and the entropy stage (parse + Huffman) per frame, median and min..max over the set x 3 passes.  Then for --n frames of
 the set: the pinned H2D copy of the packed coefficients and the two device kernels by HIP events (mean of --iters after 3 warm-up runs,
-min..max of 5 such windows), beside the HBM floor of the bytes they must move at 8 TB/s.  Then the loader: DataLoader(num_workers=k,
+min..max of 5 such windows), beside the HBM floor of the bytes they must move at 8 TB/s; the same for the files' bytes and the scan decode
+(hn_jpeg_scan_decode: two memsets + three launches; --scan-only runs just that, for a kernel trace).  Then the loader: DataLoader(num_workers=k,
 pin_memory) over a data list of the set (its files listed over and over; lane + box labels; no label maps, so the decode is what
-differs) -> to_gpu, images per second over --batches batches after 4 warm-up batches, for both decode modes at the same k, two windows
+differs) -> to_gpu, images per second over --batches batches after 4 warm-up batches, for the three decode modes at the same k, two windows
 each, alternated.  The window is longer than the loader's prefetch depth (2 k batches), so it measures production, not a drained queue,
 and the data list ends with the window, so every loader runs to its natural end.
 """
@@ -68,7 +70,29 @@ def host_times(streams):
             "pil_frames_per_s_per_core": round(1e3 / spread(pil)["median"], 1), "entropy_frames_per_s_per_core": round(1e3 / spread(ent)["median"], 1)}
 
 
-def device_times(streams, n, iters, dev):
+def scan_times(streams, n, iters, dev, window):
+    """the upload of the files' bytes and hn_jpeg_scan_decode on --n frames; the coefficients are checked against the host's once"""
+    items = [jpeg.stream_stage(streams[i % len(streams)]) for i in range(n)]
+    pk = jpeg.pack_streams(items, pin=True)
+    ent = jpeg.entropy_decode_device(pk, device=dev)
+    assert int(ent["status"].abs().sum()) == 0
+    want = jpeg.entropy_decode(streams[0], items[0][0]).reshape(-1)
+    assert np.array_equal(ent["data"][:want.size].cpu().numpy(), want), "device coefficients differ from the host's"
+    h2d = window(lambda: pk["data"].to(dev, non_blocking=True))
+    scans = pk["scans"]
+    data, desc = pk["data"].to(dev), torch.from_numpy(scans.view(np.uint8).copy()).to(dev)
+    max_scan, max_blocks = int(scans["scan_bytes"].max()), max(jpeg.n_blocks(it[0]) for it in items)
+    wsb = int(lib().query("hn_jpeg_scan_ws_bytes", n, max_scan, max_blocks))
+    ws = torch.empty((wsb,), device=dev, dtype=torch.uint8)
+    coefs = torch.empty((pk["coef_bytes"] // 2,), device=dev, dtype=torch.int16)
+    status = torch.zeros((n,), device=dev, dtype=torch.int32)
+    ker = window(lambda: lib().call("hn_jpeg_scan_decode", data.data_ptr(), int(data.numel()), desc.data_ptr(), n, max_scan, max_blocks,
+                                    ws.data_ptr(), wsb, coefs.data_ptr(), int(coefs.numel()) * 2, status.data_ptr()))
+    return {"stream_MB": round(int(pk["data"].numel()) / 1e6, 2), "scan_MB": round(int(scans["scan_bytes"].sum()) / 1e6, 2),
+            "h2d_pinned_ms": spread(h2d), "scan_decode_ms": spread(ker)}
+
+
+def device_times(streams, n, iters, dev, scan_only=False):
     items = [jpeg.host_stage(streams[i % len(streams)]) for i in range(n)]
     assert all(h is not None for h, _ in items), "the set holds a JPEG outside the supported set"
     pk = jpeg.pack_coefs(items, pin=True)
@@ -88,6 +112,8 @@ def device_times(streams, n, iters, dev):
             torch.cuda.synchronize()
             ms.append(e0.elapsed_time(e1) / iters)
         return ms
+    if scan_only:
+        return {"frames": n, "scan": scan_times(streams, n, iters, dev, window)}
     h2d = window(lambda: pk["data"].to(dev, non_blocking=True))
     coefs = pk["data"].to(dev)
     desc_d = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
@@ -101,7 +127,8 @@ def device_times(streams, n, iters, dev):
     floor = moved / HBM_BPS * 1e3
     return {"frames": n, "coef_MB": round(coef_bytes / 1e6, 2), "bgr_MB": round(int(offs[-1]) / 1e6, 2), "planes_MB": round(plane_total / 1e6, 2),
             "h2d_pinned_ms": spread(h2d), "h2d_GBps": round(pk["data"].numel() * 2 / (spread(h2d)["median"] * 1e-3) / 1e9, 1),
-            "kernels_ms": spread(ker), "hbm_floor_ms": round(floor, 4), "achieved_over_floor": round(spread(ker)["median"] / floor, 2)}
+            "kernels_ms": spread(ker), "hbm_floor_ms": round(floor, 4), "achieved_over_floor": round(spread(ker)["median"] / floor, 2),
+            "scan": scan_times(streams, n, iters, dev, window)}
 
 
 WARM = 4
@@ -130,7 +157,7 @@ def loader_rates(streams, n_files, workers, batch, batches, out_hw, dev):
         cfgs["train"].update(train_seg=False)
         tr = HydraTrainer(cfgs, iters_per_epoch=10)
         res = {}
-        for mode in ("host", "device", "host", "device"):                   # alternated: two windows per mode
+        for mode in ("host", "device", "device-entropy") * 2:               # alternated: two windows per mode
             ds = MultitaskData(cfgs, "train", decode=mode)
             loader = torch.utils.data.DataLoader(ds, batch_size=batch, shuffle=False, num_workers=workers, collate_fn=ds.collate_fn, pin_memory=True,
                                                  drop_last=True)
@@ -159,6 +186,8 @@ def main():
     ap.add_argument("--batches", type=int, default=96)
     ap.add_argument("--out-hw", default="512x1024")
     ap.add_argument("--no-loader", action="store_true")
+    ap.add_argument("--set", default=None, help="measure only the frame set of this name")
+    ap.add_argument("--scan-only", action="store_true", help="only the scan decode's upload and kernels (for a kernel trace)")
     a = ap.parse_args()
     assert 0 < a.workers <= 16
     out_hw = tuple(int(v) for v in a.out_hw.split("x"))
@@ -169,6 +198,11 @@ def main():
     if a.files:
         sets["files"] = [open(p, "rb").read() for p in sorted(glob.glob(os.path.join(a.files, "*.jpg")))]
     for name, streams in sets.items():
+        if a.set and name != a.set:
+            continue
+        if a.scan_only:
+            print(json.dumps({"set": name, "device": device_times(streams, a.n, a.iters, dev, scan_only=True)}), flush=True)
+            continue
         res = {"set": name, "files": len(streams), "host": host_times(streams), "device": device_times(streams, a.n, a.iters, dev)}
         if not a.no_loader:
             res["loader"] = loader_rates(streams, a.n * (a.batches + WARM), a.workers, a.n, a.batches, out_hw, dev)
