@@ -1863,7 +1863,7 @@ extern "C" int hn_dwconv_bwd_levels(const void* dz, int ldz, const void* x, int 
     const long blocks = dwconv_bwd_strip_blocks(strips, C);
     const int spl = (int)((strips + blocks * lanes - 1) / (blocks * lanes));
     const size_t lds = (256 * 37 + 9 * (size_t)C) * sizeof(float);
-    if (lds > 64 * 1024) {                                             // > 64 KiB of dynamic LDS: opt-in once per device (C > 727)
+    if (lds > 64 * 1024) {                                             // > 64 KiB of dynamic LDS: opt-in once per device (C > 768)
         static std::atomic<unsigned long long> optin{0};
         if (!lds_optin(optin, {(const void*)dwconv_bwd_kernel})) return HN_ERR_LAUNCH;
     }
