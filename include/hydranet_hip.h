@@ -577,6 +577,19 @@ int hn_seg_overlay(const long* mask, int N, int H, int W, const void* lut, int n
 int hn_lane_raster(const int* pts, const int* seg_lane, const int* seg_first, int nseg, int lane_width, int H, int W, void* masks,
                    hipStream_t stream);
 int hn_lane_iou(const void* masks, int G, int P, long HW, void* inter, void* area, hipStream_t stream);
+/* The same counts for a ragged batch of images, from the lanes' float64 points, without a mask in HBM (hn_lane_metric.hip, DESIGN.md 4i):
+ * natural cubic spline per lane in float64 (calc_params, every operation rounded once), unit-step samples truncated toward zero, thick
+ * lines painted per 64 x 64 tile in LDS (the distance test of hn_lane_raster), integer atomics into the images' tables.
+ * pts: DEVICE fp64 [n_points][2] = x, y of every lane's points, lanes back to back.  tab: DEVICE int32, back to back: lane_off
+ * [n_lanes + 1] (CSR offsets of the lanes' points), img_lane [N + 1] (CSR offsets of the images' lanes, an image's ground truths first),
+ * img_g [N] (ground-truth lanes per image), img_h [N], img_w [N], cnt_off [N] (the image's tables in counts), work [n_work][4] = {image, g0,
+ * p0, first tile}: one block of up to 32 x 32 pairs of one image, ceil(H / 64) * ceil(W / 64) tiles each; n_tiles = their sum.  counts: uint64
+ * [n_counts], zeroed here: image b holds |g & p| [G][P], |g| [G], |p| [P] at cnt_off[b]; counts[n_counts - 1] is a status word (0, or
+ * non-zero when a segment is longer than 1e9 or the batch has more than sample_cap samples: the tables are then incomplete).  ws:
+ * hn_lane_metric_ws_bytes(n_lanes, n_points, sample_cap) bytes, 16-byte aligned (-1: sizes out of range).  Two memsets, four launches. */
+long hn_lane_metric_ws_bytes(int n_lanes, long n_points, long sample_cap);
+int hn_lane_metric_batch(const double* pts, const int* tab, int N, int n_lanes, long n_points, int n_work, long n_tiles, long sample_cap,
+                         int lane_width, void* ws, long ws_bytes, void* counts, long n_counts, hipStream_t stream);
 
 /* Streaming confusion counts for the segmentation mIoU (head_seg/seg_metrics.py:12-47): conf uint64 [(C+1)*(C+1)] += counts of
  * (pred, target) pairs, both clamped to C (the ignore bucket).  pred int64 [M]; target int64 or float32 [M]. */

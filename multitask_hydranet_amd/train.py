@@ -372,8 +372,10 @@ class HydraTrainer:
         Returns the per-class IoU tensor; everything else is left in self.last_valid."""
         from .coco_json import detections_to_coco, write_results
         from .lane_metric import LaneMetric
-        lane_metric = LaneMetric(method="f1_measure", iou_thresh=0.5, lane_width=30, thresh_list=[0.5])           # train.py:188
-        lane_pairs = []
+        # train.py:188.  batched: every batch's lanes are rasterised and counted on the device while the next batch's forward runs; one
+        # synchronisation, in summary()
+        lane_metric = LaneMetric(method="f1_measure", iou_thresh=0.5, lane_width=30, thresh_list=[0.5], batched=True, device=self.device)
+        lane_pairs = 0
         net = self.hydranet
         net.eval()
         if self.train_seg:
@@ -416,17 +418,20 @@ class HydraTrainer:
                 lanes = net.laneheader.decode_batch(outputs["lane"]["predict_cls"], outputs["lane"]["predict_loc"], lane_coder,
                                                     l.get("conf_thres", 0.5), l.get("nms_thres", 100), False)
                 gts = batch_data.get("gt_lane_json")
+                pairs = []
                 for i, (ln, sh) in enumerate(zip(lanes, shapes)):
                     pj = net.laneheader.scale_to_org(ln, net_w, net_h, sh["width"], sh["height"])
                     lane_result.append(dict(pr_result={**pj, **dict(Shape=sh)}))
                     if gts is not None:
-                        lane_pairs.append(dict(pr_result=lane_result[-1]["pr_result"], gt_result={**gts[i], **dict(Shape=sh)}))
+                        pairs.append(dict(pr_result=lane_result[-1]["pr_result"], gt_result={**gts[i], **dict(Shape=sh)}))
+                if pairs:
+                    lane_metric(output=pairs)                                                                      # train.py:397
+                    lane_pairs += len(pairs)
         net.train()
         scores = self.metric_evaluator_iou.compute() if self.train_seg else None
         path = write_results(detect_result, eval_dir) if (eval_dir and self.train_detect and self.rank == 0) else None
         lane_f1 = None
         if lane_pairs:
-            lane_metric(output=lane_pairs)                                                                         # train.py:397
             lane_f1 = lane_metric.summary()                                                                        # train.py:433
             if self.rank == 0:
                 print("=========================== metric lane %i ===========================" % epoch)
