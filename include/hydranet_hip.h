@@ -687,6 +687,25 @@ int hn_jpeg_scan_subseq_bytes(void);
 int hn_jpeg_scan_decode(const void* streams, long stream_bytes, const void* desc, int N, long max_scan_bytes, long max_blocks, void* ws,
                         long ws_bytes, void* coefs, long coef_bytes, void* status, hipStream_t stream);
 
+/* PNG label decode on the device (png.py; hn_png.hip, semantics in DESIGN.md 4j): inflate (RFC 1950 / 1951: stored, fixed and dynamic
+ * blocks) and the five PNG row filters.  data = the batch's zlib streams (every image's IDAT payloads concatenated; data_bytes a multiple
+ * of 4, data 16-byte aligned); desc = DEVICE array of N 48-byte PngDesc {long idat_off (a multiple of 4), idat_len; long raw_off (into ws, a
+ * multiple of 16: H (1 + W bpp) bytes of filtered scanlines, rounded up to 16); long out_off (into out: H W bytes); int W, H, bpp (1 or 3),
+ * pad} (png.py DESC_DTYPE).  out + out_off receives channel 0 of every pixel, H x W uint8 (what dataset.imread_label returns).  max_idat_bytes
+ * / max_raw_bytes: the batch's largest stream and largest raw size (< 2^28 / < 2^30).  ws: hn_png_ws_bytes (-1 for arguments out of
+ * range) bytes, 16-byte aligned: the raw regions live in its first N * round16(max_raw_bytes) bytes, the library's own scratch behind them.
+ * status: N int32, written for every image:
+ *   0 decoded                        1 reserved block type             2 stored block LEN / NLEN mismatch
+ *   3 code lengths over-subscribed, incomplete, too many, a repeat out of range or no end-of-block code
+ *   4 invalid litlen / distance symbol     5 distance reaches before the start of the output      6 input exhausted
+ *   7 more or fewer raw bytes than H (1 + W bpp)     8 filter byte > 4     9 Adler-32 mismatch     10 bad zlib header (CMF / FLG)
+ *   11 the record does not fit the buffers (nothing written)
+ * A rejected image leaves its out region in any state; nothing outside an image's own ws / out regions (and the library's scratch in ws)
+ * is written.  Three launches, no allocation, no synchronisation. */
+long hn_png_ws_bytes(int N, long max_idat_bytes, long max_raw_bytes);
+int hn_png_decode(const void* data, long data_bytes, const void* desc, int N, long max_idat_bytes, long max_raw_bytes, void* ws,
+                  long ws_bytes, void* out, long out_bytes, void* status, hipStream_t stream);
+
 /* Baseline JPEG encode, the mirror image (jpeg_encode.py; hn_jpeg_enc.hip, semantics in DESIGN.md 4h): libjpeg's default compressor, all
  * integer.  Device stage for a ragged batch: desc = DEVICE array of N 432-byte JpegEncDesc (offsets into frames / coefs, geometry,
  * quantisation tables in natural order).  frames: packed BGR uint8 H x W x 3 frames (augment.pack's layout; a 1-component image encodes

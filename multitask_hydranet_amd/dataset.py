@@ -6,6 +6,8 @@ the parsed labels and `aug_plans` instead of `image`; HydraTrainer.to_gpu runs a
 contract.  Workers never touch the GPU.  With decode="device" a worker stops after the JPEG's entropy stage (jpeg.py: host functions of the
 library) and the batch carries `src_coefs`, which to_gpu decodes on the device into the same packed frames.  With decode="device-entropy" a
 worker only reads the file and parses its header: the batch carries the files' bytes (`src_streams`) and the device decodes the scans too.
+With decode_labels="device" (independent of `decode`) a worker does not decode the label PNG either: it walks the chunk list (png.py) and
+the batch carries the zlib streams (`src_seg_streams`), which to_gpu inflates and unfilters on the device into the packed label maps.
 
     ds = MultitaskData(cfgs, "train")                 # with dataloader.do_split: MultitaskData(cfgs, "train", split_rule=augment.cal_split)
     loader = DataLoader(ds, batch_size=16, shuffle=True, num_workers=8, collate_fn=ds.collate_fn, pin_memory=True)
@@ -89,7 +91,8 @@ def imread_label(path):
 class MultitaskData:
     """torch Dataset (map style) of the reference's layout; items are host-side only"""
 
-    def __init__(self, cfgs, mode, base_seed: int = 0, split_rule: Optional[Callable] = None, decode: str = "host"):
+    def __init__(self, cfgs, mode, base_seed: int = 0, split_rule: Optional[Callable] = None, decode: str = "host",
+                 decode_labels: str = "host"):
         """split_rule: (parsed lanes, source width, source height) -> (split possible, ratio), the rule that dataloader.do_split draws
         its split crops from; augment.cal_split is the reference's (MultitaskData.cal_split, its quirks kept).  A training set with
         augmentation and do_split needs one, and lane labels to apply it to.
@@ -97,10 +100,15 @@ class MultitaskData:
         (jpeg.parse + jpeg.entropy_decode: `src_coefs` + `jpeg_head`) and HydraTrainer.to_gpu finishes the decode on the device
         (jpeg.decode_batch); "device-entropy" -- the worker only reads the file, parses its header and prepares its scan (jpeg.parse +
         jpeg.scan_prepare: `src_stream`, the file's bytes, + `jpeg_head` + `jpeg_scan`) and the device runs the Huffman stage too; a file
-        outside jpeg.py's supported set is decoded with PIL as before, that image only."""
+        outside jpeg.py's supported set is decoded with PIL as before, that image only.
+        decode_labels: "host" -- the worker decodes the label PNG with PIL (`src_seg`); "device" -- the worker only parses the file
+        (png.stream_stage: `src_seg_stream`, the zlib stream, + `png_head`) and HydraTrainer.to_gpu decodes it on the device
+        (png.decode_batch); a file outside png.py's supported set is decoded with PIL as before, that image only."""
         if decode not in ("host", "device", "device-entropy"):
             raise ValueError("decode should be one of ('host', 'device', 'device-entropy')")
-        self.decode = decode
+        if decode_labels not in ("host", "device"):
+            raise ValueError("decode_labels should be one of ('host', 'device')")
+        self.decode, self.decode_labels = decode, decode_labels
         dl = cfgs["dataloader"]
         self.cfgs, self.mode, self.base_seed, self.epoch = cfgs, mode, int(base_seed), 0
         self.network_input_width, self.network_input_height = dl["network_input_width"], dl["network_input_height"]
@@ -174,9 +182,19 @@ class MultitaskData:
         else:
             item["aug_plan"] = sample_plan(self.base_seed, self.epoch, idx, do_flip=self.do_flip)
         if self.train_seg:
-            item["src_seg"] = imread_label(pair["annot_path_seg"])
-            if item["src_seg"].shape != (h, w):
-                raise ValueError("%s: label map %s does not match the frame %s" % (pair["annot_path_seg"], item["src_seg"].shape, (h, w)))
+            phead = None
+            if self.decode_labels == "device":
+                from . import png
+                phead, seg = png.stream_stage(png.read_bytes(pair["annot_path_seg"]))   # (head, zlib stream) or (None, PIL's map)
+            else:
+                seg = imread_label(pair["annot_path_seg"])
+            shape = (phead["height"], phead["width"]) if phead is not None else seg.shape
+            if shape != (h, w):
+                raise ValueError("%s: label map %s does not match the frame %s" % (pair["annot_path_seg"], shape, (h, w)))
+            if phead is not None:
+                item["src_seg_stream"], item["png_head"] = np.frombuffer(seg, dtype=np.uint8), phead
+            else:
+                item["src_seg"] = seg
         if self.train_detect:
             item["det_raw"] = load_detect_annot(pair["annot_path_detect"])
         return item
@@ -188,7 +206,9 @@ class MultitaskData:
 def collate(batch, net_h, net_w):
     """host half of the Collater: the frames (and label maps) packed into one uint8 buffer each; labels and plans as lists.  A batch with
     entropy-decoded items (decode="device") carries `src_coefs` instead of `src_frames`: jpeg.pack_coefs' buffers, the PIL-decoded frames of
-    its unsupported files among them; one with items of decode="device-entropy" carries `src_streams`, jpeg.pack_streams' buffers, likewise."""
+    its unsupported files among them; one with items of decode="device-entropy" carries `src_streams`, jpeg.pack_streams' buffers, likewise.
+    A batch with items of decode_labels="device" carries `src_seg_streams` (png.pack_streams' buffers, the PIL-decoded maps of its
+    unsupported files among them) in place of `src_segs`."""
     if any("src_stream" in b for b in batch):
         from .jpeg import pack_streams
         src = dict(src_streams=pack_streams([(b["jpeg_head"], b["jpeg_scan"], b["src_stream"]) if "src_stream" in b else (None, b["src_frame"])
@@ -204,7 +224,10 @@ def collate(batch, net_h, net_w):
     if "lane_raw" in batch[0]:
         out["lane_raw"] = [b["lane_raw"] for b in batch]
         out["annot_lane_path"] = [b["annot_lane_path"] for b in batch]
-    if "src_seg" in batch[0]:
+    if any("src_seg_stream" in b for b in batch):
+        from .png import pack_streams as pack_png
+        out["src_seg_streams"] = pack_png([(b["png_head"], b["src_seg_stream"]) if "src_seg_stream" in b else (None, b["src_seg"]) for b in batch])
+    elif "src_seg" in batch[0]:
         out["src_segs"] = pack([b["src_seg"] for b in batch])
     if "det_raw" in batch[0]:
         out["det_raw"] = [b["det_raw"] for b in batch]

@@ -192,7 +192,8 @@ class HydraTrainer:
         the device (augment.augment_batch) into the Collater contract; lane targets are then encoded from its annot_lane as for any batch
         without gt_loc / gt_cls.  A batch of MultitaskData(decode="device") carries `src_coefs` (entropy-decoded JPEG coefficients) instead
         of `src_frames`, one of decode="device-entropy" `src_streams` (the files' bytes): jpeg.decode_batch finishes the decode on the device
-        into the same packed frames first."""
+        into the same packed frames first.  A batch of MultitaskData(decode_labels="device") carries `src_seg_streams` (the label PNGs'
+        zlib streams) instead of `src_segs`: png.decode_batch inflates and unfilters them on the device into the packed label maps."""
         if "image" not in batch_data and ("src_frames" in batch_data or "src_coefs" in batch_data or "src_streams" in batch_data):
             batch_data = self._augment(batch_data)
         batch_data["image"] = batch_data["image"].to(self.device).float()
@@ -215,10 +216,14 @@ class HydraTrainer:
             frames = decode_batch(batch_data.get("src_coefs", batch_data.get("src_streams")), device=self.device)
         else:
             frames = batch_data["src_frames"]
+        segs = batch_data.get("src_segs") if self.train_seg else None
+        if self.train_seg and "src_seg_streams" in batch_data:
+            from .png import decode_batch as decode_labels
+            segs = decode_labels(batch_data["src_seg_streams"], device=self.device)
         out = augment_batch(frames, batch_data.get("lane_raw") if self.train_lane else None,
-                            batch_data.get("det_raw") if self.train_detect else None, batch_data.get("src_segs") if self.train_seg else None,
+                            batch_data.get("det_raw") if self.train_detect else None, segs,
                             batch_data["aug_plans"], (dl["network_input_height"], dl["network_input_width"]), device=self.device)
-        rest = {k: v for k, v in batch_data.items() if k not in ("src_frames", "src_coefs", "src_streams", "src_segs", "lane_raw", "det_raw", "aug_plans")}
+        rest = {k: v for k, v in batch_data.items() if k not in ("src_frames", "src_coefs", "src_streams", "src_segs", "src_seg_streams", "lane_raw", "det_raw", "aug_plans")}
         rest.update(out)
         return rest
 
