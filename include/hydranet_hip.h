@@ -560,6 +560,11 @@ int hn_lane_decode_nms(const float* predict_cls, const float* predict_loc, int N
 /* Input pre-processing (demo.py:26-50,186-196; dataset/utility.py:213-227): uint8 BGR frames [N][Hs][Ws][3] -> bilinear resize (cv2.resize
  * INTER_LINEAR fixed-point form for 8-bit images) -> RGB -> (v/255 - mean)/std -> fp32 [N][3][Hd][Wd]. */
 int hn_preprocess_bgr(const void* src, int N, int Hs, int Ws, float* dst, int Hd, int Wd, hipStream_t stream);
+/* The same resize up to its 8-bit value (cv2.resize of a BGR frame, INTER_LINEAR; preprocess.resize_bgr): a ragged batch of uint8 BGR
+ * frames, frame n of desc[n].H x desc[n].W at src + desc[n].off (desc = DEVICE array of N 16-byte records {long off; int H, W}) -> uint8
+ * dst [N][Hd][Wd][3].  A frame that has the output size is copied; a record that does not fit [src, src + src_bytes) leaves its frame
+ * unwritten.  One launch, no allocation, no synchronisation.  N, Hd <= 65535. */
+int hn_resize_bgr8(const void* src, long src_bytes, const void* desc, int N, void* dst, int Hd, int Wd, hipStream_t stream);
 
 /* Segmentation overlay = SegmentHeader.decode (head_seg/segmentation.py:107-125; deploy/src/model/hydranet_model.cpp:758) after the
  * arg-max: mask int64 [N][H][W] -> colour LUT uint8 [ncls][3] (ids without a colour stay black) -> cv2.resize to the frame size (the

@@ -352,6 +352,18 @@ __device__ __forceinline__ void lin_coef(int d, double scale, int ssize, int& s0
     c1 = (short)__float2int_rn(a1);
 }
 
+// one output pixel of the 8-bit resize: rows r0 / r1 of the source frame, columns sx / sx1, the two coefficient pairs -> v[3] in 0..255
+__device__ __forceinline__ void lin_bgr8(const unsigned char* r0, const unsigned char* r1, int sx, int sx1, short ax0, short ax1, short by0,
+                                         short by1, int v[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int h0 = r0[sx * 3 + c] * ax0 + r0[sx1 * 3 + c] * ax1;           // horizontal pass, 11-bit fixed point
+        const int h1 = r1[sx * 3 + c] * ax0 + r1[sx1 * 3 + c] * ax1;
+        v[c] = (((by0 * (h0 >> 4)) >> 16) + ((by1 * (h1 >> 4)) >> 16) + 2) >> 2;
+        v[c] = v[c] < 0 ? 0 : (v[c] > 255 ? 255 : v[c]);
+    }
+}
+
 __global__ __launch_bounds__(256) void preprocess_kernel(const unsigned char* src, int Hs, int Ws, float* dst, int Hd, int Wd, int N) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     const long total = (long)N * Hd * Wd;
@@ -371,15 +383,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const unsigned char* sr
         lin_coef(x, (double)Ws / Wd, Ws, sx, ax0, ax1);
         lin_coef(y, (double)Hs / Hd, Hs, sy, by0, by1);
         const int sx1 = sx + 1 < Ws ? sx + 1 : Ws - 1, sy1 = sy + 1 < Hs ? sy + 1 : Hs - 1;
-        const unsigned char* r0 = im + (long)sy * Ws * 3;
-        const unsigned char* r1 = im + (long)sy1 * Ws * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int h0 = r0[sx * 3 + c] * ax0 + r0[sx1 * 3 + c] * ax1;       // horizontal pass, 11-bit fixed point
-            const int h1 = r1[sx * 3 + c] * ax0 + r1[sx1 * 3 + c] * ax1;
-            v[c] = (((by0 * (h0 >> 4)) >> 16) + ((by1 * (h1 >> 4)) >> 16) + 2) >> 2;
-            v[c] = v[c] < 0 ? 0 : (v[c] > 255 ? 255 : v[c]);
-        }
+        lin_bgr8(im + (long)sy * Ws * 3, im + (long)sy1 * Ws * 3, sx, sx1, ax0, ax1, by0, by1, v);
     }
     const double mean[3] = {0.485, 0.456, 0.406}, sd[3] = {0.229, 0.224, 0.225};
     const long plane = (long)Hd * Wd;
@@ -396,6 +400,77 @@ extern "C" int hn_preprocess_bgr(const void* src, int N, int Hs, int Ws, float* 
     HN_CHECK_ARG(src && dst && N > 0 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0);
     const long total = (long)N * Hd * Wd;
     hipLaunchKernelGGL(preprocess_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const unsigned char*)src, Hs, Ws, dst, Hd, Wd, N);
+    HN_LAUNCH_CHECK();
+}
+
+// 3b. the same resize up to the 8-bit value (cv2.resize of a BGR frame): a ragged packed batch of uint8 BGR frames -> uint8 BGR frames
+//     of ONE size, back to back.  One thread per quad of output pixels (12 bytes = three dword stores when the output rows are dword
+//     aligned), one workgroup row per output row: the row pair and its coefficients are uniform over the workgroup.  A frame that has
+//     the output size already is copied.
+struct ResizeSrc {
+    long off;      // byte offset of the frame in src
+    int H, W;
+};
+
+__global__ __launch_bounds__(128) void resize_bgr8_kernel(const unsigned char* src, long src_bytes, const ResizeSrc* desc, unsigned char* dst, int Hd,
+                                                          int Wd, int vec) {
+    const int q = blockIdx.x * 128 + threadIdx.x;
+    const int x0 = q * 4;
+    if (x0 >= Wd) return;
+    const int y = blockIdx.y, n = blockIdx.z;
+    const ResizeSrc d = desc[n];
+    const int Hs = d.H, Ws = d.W;
+    if (d.off < 0 || Hs <= 0 || Ws <= 0 || d.off + (long)Hs * Ws * 3 > src_bytes) return;       // a descriptor that does not fit: left unwritten
+    const unsigned char* im = src + d.off;
+    const int nx = Wd - x0 < 4 ? Wd - x0 : 4;
+    unsigned char px[12];
+    if (Hs == Hd && Ws == Wd) {
+        const unsigned char* p = im + ((long)y * Ws + x0) * 3;
+#pragma unroll
+        for (int i = 0; i < 12; ++i)
+            if (i < nx * 3) px[i] = p[i];
+    } else {
+        int sy;
+        short by0, by1;
+        lin_coef(y, (double)Hs / Hd, Hs, sy, by0, by1);
+        const int sy1 = sy + 1 < Hs ? sy + 1 : Hs - 1;
+        const unsigned char* r0 = im + (long)sy * Ws * 3;
+        const unsigned char* r1 = im + (long)sy1 * Ws * 3;
+        const double xs = (double)Ws / Wd;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (i < nx) {
+                int sx, v[3];
+                short ax0, ax1;
+                lin_coef(x0 + i, xs, Ws, sx, ax0, ax1);
+                lin_bgr8(r0, r1, sx, sx + 1 < Ws ? sx + 1 : Ws - 1, ax0, ax1, by0, by1, v);
+                px[3 * i] = (unsigned char)v[0];
+                px[3 * i + 1] = (unsigned char)v[1];
+                px[3 * i + 2] = (unsigned char)v[2];
+            }
+        }
+    }
+    unsigned char* o = dst + (((long)n * Hd + y) * Wd + x0) * 3;
+    if (vec && nx == 4) {
+        unsigned int* o4 = (unsigned int*)o;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            o4[k] = (unsigned)px[4 * k] | ((unsigned)px[4 * k + 1] << 8) | ((unsigned)px[4 * k + 2] << 16) | ((unsigned)px[4 * k + 3] << 24);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 12; ++i)
+            if (i < nx * 3) o[i] = px[i];
+    }
+}
+
+/* src: uint8 BGR frames anywhere in [src, src + src_bytes); desc: DEVICE array of N 16-byte records {long off; int H, W}; dst: uint8
+ * [N][Hd][Wd][3].  A record that does not fit src_bytes leaves its frame unwritten. */
+extern "C" int hn_resize_bgr8(const void* src, long src_bytes, const void* desc, int N, void* dst, int Hd, int Wd, hipStream_t st) {
+    HN_CHECK_ARG(src && desc && dst && src_bytes > 0 && N > 0 && N <= 65535 && Hd > 0 && Hd <= 65535 && Wd > 0);
+    const int quads = (Wd + 3) / 4;
+    const int vec = (Wd % 4 == 0 && ((size_t)dst & 3) == 0) ? 1 : 0;
+    hipLaunchKernelGGL(resize_bgr8_kernel, dim3((unsigned)((quads + 127) / 128), (unsigned)Hd, (unsigned)N), dim3(128), 0, st,
+                       (const unsigned char*)src, src_bytes, (const ResizeSrc*)desc, (unsigned char*)dst, Hd, Wd, vec);
     HN_LAUNCH_CHECK();
 }
 

@@ -1,5 +1,6 @@
 """demo.py of the reference (model/demo.py:52-261) on the HIP path: frame -> pre-processing -> HydraNet forward -> the three decodes.
 
+    python -m multitask_hydranet_amd.demo [--cfg cfgs/hydranet_big.yml] [--weights ckpt.pth] --video IN.avi --out OUT.avi [--batch N] [--size WxH] [--max-frames N]
     python -m multitask_hydranet_amd.demo [--cfg cfgs/hydranet_big.yml] [--weights ckpt.pth] --images DIR --out DIR_VIS
     python -m multitask_hydranet_amd.demo [--cfg cfgs/hydranet_big.yml] [--weights ckpt.pth] [--frames frames.npy] [--out demo_out]
 
@@ -12,8 +13,12 @@ hn_seg_overlay, hn_det_postprocess).
 device (jpeg.imread_bgr_device), runs the sequence above, is DRAWN in the reference's order -- laneheader.visual, the seg overlay,
 detectheader.display (draw.py) -- and is written as a JPEG of the same name into --out (jpeg_encode); the frame stays on the device from
 decode to encode (Demo.process_device).
-What is not: cv2 (absent from this image), so no window and no video input / writer.  Without --images the frames come from a .npy array
-[T, H, W, 3] uint8 BGR or are synthesised, the blended frames are returned without drawing (and written as .npy by the command line) and
+--video is the reference's default mode (demo.py:64, 155-160, 178, 251-255: cv2.VideoCapture in, cv2.VideoWriter out) for a Motion-JPEG AVI: the
+container is read and written by avi.py, the frames are the JPEGs the project decodes and encodes itself, taken in groups of --batch
+through the same stages with one launch sequence and one host synchronisation per group (Demo.process_device_batch), resized to --size on
+the device when one is given (hn_resize_bgr8), and written at the input's frame rate, with OUT.avi.results.json beside it (run_video).
+What is not: cv2 (absent from this image), so no window, and no video codec other than Motion-JPEG.  Without --images / --video the frames
+come from a .npy array [T, H, W, 3] uint8 BGR or are synthesised, the blended frames are returned without drawing (and written as .npy by the command line) and
 the decoded lanes and boxes are returned as data (Demo.process)."""
 from __future__ import annotations
 
@@ -126,6 +131,63 @@ class Demo:
         return res
 
 
+    @torch.no_grad()
+    def process_device_batch(self, frames: dict, quality: int = 95, subsampling: str = "4:2:0", entropy: str = "host", out_hw=None) -> Dict[str, object]:
+        """process_device for the B frames of a packed batch that all have one size (a video's): one preprocess_bgr and one forward over
+        the batch, the lane and box decodes of the batch read back at ONE point (the drawing primitives are built from them on the host),
+        one draw_packed per drawing stage, one seg overlay, an optional resize_bgr of the annotated frames to out_hw = (height, width),
+        one encode_batch.  "jpeg", "lanes" and "detections" hold one entry per frame -- for every frame what process_device gives for
+        that frame alone, as long as the forward's arithmetic for an image does not depend on the batch it runs in --
+        and "visual" the annotated (and resized) frames in the packed device layout.  Like process_device it paints into `frames`."""
+        from . import jpeg_encode
+        from .postprocess import postprocess, postprocess_device
+        from .preprocess import preprocess_bgr, resize_bgr
+        from .visual import seg_decode_device
+        net = self.net
+        shapes = np.asarray(frames["shapes"], dtype=np.int64).reshape(-1, 2)
+        offsets = np.asarray(frames["offsets"], dtype=np.int64).reshape(-1)
+        B = len(shapes)
+        assert B > 0 and bool((shapes == shapes[0]).all()), "the frames of a batch have one size"
+        org_h, org_w = (int(v) for v in shapes[0])
+        org_size = (org_w, org_h)
+        nbytes = org_h * org_w * 3
+        tic = time.time()
+        if not np.array_equal(offsets, offsets[0] + nbytes * np.arange(B)):               # not back to back: make them so
+            data = torch.cat([frames["data"][int(o):int(o) + nbytes] for o in offsets])
+            offsets = nbytes * np.arange(B, dtype=np.int64)
+            frames = {"data": data, "offsets": offsets, "shapes": shapes}
+        off = int(offsets[0])
+        batch = frames["data"][off:off + B * nbytes].view(B, org_h, org_w, 3)
+        img = preprocess_bgr(batch, (self.net_h, self.net_w), device=self.device)
+        outputs = net(img)
+        res: Dict[str, object] = {"org_size": org_size}
+        # the two decodes first, launched back to back and read back together: the one point where the host waits for the device
+        if self.train_detect:
+            det = outputs["detection"]
+            det_args = ((img.shape[2], img.shape[3]), det["anchors"], det["regression"], det["classification"], self.det_conf, self.det_iou)
+            launched = postprocess_device(*det_args)
+        if self.train_lane:
+            cls_preds, loc_preds = outputs["lane"]["predict_cls"], outputs["lane"]["predict_loc"]
+            nms_sets = net.laneheader.decode_batch(cls_preds, loc_preds, self.lane_coder, self.lane_conf, self.lane_nms, False)
+            res["lanes"] = [net.laneheader.scale_to_org(s, self.net_w, self.net_h, org_w, org_h)["Lines"] for s in nms_sets]
+        if self.train_detect:
+            res["detections"] = postprocess(*det_args, launched=launched)
+        # the drawing, in the reference's order: lanes, seg overlay, boxes
+        if self.train_lane:
+            frames = net.laneheader.visual(frames, res["lanes"], org_w, filter_vertical=True)
+        if self.train_seg:
+            blended = seg_decode_device(batch, outputs["seg"], self.colors)
+            frames = {"data": blended.view(-1), "offsets": nbytes * np.arange(B, dtype=np.int64), "shapes": shapes.copy()}
+        if self.train_detect:
+            frames = net.detectheader.display(res["detections"], frames, self.obj_list, org_size, (self.net_w, self.net_h))
+        if out_hw is not None and (int(out_hw[0]), int(out_hw[1])) != (org_h, org_w):
+            frames = resize_bgr(frames, out_hw)
+        res["jpeg"] = jpeg_encode.encode_batch(frames, quality, subsampling, entropy)
+        res["visual"] = frames
+        res["ms"] = 1000.0 * (time.time() - tic)
+        return res
+
+
 def list_images(folder: str) -> List[str]:
     """the *.jpg / *.jpeg files of the folder, sorted by name"""
     return [os.path.join(folder, f) for f in sorted(os.listdir(folder)) if f.lower().endswith((".jpg", ".jpeg"))]
@@ -148,6 +210,67 @@ def run_images(demo: "Demo", folder: str, out_dir: str, quality: int = 95, subsa
         print("frame %d (%s): total process time is %i ms, %d lanes, %d boxes" % (t, os.path.basename(path), r["ms"], nl, nd))
         summary.append({"frame": t, "file": os.path.basename(path), "ms": r["ms"], "lanes": nl, "boxes": nd})
     json.dump(summary, open(os.path.join(out_dir, "results.json"), "w"), indent=1)
+    return summary
+
+
+def parse_size(text: str):
+    """"1920x1080" -> (1920, 1080)"""
+    w, _, h = text.lower().partition("x")
+    if not (w.isdigit() and h.isdigit() and int(w) > 0 and int(h) > 0):
+        raise argparse.ArgumentTypeError("a frame size is WIDTHxHEIGHT, e.g. 1920x1080, not %r" % text)
+    return int(w), int(h)
+
+
+def run_video(demo: "Demo", src: str, dst: str, batch: int = 8, quality: int = 95, subsampling: str = "4:2:0", entropy: str = "host",
+              decode_entropy: str = "host", size=None, max_frames: Optional[int] = None) -> List[dict]:
+    """--video: a Motion-JPEG AVI -> the annotated Motion-JPEG AVI `dst` of the input's frame rate, plus dst + ".results.json".  The frames
+    are taken in file order in groups of `batch` (the last group is smaller), decoded (jpeg.imread_bgr_device), annotated
+    (Demo.process_device_batch) and appended to an avi.AviWriter; size = (width, height) of the output frames, the input's without.  A
+    zero-length chunk -- "repeat the previous frame" -- writes the previous annotated JPEG again (a leading one is skipped).  The bytes
+    of the next group are read and completed (avi.frame_bytes) while the device works on the current one."""
+    import json
+    import mmap
+    from . import avi, jpeg
+    assert batch >= 1, batch
+    summary: List[dict] = []
+    with open(src, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as data:
+        index = avi.read_index(data)
+        if index["truncated"]:
+            print("%s is cut short: %d complete frames" % (src, len(index["frames"])))
+        in_w, in_h = index["width"], index["height"]
+        out_w, out_h = (int(size[0]), int(size[1])) if size else (in_w, in_h)
+        # which coded frame every output frame shows: a repeat chunk shows the one before it
+        plan, coded = [], []
+        for i, (_, nbytes) in enumerate(index["frames"]):
+            if max_frames is not None and len(plan) >= max_frames:
+                break
+            if nbytes:
+                coded.append(i)
+            if coded:
+                plan.append(len(coded) - 1)
+        groups = [coded[a:a + batch] for a in range(0, len(coded), batch)]
+        read = lambda g: [avi.frame_bytes(index, data, i) for i in groups[g]] if g < len(groups) else None
+        fps = (index["rate"], index["scale"]) if index["rate"] > 0 and index["scale"] > 0 else (10, 1)
+        with avi.AviWriter(dst, out_w, out_h, fps) as out:
+            nxt, done, p = read(0), 0, 0
+            for g in range(len(groups)):
+                frames = jpeg.imread_bgr_device(nxt, device=demo.device, entropy=decode_entropy)
+                got = [tuple(int(v) for v in s) for s in frames["shapes"]]
+                if got != [(in_h, in_w)] * len(got):
+                    raise ValueError("%s: frames of %s in a stream whose header says %dx%d" % (src, sorted(set(got)), in_w, in_h))
+                nxt = read(g + 1)                                        # the device is decoding: the host's share of the next group
+                r = demo.process_device_batch(frames, quality, subsampling, entropy, out_hw=(out_h, out_w))
+                B = len(groups[g])
+                while p < len(plan) and plan[p] < done + B:
+                    k = plan[p] - done
+                    out.write(r["jpeg"][k])
+                    nd = len(r["detections"][k]["rois"]) if "detections" in r else 0
+                    nl = len(r["lanes"][k]) if "lanes" in r else 0
+                    summary.append({"frame": p, "file": os.path.basename(src), "ms": r["ms"] / B, "lanes": nl, "boxes": nd})
+                    p += 1
+                done += B
+                print("frames %d-%d: total process time is %i ms" % (done - B, done - 1, r["ms"]))
+    json.dump(summary, open(dst + ".results.json", "w"), indent=1)
     return summary
 
 
@@ -176,12 +299,19 @@ def main(argv=None):
     ap.add_argument("--weights", default=None, help="checkpoint written by train.py (module.-prefixed keys are accepted); random init without")
     ap.add_argument("--frames", default=None, help=".npy uint8 [T, H, W, 3] BGR frames; synthetic 1080p frames without")
     ap.add_argument("--images", default=None, help="folder of *.jpg / *.jpeg frames: each is annotated and written as a JPEG of the same name into --out")
-    ap.add_argument("--quality", type=int, default=95, help="JPEG quality of the annotated frames (--images)")
-    ap.add_argument("--entropy", choices=("host", "device"), default="host", help="where the Huffman stage of the JPEG encode runs (--images)")
-    ap.add_argument("--decode-entropy", choices=("host", "device"), default="host", help="where the Huffman stage of the JPEG decode runs (--images)")
+    ap.add_argument("--video", default=None, help="Motion-JPEG AVI: every frame is annotated and written to the AVI --out (and --out.results.json)")
+    ap.add_argument("--batch", type=int, default=8, help="frames per launch sequence (--video)")
+    ap.add_argument("--size", type=parse_size, default=None, help="WIDTHxHEIGHT of the output video's frames (--video); the input's without")
+    ap.add_argument("--max-frames", type=int, default=None, help="stop after this many frames (--video)")
+    ap.add_argument("--quality", type=int, default=95, help="JPEG quality of the annotated frames (--images, --video)")
+    ap.add_argument("--entropy", choices=("host", "device"), default="host", help="where the Huffman stage of the JPEG encode runs (--images, --video)")
+    ap.add_argument("--decode-entropy", choices=("host", "device"), default="host", help="where the Huffman stage of the JPEG decode runs (--images, --video)")
     ap.add_argument("--count", type=int, default=4)
-    ap.add_argument("--out", default=None, help="directory for the annotated JPEGs (--images) or frame_%%04d.npy (blended frames), and results.json")
+    ap.add_argument("--out", default=None, help="directory for the annotated JPEGs (--images) or frame_%%04d.npy (blended frames), and results.json; "
+                    "the annotated AVI (--video)")
     args = ap.parse_args(argv)
+    if args.video and not args.out:
+        ap.error("--video needs --out")
     cfgs = yaml.safe_load(open(args.cfg))
     torch.manual_seed(0)
     demo = Demo(cfgs, args.weights)
@@ -193,6 +323,9 @@ def main(argv=None):
         if not args.out:
             ap.error("--images needs --out")
         return run_images(demo, args.images, args.out, args.quality, entropy=args.entropy, decode_entropy=args.decode_entropy)
+    if args.video:
+        return run_video(demo, args.video, args.out, args.batch, args.quality, entropy=args.entropy, decode_entropy=args.decode_entropy, size=args.size,
+                         max_frames=args.max_frames)
     frames = np.load(args.frames) if args.frames else synthetic_frames(args.count)
     if args.out:
         os.makedirs(args.out, exist_ok=True)

@@ -54,11 +54,14 @@ def postprocess_device(img_hw, anchors, regression, classification, threshold, i
     return out
 
 
-def postprocess(img_hw, anchors, regression, classification, threshold, iou_threshold):
-    """the reference's return contract: one dict(rois, class_ids, scores) of numpy arrays per image (empty arrays when nothing is kept)"""
+def postprocess(img_hw, anchors, regression, classification, threshold, iou_threshold, launched=None):
+    """the reference's return contract: one dict(rois, class_ids, scores) of numpy arrays per image (empty arrays when nothing is kept).
+    launched: what postprocess_device returned for the same arguments at the default capacity, when the caller has launched it already
+    (to read its result back at a synchronisation point of its own choosing)"""
     cap = 4096
     while True:
-        res = postprocess_device(img_hw, anchors, regression, classification, threshold, iou_threshold, cap)
+        res = launched if launched is not None else postprocess_device(img_hw, anchors, regression, classification, threshold, iou_threshold, cap)
+        launched = None
         total = res["total"].cpu().numpy()
         if int(total.max(initial=0)) <= res["cap"]:
             break
