@@ -711,6 +711,28 @@ long hn_png_ws_bytes(int N, long max_idat_bytes, long max_raw_bytes);
 int hn_png_decode(const void* data, long data_bytes, const void* desc, int N, long max_idat_bytes, long max_raw_bytes, void* ws,
                   long ws_bytes, void* out, long out_bytes, void* status, hipStream_t stream);
 
+/* PNG label encode on the device, the mirror image (png_encode.py; hn_png_enc.hip, semantics in DESIGN.md 4l): class maps -> per image a
+ * complete zlib stream (header 78 01, fixed-Huffman deflate blocks of hn_png_enc_chunk_bytes() raw bytes each, big-endian Adler-32) of the
+ * filtered scanlines of the map resized to (Ho, Wo) with cv2's INTER_NEAREST index rule: the payload of a PNG file's IDAT chunk (bit
+ * depth 8, one byte per pixel).  src = int64 class ids (src_is_int64 = 1; 8-byte aligned) or uint8 maps (0), src_elems elements; desc =
+ * DEVICE array of N 64-byte PngEncDesc {long src_off (elements); long raw_off (into ws, a multiple of 16: Ho (1 + Wo) bytes of filtered
+ * scanlines, rounded up to 16); long out_off (into out, a multiple of 4), out_cap (bytes the stream may use, a multiple of 4); int Hs, Ws,
+ * Ho, Wo (1..65535); long pad[2]} (png_encode.py DESC_DTYPE).  result = DEVICE array of N 16-byte records {long stream_bytes; int status,
+ * pad}, written for every image:
+ *   0 encoded      1 an int64 value outside 0..255 among the values the resize samples      2 the stream is longer than out_cap
+ *   3 the record does not fit the buffers
+ * An image with a non-zero status has stream_bytes 0 and nothing written to out; no write ever lands at or past an image's out_cap, or
+ * outside [ws, ws + hn_png_enc_ws_bytes(...)).  hn_png_enc_cap_bytes(raw): a capacity no stream of `raw` filtered bytes exceeds, 2 +
+ * ceil((9 raw + 10 ceil(raw / chunk)) / 8) + 4 rounded up to 16 (-1 out of range).  max_out_h / max_raw_bytes: the batch's largest Ho and
+ * Ho (1 + Wo) (< 2^30); they size the grids and the workspace (hn_png_enc_ws_bytes, -1 for arguments out of range; 16-byte aligned, the
+ * raw regions in its first N * round16(max_raw_bytes) bytes; it needs no clearing).  One memset of N words and four launches, no
+ * allocation, no synchronisation; no workgroup waits on another. */
+int hn_png_enc_chunk_bytes(void);
+long hn_png_enc_cap_bytes(long raw_bytes);
+long hn_png_enc_ws_bytes(int N, long max_raw_bytes);
+int hn_png_encode(const void* src, long src_elems, int src_is_int64, const void* desc, int N, int max_out_h, long max_raw_bytes, void* ws,
+                  long ws_bytes, void* out, long out_bytes, void* result, hipStream_t stream);
+
 /* Baseline JPEG encode, the mirror image (jpeg_encode.py; hn_jpeg_enc.hip, semantics in DESIGN.md 4h): libjpeg's default compressor, all
  * integer.  Device stage for a ragged batch: desc = DEVICE array of N 432-byte JpegEncDesc (offsets into frames / coefs, geometry,
  * quantisation tables in natural order).  frames: packed BGR uint8 H x W x 3 frames (augment.pack's layout; a 1-component image encodes

@@ -1,7 +1,7 @@
 """demo.py of the reference (model/demo.py:52-261) on the HIP path: frame -> pre-processing -> HydraNet forward -> the three decodes.
 
     python -m multitask_hydranet_amd.demo [--cfg cfgs/hydranet_big.yml] [--weights ckpt.pth] --video IN.avi --out OUT.avi [--batch N] [--size WxH] [--max-frames N]
-    python -m multitask_hydranet_amd.demo [--cfg cfgs/hydranet_big.yml] [--weights ckpt.pth] --images DIR --out DIR_VIS
+    python -m multitask_hydranet_amd.demo [--cfg cfgs/hydranet_big.yml] [--weights ckpt.pth] --images DIR --out DIR_VIS [--save-seg DIR_SEG [--seg-palette]]
     python -m multitask_hydranet_amd.demo [--cfg cfgs/hydranet_big.yml] [--weights ckpt.pth] [--frames frames.npy] [--out demo_out]
 
 What is kept: the configuration handling (network input size, which heads run, lane codec geometry, colour table), `module.`-prefixed
@@ -19,7 +19,11 @@ through the same stages with one launch sequence and one host synchronisation pe
 the device when one is given (hn_resize_bgr8), and written at the input's frame rate, with OUT.avi.results.json beside it (run_video).
 What is not: cv2 (absent from this image), so no window, and no video codec other than Motion-JPEG.  Without --images / --video the frames
 come from a .npy array [T, H, W, 3] uint8 BGR or are synthesised, the blended frames are returned without drawing (and written as .npy by the command line) and
-the decoded lanes and boxes are returned as data (Demo.process)."""
+the decoded lanes and boxes are returned as data (Demo.process).
+--save-seg DIR (with --images / --video) also keeps what the seg head predicted, not only its colour blend: the arg-max class map the overlay
+is painted from, nearest-resized to the frame's original size and written as an 8-bit label PNG per frame (<image stem>.png, or
+frame_%06d.png for a video) -- the format MultitaskData reads its seg labels from.  Filter and deflate run on the device (png_encode,
+hn_png_enc.hip); --seg-palette writes colour type 3 with the demo's colours instead of grey, the same index bytes."""
 from __future__ import annotations
 
 import argparse
@@ -32,6 +36,11 @@ import torch
 import yaml
 
 SEG_CLASS_COLOR_ID = {0: (0, 0, 0), 1: (128, 0, 128), 2: (255, 255, 255), 3: (0, 255, 255), 4: (0, 255, 0)}    # demo.py:91-96
+
+
+def seg_palette(colors: dict) -> dict:
+    """the demo's colour table (BGR, as it is painted into BGR frames) -> a PNG palette {id: (r, g, b)}"""
+    return {int(k): (int(c[2]), int(c[1]), int(c[0])) for k, c in colors.items()}
 
 
 class Demo:
@@ -93,12 +102,27 @@ class Demo:
 
 
     @torch.no_grad()
-    def process_device(self, frames: dict, quality: int = 95, subsampling: str = "4:2:0", entropy: str = "host") -> Dict[str, object]:
+    def _need_seg(self):
+        if not self.train_seg:
+            raise ValueError("seg class maps were asked for, but this configuration runs no seg head (train.train_seg is off)")
+
+    def _seg_mask(self, seg):
+        """the arg-max class map [N, H, W] int64 the overlay is painted from (the deploy forward already returns it)"""
+        from . import ops as K
+        return K.argmax_channels(seg.detach().float()) if seg.dim() == 4 else seg
+
+    @torch.no_grad()
+    def process_device(self, frames: dict, quality: int = 95, subsampling: str = "4:2:0", entropy: str = "host", seg_png: bool = False,
+                       seg_palette: Optional[dict] = None) -> Dict[str, object]:
         """the same iteration for ONE frame that is already on the device in the packed layout of jpeg.imread_bgr_device, with the
         reference's drawing (demo.py:230, 235, 244) and its cv2.imwrite (demo.py:261): "jpeg" holds the annotated frame's JFIF bytes,
         "visual" the annotated frame in the packed device layout.  The frame is not copied to the host.  entropy: "host" | "device", where
-        the Huffman stage of the encode runs (jpeg_encode.encode_batch); the bytes are the same."""
-        from . import draw, jpeg_encode
+        the Huffman stage of the encode runs (jpeg_encode.encode_batch); the bytes are the same.  seg_png: "seg_png" holds the PNG file
+        bytes of the arg-max class map at the frame's original size (png_encode.encode_batch; colour type 3 with seg_palette = {id: (r, g,
+        b)}, grey without); everything else is what the call gives without it."""
+        from . import draw, jpeg_encode, png_encode
+        if seg_png:
+            self._need_seg()
         from .preprocess import preprocess_bgr
         from .visual import seg_decode_device
         net = self.net
@@ -118,8 +142,11 @@ class Demo:
             res["lanes"] = [net.laneheader.scale_to_org(nms_set, self.net_w, self.net_h, org_w, org_h)["Lines"]]
             frames = net.laneheader.visual(frames, res["lanes"], org_w, filter_vertical=True)
         if self.train_seg:
-            blended = seg_decode_device(frame, outputs["seg"], self.colors)
+            seg = self._seg_mask(outputs["seg"]) if seg_png else outputs["seg"]
+            blended = seg_decode_device(frame, seg, self.colors)
             frames = {"data": blended.view(-1), "offsets": np.zeros(1, np.int64), "shapes": np.array([[org_h, org_w]], np.int64)}
+            if seg_png:
+                res["seg_png"] = png_encode.encode_batch(seg, out_sizes=(org_h, org_w), palette=seg_palette, device=self.device)[0]
         if self.train_detect:
             det = outputs["detection"]
             res["detections"] = net.detectheader.decode(img, det["regression"], det["classification"], det["anchors"], conf_thres=self.det_conf,
@@ -132,14 +159,19 @@ class Demo:
 
 
     @torch.no_grad()
-    def process_device_batch(self, frames: dict, quality: int = 95, subsampling: str = "4:2:0", entropy: str = "host", out_hw=None) -> Dict[str, object]:
+    def process_device_batch(self, frames: dict, quality: int = 95, subsampling: str = "4:2:0", entropy: str = "host", out_hw=None,
+                             seg_png: bool = False, seg_palette: Optional[dict] = None) -> Dict[str, object]:
         """process_device for the B frames of a packed batch that all have one size (a video's): one preprocess_bgr and one forward over
         the batch, the lane and box decodes of the batch read back at ONE point (the drawing primitives are built from them on the host),
         one draw_packed per drawing stage, one seg overlay, an optional resize_bgr of the annotated frames to out_hw = (height, width),
         one encode_batch.  "jpeg", "lanes" and "detections" hold one entry per frame -- for every frame what process_device gives for
         that frame alone, as long as the forward's arithmetic for an image does not depend on the batch it runs in --
-        and "visual" the annotated (and resized) frames in the packed device layout.  Like process_device it paints into `frames`."""
-        from . import jpeg_encode
+        and "visual" the annotated (and resized) frames in the packed device layout.  Like process_device it paints into `frames`.
+        seg_png: "seg_png" holds one PNG file per frame, the arg-max class maps at the frames' ORIGINAL size (out_hw does not apply),
+        encoded for the whole batch in one png_encode.encode_batch."""
+        from . import jpeg_encode, png_encode
+        if seg_png:
+            self._need_seg()
         from .postprocess import postprocess, postprocess_device
         from .preprocess import preprocess_bgr, resize_bgr
         from .visual import seg_decode_device
@@ -176,8 +208,11 @@ class Demo:
         if self.train_lane:
             frames = net.laneheader.visual(frames, res["lanes"], org_w, filter_vertical=True)
         if self.train_seg:
-            blended = seg_decode_device(batch, outputs["seg"], self.colors)
+            seg = self._seg_mask(outputs["seg"]) if seg_png else outputs["seg"]
+            blended = seg_decode_device(batch, seg, self.colors)
             frames = {"data": blended.view(-1), "offsets": nbytes * np.arange(B, dtype=np.int64), "shapes": shapes.copy()}
+            if seg_png:
+                res["seg_png"] = png_encode.encode_batch(seg, out_sizes=(org_h, org_w), palette=seg_palette, device=self.device)
         if self.train_detect:
             frames = net.detectheader.display(res["detections"], frames, self.obj_list, org_size, (self.net_w, self.net_h))
         if out_hw is not None and (int(out_hw[0]), int(out_hw[1])) != (org_h, org_w):
@@ -194,17 +229,25 @@ def list_images(folder: str) -> List[str]:
 
 
 def run_images(demo: "Demo", folder: str, out_dir: str, quality: int = 95, subsampling: str = "4:2:0", entropy: str = "host",
-               decode_entropy: str = "host") -> List[dict]:
+               decode_entropy: str = "host", seg_dir: Optional[str] = None, seg_palette: Optional[dict] = None) -> List[dict]:
     """--images: folder of JPEGs -> annotated JPEGs of the same names in out_dir, plus results.json.  entropy / decode_entropy: where the
-    Huffman stage of the encode / of the decode runs; the bytes written are the same."""
+    Huffman stage of the encode / of the decode runs; the bytes written are the same.  seg_dir: every frame's class map goes there as
+    <image stem>.png (Demo.process_device's seg_png)."""
     import json
     from . import jpeg
+    if seg_dir is not None:
+        demo._need_seg()
+        os.makedirs(seg_dir, exist_ok=True)
     os.makedirs(out_dir, exist_ok=True)
     summary = []
     for t, path in enumerate(list_images(folder)):
-        r = demo.process_device(jpeg.imread_bgr_device(path, device=demo.device, entropy=decode_entropy), quality, subsampling, entropy)
+        r = demo.process_device(jpeg.imread_bgr_device(path, device=demo.device, entropy=decode_entropy), quality, subsampling, entropy,
+                                seg_png=seg_dir is not None, seg_palette=seg_palette)
         with open(os.path.join(out_dir, os.path.basename(path)), "wb") as f:
             f.write(r["jpeg"])
+        if seg_dir is not None:
+            with open(os.path.join(seg_dir, os.path.splitext(os.path.basename(path))[0] + ".png"), "wb") as f:
+                f.write(r["seg_png"])
         nd = sum(len(d["rois"]) for d in r.get("detections", []) or [])
         nl = sum(len(l) for l in r.get("lanes", []))
         print("frame %d (%s): total process time is %i ms, %d lanes, %d boxes" % (t, os.path.basename(path), r["ms"], nl, nd))
@@ -222,16 +265,21 @@ def parse_size(text: str):
 
 
 def run_video(demo: "Demo", src: str, dst: str, batch: int = 8, quality: int = 95, subsampling: str = "4:2:0", entropy: str = "host",
-              decode_entropy: str = "host", size=None, max_frames: Optional[int] = None) -> List[dict]:
+              decode_entropy: str = "host", size=None, max_frames: Optional[int] = None, seg_dir: Optional[str] = None,
+              seg_palette: Optional[dict] = None) -> List[dict]:
     """--video: a Motion-JPEG AVI -> the annotated Motion-JPEG AVI `dst` of the input's frame rate, plus dst + ".results.json".  The frames
     are taken in file order in groups of `batch` (the last group is smaller), decoded (jpeg.imread_bgr_device), annotated
     (Demo.process_device_batch) and appended to an avi.AviWriter; size = (width, height) of the output frames, the input's without.  A
     zero-length chunk -- "repeat the previous frame" -- writes the previous annotated JPEG again (a leading one is skipped).  The bytes
-    of the next group are read and completed (avi.frame_bytes) while the device works on the current one."""
+    of the next group are read and completed (avi.frame_bytes) while the device works on the current one.  seg_dir: the class map of
+    every output frame goes there as frame_%06d.png, at the INPUT's frame size (a repeated frame writes its map again)."""
     import json
     import mmap
     from . import avi, jpeg
     assert batch >= 1, batch
+    if seg_dir is not None:
+        demo._need_seg()
+        os.makedirs(seg_dir, exist_ok=True)
     summary: List[dict] = []
     with open(src, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as data:
         index = avi.read_index(data)
@@ -259,11 +307,15 @@ def run_video(demo: "Demo", src: str, dst: str, batch: int = 8, quality: int = 9
                 if got != [(in_h, in_w)] * len(got):
                     raise ValueError("%s: frames of %s in a stream whose header says %dx%d" % (src, sorted(set(got)), in_w, in_h))
                 nxt = read(g + 1)                                        # the device is decoding: the host's share of the next group
-                r = demo.process_device_batch(frames, quality, subsampling, entropy, out_hw=(out_h, out_w))
+                r = demo.process_device_batch(frames, quality, subsampling, entropy, out_hw=(out_h, out_w), seg_png=seg_dir is not None,
+                                              seg_palette=seg_palette)
                 B = len(groups[g])
                 while p < len(plan) and plan[p] < done + B:
                     k = plan[p] - done
                     out.write(r["jpeg"][k])
+                    if seg_dir is not None:
+                        with open(os.path.join(seg_dir, "frame_%06d.png" % p), "wb") as f:
+                            f.write(r["seg_png"][k])
                     nd = len(r["detections"][k]["rois"]) if "detections" in r else 0
                     nl = len(r["lanes"][k]) if "lanes" in r else 0
                     summary.append({"frame": p, "file": os.path.basename(src), "ms": r["ms"] / B, "lanes": nl, "boxes": nd})
@@ -306,26 +358,35 @@ def main(argv=None):
     ap.add_argument("--quality", type=int, default=95, help="JPEG quality of the annotated frames (--images, --video)")
     ap.add_argument("--entropy", choices=("host", "device"), default="host", help="where the Huffman stage of the JPEG encode runs (--images, --video)")
     ap.add_argument("--decode-entropy", choices=("host", "device"), default="host", help="where the Huffman stage of the JPEG decode runs (--images, --video)")
+    ap.add_argument("--save-seg", default=None, metavar="DIR", help="also write every frame's predicted class map as an 8-bit label PNG into DIR "
+                    "(--images: <image stem>.png; --video: frame_%%06d.png); needs a configuration with the seg head")
+    ap.add_argument("--seg-palette", action="store_true", help="write the class maps of --save-seg as palette PNGs with the demo's colours")
     ap.add_argument("--count", type=int, default=4)
     ap.add_argument("--out", default=None, help="directory for the annotated JPEGs (--images) or frame_%%04d.npy (blended frames), and results.json; "
                     "the annotated AVI (--video)")
     args = ap.parse_args(argv)
     if args.video and not args.out:
         ap.error("--video needs --out")
+    if args.save_seg and not (args.images or args.video):
+        ap.error("--save-seg needs --images or --video")
     cfgs = yaml.safe_load(open(args.cfg))
+    if args.save_seg and not cfgs["train"]["train_seg"]:
+        raise ValueError("--save-seg: %s runs no seg head (train.train_seg is off)" % args.cfg)
     torch.manual_seed(0)
     demo = Demo(cfgs, args.weights)
     if not args.weights:
         # random initialisation: every anchor scores ~0.5, far more candidates than any real frame has (the device NMS holds 32 768)
         print("no --weights: random initialisation, detection threshold raised to 0.95 for this run")
         demo.det_conf = 0.95
+    palette = seg_palette(demo.colors) if args.seg_palette else None
     if args.images:
         if not args.out:
             ap.error("--images needs --out")
-        return run_images(demo, args.images, args.out, args.quality, entropy=args.entropy, decode_entropy=args.decode_entropy)
+        return run_images(demo, args.images, args.out, args.quality, entropy=args.entropy, decode_entropy=args.decode_entropy,
+                          seg_dir=args.save_seg, seg_palette=palette)
     if args.video:
         return run_video(demo, args.video, args.out, args.batch, args.quality, entropy=args.entropy, decode_entropy=args.decode_entropy, size=args.size,
-                         max_frames=args.max_frames)
+                         max_frames=args.max_frames, seg_dir=args.save_seg, seg_palette=palette)
     frames = np.load(args.frames) if args.frames else synthetic_frames(args.count)
     if args.out:
         os.makedirs(args.out, exist_ok=True)
