@@ -733,6 +733,23 @@ long hn_png_enc_ws_bytes(int N, long max_raw_bytes);
 int hn_png_encode(const void* src, long src_elems, int src_is_int64, const void* desc, int N, int max_out_h, long max_raw_bytes, void* ws,
                   long ws_bytes, void* out, long out_bytes, void* result, hipStream_t stream);
 
+/* The same encode with dynamic-Huffman deflate blocks (png_encode.py huffman="dynamic"; restated in tests/png_enc_dyn_ref.py): arguments,
+ * descriptors, result records and status codes are hn_png_encode's.  The stream: 78 01, then ONE deflate block for every
+ * hn_png_enc_block_chunks() (16) chunks of hn_png_enc_chunk_bytes() raw bytes -- the last block holds the remaining 1..16 chunks and
+ * carries BFINAL -- then the big-endian Adler-32.  The token parse is per chunk, as in hn_png_encode.  Every block is written with the
+ * smaller of two codes: a literal/length Huffman code built from the block's own tokens (at most 15 bits; the header's code-length code at
+ * most 7) with a two-entry distance code (distance 1 and the row distance Wo + 1, one bit each), or the fixed code when the dynamic
+ * block, its header included, is not strictly smaller.  So a stream is never longer than hn_png_encode's, and hn_png_enc_cap_bytes bounds
+ * it.  The workspace is larger (hn_png_enc_dyn_ws_bytes, -1 for arguments out of range): hn_png_encode's layout, then 292 words per chunk
+ * and 440 per block.  One memset of N words and five launches (filter, per-chunk counts, per-block code, scan, emit), no allocation, no
+ * synchronisation; no workgroup waits on another; integer atomics and OR into zeroed words only, so the bytes are deterministic.  A
+ * non-zero status leaves stream_bytes 0 and nothing written to out; no write lands at or past an image's out_cap or outside the
+ * workspace. */
+int hn_png_enc_block_chunks(void);
+long hn_png_enc_dyn_ws_bytes(int N, long max_raw_bytes);
+int hn_png_encode_dyn(const void* src, long src_elems, int src_is_int64, const void* desc, int N, int max_out_h, long max_raw_bytes, void* ws,
+                      long ws_bytes, void* out, long out_bytes, void* result, hipStream_t stream);
+
 /* Baseline JPEG encode, the mirror image (jpeg_encode.py; hn_jpeg_enc.hip, semantics in DESIGN.md 4h): libjpeg's default compressor, all
  * integer.  Device stage for a ragged batch: desc = DEVICE array of N 432-byte JpegEncDesc (offsets into frames / coefs, geometry,
  * quantisation tables in natural order).  frames: packed BGR uint8 H x W x 3 frames (augment.pack's layout; a 1-component image encodes

@@ -1,7 +1,7 @@
 """demo.py of the reference (model/demo.py:52-261) on the HIP path: frame -> pre-processing -> HydraNet forward -> the three decodes.
 
     python -m multitask_hydranet_amd.demo [--cfg cfgs/hydranet_big.yml] [--weights ckpt.pth] --video IN.avi --out OUT.avi [--batch N] [--size WxH] [--max-frames N]
-    python -m multitask_hydranet_amd.demo [--cfg cfgs/hydranet_big.yml] [--weights ckpt.pth] --images DIR --out DIR_VIS [--save-seg DIR_SEG [--seg-palette]]
+    python -m multitask_hydranet_amd.demo [--cfg cfgs/hydranet_big.yml] [--weights ckpt.pth] --images DIR --out DIR_VIS [--save-seg DIR_SEG [--seg-palette] [--seg-huffman dynamic]]
     python -m multitask_hydranet_amd.demo [--cfg cfgs/hydranet_big.yml] [--weights ckpt.pth] [--frames frames.npy] [--out demo_out]
 
 What is kept: the configuration handling (network input size, which heads run, lane codec geometry, colour table), `module.`-prefixed
@@ -23,7 +23,8 @@ the decoded lanes and boxes are returned as data (Demo.process).
 --save-seg DIR (with --images / --video) also keeps what the seg head predicted, not only its colour blend: the arg-max class map the overlay
 is painted from, nearest-resized to the frame's original size and written as an 8-bit label PNG per frame (<image stem>.png, or
 frame_%06d.png for a video) -- the format MultitaskData reads its seg labels from.  Filter and deflate run on the device (png_encode,
-hn_png_enc.hip); --seg-palette writes colour type 3 with the demo's colours instead of grey, the same index bytes."""
+hn_png_enc.hip); --seg-palette writes colour type 3 with the demo's colours instead of grey, the same index bytes; --seg-huffman dynamic
+deflates with a Huffman code per block instead of the fixed one: the same pixels, smaller files."""
 from __future__ import annotations
 
 import argparse
@@ -113,13 +114,14 @@ class Demo:
 
     @torch.no_grad()
     def process_device(self, frames: dict, quality: int = 95, subsampling: str = "4:2:0", entropy: str = "host", seg_png: bool = False,
-                       seg_palette: Optional[dict] = None) -> Dict[str, object]:
+                       seg_palette: Optional[dict] = None, seg_huffman: str = "fixed") -> Dict[str, object]:
         """the same iteration for ONE frame that is already on the device in the packed layout of jpeg.imread_bgr_device, with the
         reference's drawing (demo.py:230, 235, 244) and its cv2.imwrite (demo.py:261): "jpeg" holds the annotated frame's JFIF bytes,
         "visual" the annotated frame in the packed device layout.  The frame is not copied to the host.  entropy: "host" | "device", where
         the Huffman stage of the encode runs (jpeg_encode.encode_batch); the bytes are the same.  seg_png: "seg_png" holds the PNG file
         bytes of the arg-max class map at the frame's original size (png_encode.encode_batch; colour type 3 with seg_palette = {id: (r, g,
-        b)}, grey without); everything else is what the call gives without it."""
+        b)}, grey without; seg_huffman: "fixed" | "dynamic", png_encode's huffman -- the same pixels in a smaller file); everything else is
+        what the call gives without it."""
         from . import draw, jpeg_encode, png_encode
         if seg_png:
             self._need_seg()
@@ -146,7 +148,8 @@ class Demo:
             blended = seg_decode_device(frame, seg, self.colors)
             frames = {"data": blended.view(-1), "offsets": np.zeros(1, np.int64), "shapes": np.array([[org_h, org_w]], np.int64)}
             if seg_png:
-                res["seg_png"] = png_encode.encode_batch(seg, out_sizes=(org_h, org_w), palette=seg_palette, device=self.device)[0]
+                res["seg_png"] = png_encode.encode_batch(seg, out_sizes=(org_h, org_w), palette=seg_palette, device=self.device,
+                                                           huffman=seg_huffman)[0]
         if self.train_detect:
             det = outputs["detection"]
             res["detections"] = net.detectheader.decode(img, det["regression"], det["classification"], det["anchors"], conf_thres=self.det_conf,
@@ -160,7 +163,7 @@ class Demo:
 
     @torch.no_grad()
     def process_device_batch(self, frames: dict, quality: int = 95, subsampling: str = "4:2:0", entropy: str = "host", out_hw=None,
-                             seg_png: bool = False, seg_palette: Optional[dict] = None) -> Dict[str, object]:
+                             seg_png: bool = False, seg_palette: Optional[dict] = None, seg_huffman: str = "fixed") -> Dict[str, object]:
         """process_device for the B frames of a packed batch that all have one size (a video's): one preprocess_bgr and one forward over
         the batch, the lane and box decodes of the batch read back at ONE point (the drawing primitives are built from them on the host),
         one draw_packed per drawing stage, one seg overlay, an optional resize_bgr of the annotated frames to out_hw = (height, width),
@@ -168,7 +171,7 @@ class Demo:
         that frame alone, as long as the forward's arithmetic for an image does not depend on the batch it runs in --
         and "visual" the annotated (and resized) frames in the packed device layout.  Like process_device it paints into `frames`.
         seg_png: "seg_png" holds one PNG file per frame, the arg-max class maps at the frames' ORIGINAL size (out_hw does not apply),
-        encoded for the whole batch in one png_encode.encode_batch."""
+        encoded for the whole batch in one png_encode.encode_batch (seg_huffman: its huffman)."""
         from . import jpeg_encode, png_encode
         if seg_png:
             self._need_seg()
@@ -212,7 +215,8 @@ class Demo:
             blended = seg_decode_device(batch, seg, self.colors)
             frames = {"data": blended.view(-1), "offsets": nbytes * np.arange(B, dtype=np.int64), "shapes": shapes.copy()}
             if seg_png:
-                res["seg_png"] = png_encode.encode_batch(seg, out_sizes=(org_h, org_w), palette=seg_palette, device=self.device)
+                res["seg_png"] = png_encode.encode_batch(seg, out_sizes=(org_h, org_w), palette=seg_palette, device=self.device,
+                                                           huffman=seg_huffman)
         if self.train_detect:
             frames = net.detectheader.display(res["detections"], frames, self.obj_list, org_size, (self.net_w, self.net_h))
         if out_hw is not None and (int(out_hw[0]), int(out_hw[1])) != (org_h, org_w):
@@ -229,7 +233,8 @@ def list_images(folder: str) -> List[str]:
 
 
 def run_images(demo: "Demo", folder: str, out_dir: str, quality: int = 95, subsampling: str = "4:2:0", entropy: str = "host",
-               decode_entropy: str = "host", seg_dir: Optional[str] = None, seg_palette: Optional[dict] = None) -> List[dict]:
+               decode_entropy: str = "host", seg_dir: Optional[str] = None, seg_palette: Optional[dict] = None,
+               seg_huffman: str = "fixed") -> List[dict]:
     """--images: folder of JPEGs -> annotated JPEGs of the same names in out_dir, plus results.json.  entropy / decode_entropy: where the
     Huffman stage of the encode / of the decode runs; the bytes written are the same.  seg_dir: every frame's class map goes there as
     <image stem>.png (Demo.process_device's seg_png)."""
@@ -242,7 +247,7 @@ def run_images(demo: "Demo", folder: str, out_dir: str, quality: int = 95, subsa
     summary = []
     for t, path in enumerate(list_images(folder)):
         r = demo.process_device(jpeg.imread_bgr_device(path, device=demo.device, entropy=decode_entropy), quality, subsampling, entropy,
-                                seg_png=seg_dir is not None, seg_palette=seg_palette)
+                                seg_png=seg_dir is not None, seg_palette=seg_palette, seg_huffman=seg_huffman)
         with open(os.path.join(out_dir, os.path.basename(path)), "wb") as f:
             f.write(r["jpeg"])
         if seg_dir is not None:
@@ -266,7 +271,7 @@ def parse_size(text: str):
 
 def run_video(demo: "Demo", src: str, dst: str, batch: int = 8, quality: int = 95, subsampling: str = "4:2:0", entropy: str = "host",
               decode_entropy: str = "host", size=None, max_frames: Optional[int] = None, seg_dir: Optional[str] = None,
-              seg_palette: Optional[dict] = None) -> List[dict]:
+              seg_palette: Optional[dict] = None, seg_huffman: str = "fixed") -> List[dict]:
     """--video: a Motion-JPEG AVI -> the annotated Motion-JPEG AVI `dst` of the input's frame rate, plus dst + ".results.json".  The frames
     are taken in file order in groups of `batch` (the last group is smaller), decoded (jpeg.imread_bgr_device), annotated
     (Demo.process_device_batch) and appended to an avi.AviWriter; size = (width, height) of the output frames, the input's without.  A
@@ -308,7 +313,7 @@ def run_video(demo: "Demo", src: str, dst: str, batch: int = 8, quality: int = 9
                     raise ValueError("%s: frames of %s in a stream whose header says %dx%d" % (src, sorted(set(got)), in_w, in_h))
                 nxt = read(g + 1)                                        # the device is decoding: the host's share of the next group
                 r = demo.process_device_batch(frames, quality, subsampling, entropy, out_hw=(out_h, out_w), seg_png=seg_dir is not None,
-                                              seg_palette=seg_palette)
+                                              seg_palette=seg_palette, seg_huffman=seg_huffman)
                 B = len(groups[g])
                 while p < len(plan) and plan[p] < done + B:
                     k = plan[p] - done
@@ -361,6 +366,8 @@ def main(argv=None):
     ap.add_argument("--save-seg", default=None, metavar="DIR", help="also write every frame's predicted class map as an 8-bit label PNG into DIR "
                     "(--images: <image stem>.png; --video: frame_%%06d.png); needs a configuration with the seg head")
     ap.add_argument("--seg-palette", action="store_true", help="write the class maps of --save-seg as palette PNGs with the demo's colours")
+    ap.add_argument("--seg-huffman", choices=("fixed", "dynamic"), default=None, help="the deflate code of the --save-seg PNGs: fixed (the default), "
+                    "or dynamic -- a Huffman code per block of 16 chunks, the same pixels in less than half the bytes")
     ap.add_argument("--count", type=int, default=4)
     ap.add_argument("--out", default=None, help="directory for the annotated JPEGs (--images) or frame_%%04d.npy (blended frames), and results.json; "
                     "the annotated AVI (--video)")
@@ -369,6 +376,9 @@ def main(argv=None):
         ap.error("--video needs --out")
     if args.save_seg and not (args.images or args.video):
         ap.error("--save-seg needs --images or --video")
+    if args.seg_huffman and not args.save_seg:
+        ap.error("--seg-huffman needs --save-seg")
+    huffman = args.seg_huffman or "fixed"
     cfgs = yaml.safe_load(open(args.cfg))
     if args.save_seg and not cfgs["train"]["train_seg"]:
         raise ValueError("--save-seg: %s runs no seg head (train.train_seg is off)" % args.cfg)
@@ -383,10 +393,10 @@ def main(argv=None):
         if not args.out:
             ap.error("--images needs --out")
         return run_images(demo, args.images, args.out, args.quality, entropy=args.entropy, decode_entropy=args.decode_entropy,
-                          seg_dir=args.save_seg, seg_palette=palette)
+                          seg_dir=args.save_seg, seg_palette=palette, seg_huffman=huffman)
     if args.video:
         return run_video(demo, args.video, args.out, args.batch, args.quality, entropy=args.entropy, decode_entropy=args.decode_entropy, size=args.size,
-                         max_frames=args.max_frames, seg_dir=args.save_seg, seg_palette=palette)
+                         max_frames=args.max_frames, seg_dir=args.save_seg, seg_palette=palette, seg_huffman=huffman)
     frames = np.load(args.frames) if args.frames else synthetic_frames(args.count)
     if args.out:
         os.makedirs(args.out, exist_ok=True)

@@ -1,7 +1,8 @@
 """PNG label encode on the device (hn_png_enc.hip), the mirror image of png.py: class maps -- the int64 [N, Hs, Ws] mask of
 ops.argmax_channels / the deploy forward, or packed uint8 maps in augment.pack's layout -- are resized to a per-image (Ho, Wo) with cv2's
-INTER_NEAREST index rule, filtered row by row (the five PNG filters, smallest sum of |int8|) and deflated with fixed-Huffman blocks on the
-device; the host only frames the few KB that come back (signature, IHDR, an optional PLTE, one IDAT, IEND, with zlib.crc32).
+INTER_NEAREST index rule, filtered row by row (the five PNG filters, smallest sum of |int8|) and deflated on the device -- with one
+fixed-Huffman block per chunk or, huffman="dynamic", with blocks of 16 chunks whose code is built from their own tokens; the host only
+frames the few KB that come back (signature, IHDR, an optional PLTE, one IDAT, IEND, with zlib.crc32).
 
     files = png_encode.encode_batch(mask, out_sizes=[(1080, 1920)] * n)                 # list of bytes: 8-bit grey PNG files
     files = png_encode.encode_batch(mask, palette={0: (0, 0, 0), 1: (128, 0, 128)})     # colour type 3, the same index bytes
@@ -168,15 +169,31 @@ def _as_source(maps, device):
     return torch.from_numpy(flat).to(dev), True, [tuple(a.shape) for a in arrs], [int(o) for o in offs[:-1]]
 
 
-def encode_streams(maps, out_sizes=None, cap=None, device=None, lean: bool = False) -> dict:
+HUFFMAN = {"fixed": ("hn_png_encode", "hn_png_enc_ws_bytes"), "dynamic": ("hn_png_encode_dyn", "hn_png_enc_dyn_ws_bytes")}
+
+
+def _entry(huffman: str) -> Tuple[str, str]:
+    if huffman not in HUFFMAN:
+        raise ValueError("huffman must be 'fixed' or 'dynamic', not %r" % (huffman,))
+    return HUFFMAN[huffman]
+
+
+def block_chunks() -> int:
+    """chunks per deflate block of huffman="dynamic" streams"""
+    return int(lib().query("hn_png_enc_block_chunks"))
+
+
+def encode_streams(maps, out_sizes=None, cap=None, device=None, lean: bool = False, huffman: str = "fixed") -> dict:
     """the device part, nothing read back: maps -- an int64 (or uint8) tensor [N, Hs, Ws], a packed uint8 dict of augment.pack's layout, or
     a list of H x W integer arrays; out_sizes: one (Ho, Wo) or one per image, the source sizes without; cap: bytes per stream slot (one
     value or one per image, rounded down to a multiple of 4; default: what no stream exceeds, hn_png_enc_cap_bytes -- with lean, at most
     64 KB plus a quarter of the raw size).  -> {"buf": device
     uint8 tensor, the N result records (RESULT_DTYPE) then the stream slots; "rbytes": where the slots start; "offsets" [n + 1]: every
     slot's byte offset behind rbytes; "caps"; "sizes": the (Ho, Wo); "src": (flat tensor, is_int64, shapes, offsets)}.  One launch
-    sequence on the current stream."""
+    sequence on the current stream.  huffman: "fixed" -- one fixed-Huffman block per chunk -- or "dynamic" -- one block per 16 chunks with
+    a code built from its own tokens where that is smaller (hn_png_encode_dyn): never longer, on label maps less than half the bytes."""
     import torch
+    entry, ws_query = _entry(huffman)
     src, is_i64, shapes, soffs = _as_source(maps, device)
     n = len(shapes)
     assert n > 0
@@ -195,12 +212,12 @@ def encode_streams(maps, out_sizes=None, cap=None, device=None, lean: bool = Fal
     desc, ooff, max_h, max_raw = describe(shapes, soffs, sizes, caps)
     rbytes = (n * RESULT_DTYPE.itemsize + 15) // 16 * 16
     with torch.cuda.device(src.device):
-        ws_bytes = int(lib().query("hn_png_enc_ws_bytes", n, max_raw))
+        ws_bytes = int(lib().query(ws_query, n, max_raw))
         assert ws_bytes > 0, (n, max_raw)
         ws = torch.empty((ws_bytes,), device=src.device, dtype=torch.uint8)
         desc_d = torch.from_numpy(desc.view(np.uint8).copy()).to(src.device)
         buf = torch.empty((rbytes + max(int(ooff[-1]), 16),), device=src.device, dtype=torch.uint8)
-        lib().call("hn_png_encode", src.data_ptr(), int(src.numel()), int(is_i64), desc_d.data_ptr(), n, max_h, max_raw, ws.data_ptr(), ws_bytes,
+        lib().call(entry, src.data_ptr(), int(src.numel()), int(is_i64), desc_d.data_ptr(), n, max_h, max_raw, ws.data_ptr(), ws_bytes,
                    buf.data_ptr() + rbytes, max(int(ooff[-1]), 16), buf.data_ptr())
     return {"buf": buf, "rbytes": rbytes, "offsets": ooff, "caps": caps, "sizes": sizes, "src": (src, is_i64, shapes, soffs), "ws": ws}
 
@@ -211,14 +228,14 @@ def _default_caps(sizes) -> List[int]:
     return [min(capacity(h * (1 + w)), ((1 << 16) + h * (1 + w) // 4) // 4 * 4) for h, w in sizes]
 
 
-def encode_batch(maps, out_sizes=None, palette=None, cap=None, device=None) -> List[bytes]:
+def encode_batch(maps, out_sizes=None, palette=None, cap=None, device=None, huffman: str = "fixed") -> List[bytes]:
     """class maps -> whole PNG files (bit depth 8, colour type 0, or 3 with palette = {id: (r, g, b)}; non-interlaced, one IDAT).  One
     launch sequence (encode_streams) and ONE copy of the result records and the streams through a pinned staging buffer; an image whose
     stream outgrew its capacity (status "full") is encoded on the host (host_stream), that image only.  A class id outside 0..255 raises
-    ValueError; a record the device refuses is a bug in the caller's buffers and raises RuntimeError."""
+    ValueError; a record the device refuses is a bug in the caller's buffers and raises RuntimeError.  huffman: see encode_streams."""
     import torch
     from .jpeg_encode import _staging
-    st = encode_streams(maps, out_sizes, cap, device, lean=True)
+    st = encode_streams(maps, out_sizes, cap, device, lean=True, huffman=huffman)
     buf, rbytes, ooff, sizes = st["buf"], st["rbytes"], st["offsets"], st["sizes"]
     n = len(sizes)
     with torch.cuda.device(buf.device):
@@ -237,7 +254,7 @@ def encode_batch(maps, out_sizes=None, palette=None, cap=None, device=None) -> L
         elif int(res["status"][i]) == ST_RANGE:
             raise ValueError("image %d: a class id outside 0..255 has no 8-bit PNG" % i)
         else:
-            raise RuntimeError("hn_png_encode: image %d: %s" % (i, STATUS.get(int(res["status"][i]), int(res["status"][i]))))
+            raise RuntimeError("%s: image %d: %s" % (_entry(huffman)[0], i, STATUS.get(int(res["status"][i]), int(res["status"][i]))))
         files.append(assemble(wo, ho, stream, palette))
     return files
 
@@ -249,13 +266,13 @@ def source_map(src, i: int) -> np.ndarray:
     return flat[offs[i]:offs[i] + hs * ws].view(hs, ws).cpu().numpy()
 
 
-def imwrite(path, class_map, out_size=None, palette=None, device=None) -> None:
+def imwrite(path, class_map, out_size=None, palette=None, device=None, huffman: str = "fixed") -> None:
     """one class map (H x W integer array, or a [H, W] / [1, H, W] tensor) -> one PNG file"""
-    blobs = encode_batch(class_map, out_size, palette, device=device)
+    blobs = encode_batch(class_map, out_size, palette, device=device, huffman=huffman)
     assert len(blobs) == 1
     with open(path, "wb") as f:
         f.write(blobs[0])
 
 
 __all__ = ["encode_batch", "encode_streams", "assemble", "imwrite", "host_stream", "encode_host", "resize_nearest", "filter_rows", "describe",
-           "capacity", "chunk_bytes", "source_map", "STATUS", "DESC_DTYPE", "RESULT_DTYPE"]
+           "capacity", "chunk_bytes", "block_chunks", "source_map", "STATUS", "DESC_DTYPE", "RESULT_DTYPE"]
