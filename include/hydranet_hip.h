@@ -616,6 +616,37 @@ int hn_weighted_sum(const void* const* xs, const float* w, const float* gw, cons
 int hn_adam_step(const long* jobs, const int* block_job, long total_blocks, double lr, double beta1, double beta2, double eps,
                  double weight_decay, long step, hipStream_t stream);
 
+/* Global gradient norm, clipping coefficient and a non-finite step guard, decided on the device (no host synchronisation, no allocation,
+ * graph-capturable; three launches, none of whose workgroups waits on another).  jobs / block_job / total_blocks are hn_adam_step's tables
+ * (n_jobs rows; only g, numel and first_block are read).  record (DEVICE, 32 bytes, zeroed once by the caller):
+ *   word 0 float norm = (float)sqrt(total)       word 1 float coef       word 2 int skip (bit mask)       word 3 int steps
+ *   word 4 int skipped       word 5 int skipped_consecutive       words 6-7 pad
+ * Reduction order: a thread adds the squares of its 4 elements left to right in fp32 (products rounded, no fused multiply-add; the same
+ * instruction stream for 16-byte vector loads and element loads); a block's value is a fixed tree over its 256 thread values (DPP inside
+ * each wave, then (w0 + w1) + (w2 + w3) through LDS); a job's sum is formed in double by one workgroup (thread t adds blocks t, t + 256,
+ * ... in ascending order, then a fixed 256-leaf tree), and the total over the jobs the same way.  The order depends on the job table
+ * alone: no floating-point atomics, no dependence on which workgroup finishes first.
+ * coef = min(1.0f, (float)max_norm / (norm + 1e-6f)) in rounded fp32 operations (torch.nn.utils.clip_grad_norm_; a NaN stays a NaN as under
+ * torch.clamp); exactly 1.0f when max_norm <= 0.
+ * skip: bit 1 = the total is not finite or exceeds fp32's range, bit 2 = one of `losses` is not finite (both only when flags & 1; without
+ * it a non-finite norm just flows through the formula, as in torch), bit 4 = one of `words` is non-zero (always).  steps += 1 on every
+ * call; skip != 0: skipped += 1, skipped_consecutive += 1; else skipped_consecutive = 0.
+ * losses: HOST array of n_losses <= 8 DEVICE fp32 scalars; words: HOST array of n_words <= 4 DEVICE int32 words (both read at launch
+ * time into the kernel's arguments); ws: DEVICE, 16-byte aligned, >= hn_grad_guard_ws_bytes(total_blocks, n_jobs) bytes; job_sq (optional,
+ * DEVICE double [n_jobs]) receives the per-job sums of squares.  Writes go to ws, job_sq and record only.
+ * hn_grad_guard_ws_bytes: -1 unless 1 <= n_jobs <= total_blocks <= 2^31 - 1. */
+long hn_grad_guard_ws_bytes(long total_blocks, long n_jobs);
+int hn_grad_guard(const long* jobs, const int* block_job, long total_blocks, long n_jobs, double max_norm, int flags,
+                  const void* const* losses, int n_losses, const void* const* words, int n_words, void* ws, long ws_bytes, double* job_sq,
+                  void* record, hipStream_t stream);
+
+/* hn_adam_step that obeys `record` (written by hn_grad_guard earlier on the same stream): every thread reads it first; skip != 0: the
+ * kernel returns before its first store (p, m, v untouched bit for bit); otherwise the gradient is multiplied by coef (rounded) before the
+ * weight-decay term, which is clipping in place and then stepping -- but the gradient tensors are not written.  coef == 1.0f gives
+ * hn_adam_step's result bit for bit (one shared kernel body). */
+int hn_adam_step_guarded(const long* jobs, const int* block_job, long total_blocks, double lr, double beta1, double beta2, double eps,
+                         double weight_decay, long step, const void* record, hipStream_t stream);
+
 /* Many contiguous tensors copied in one launch (the gather of a gradient bucket before its all-reduce, train.py:130-137's DDP buckets):
  * jobs (DEVICE) = n x 4 int64 {src, dst, numel, first_block}, block = 256 threads x 4 elements, block_job (DEVICE int32) = job of every
  * block; kind 0: fp32 -> fp32, 1: fp32 -> bf16 (reduced-precision payload), 2: bf16 -> fp32. */

@@ -1183,8 +1183,20 @@ extern "C" int hn_weighted_sum(const void* const* xs, const float* w, const floa
 // Same operation order as torch's single-tensor formula (lerp for the first moment, mul + addcmul for the second, sqrt / bias2_sqrt +
 // eps, addcdiv), with explicitly rounded steps (no fused multiply-add), so that it tracks torch.optim.Adam to the last bit or two.
 // ---------------------------------------------------------------------------------------------------------------------------------
+// The step's decision, written by hn_grad_guard (below) and obeyed by hn_adam_step_guarded: 32 bytes on the device, zeroed once by the caller.
+struct GuardRecord { float norm, coef; int skip, steps, skipped, skipped_consecutive, pad[2]; };
+
+// GUARDED = false is hn_adam_step.  GUARDED = true (hn_adam_step_guarded) reads the record first: a flagged step returns before its first
+// store; otherwise the gradient is scaled by the clipping coefficient before the weight-decay term, i.e. clip in place, then step --
+// without writing the gradient.  x * 1.0f == x, so coef == 1.0f gives hn_adam_step's bits.
+template <bool GUARDED>
 __global__ __launch_bounds__(256) void adam_step_kernel(const long* jobs, const int* block_job, float lr_over_bc1, float w1, float b2, float w2,
-                                                        float eps, float wd, float bc2_sqrt) {
+                                                        float eps, float wd, float bc2_sqrt, const GuardRecord* rec) {
+    float coef = 1.f;
+    if constexpr (GUARDED) {
+        if (rec->skip != 0) return;
+        coef = rec->coef;
+    }
     const long* jb = jobs + (long)block_job[blockIdx.x] * 6;
     float* p = reinterpret_cast<float*>(jb[0]);
     const float* g = reinterpret_cast<const float*>(jb[1]);
@@ -1194,6 +1206,7 @@ __global__ __launch_bounds__(256) void adam_step_kernel(const long* jobs, const 
     const long i0 = (((long)blockIdx.x - jb[5]) * 256 + threadIdx.x) * 4;
     if (i0 >= n) return;
     auto one = [&](float pv, float gv, float& mv, float& vv) {
+        if constexpr (GUARDED) gv = __fmul_rn(gv, coef);                               // clip_grad_norm_'s grad.mul_(clip_coef), not stored
         if (wd != 0.f) gv = __fadd_rn(gv, __fmul_rn(wd, pv));
         mv = __fadd_rn(mv, __fmul_rn(w1, __fsub_rn(gv, mv)));                          // exp_avg.lerp_(grad, 1 - beta1)
         vv = __fadd_rn(__fmul_rn(vv, b2), __fmul_rn(w2, __fmul_rn(gv, gv)));           // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
@@ -1229,14 +1242,148 @@ __global__ __launch_bounds__(256) void adam_step_kernel(const long* jobs, const 
     }
 }
 
-extern "C" int hn_adam_step(const long* jobs, const int* block_job, long total_blocks, double lr, double beta1, double beta2, double eps,
-                            double weight_decay, long step, hipStream_t st) {
-    HN_CHECK_ARG(jobs && block_job && total_blocks > 0 && step >= 1 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0);
+static int adam_launch(const long* jobs, const int* block_job, long total_blocks, double lr, double beta1, double beta2, double eps,
+                       double weight_decay, long step, const GuardRecord* rec, hipStream_t st) {
     // the scalars as torch forms them from Python doubles: 1 - beta, 1 - beta ** step, lr / bias_correction1, sqrt(bias_correction2) in
     // double, rounded to fp32 once (1.0f - 0.999f differs from float(0.001) by 1.3e-5)
     const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)total_blocks), dim3(256), 0, st, jobs, block_job, (float)(lr / bc1), (float)(1.0 - beta1),
-                       (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)sqrt(bc2));
+    auto kern = rec ? adam_step_kernel<true> : adam_step_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)total_blocks), dim3(256), 0, st, jobs, block_job, (float)(lr / bc1), (float)(1.0 - beta1),
+                       (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)sqrt(bc2), rec);
+    HN_LAUNCH_CHECK();
+}
+extern "C" int hn_adam_step(const long* jobs, const int* block_job, long total_blocks, double lr, double beta1, double beta2, double eps,
+                            double weight_decay, long step, hipStream_t st) {
+    HN_CHECK_ARG(jobs && block_job && total_blocks > 0 && step >= 1 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0);
+    return adam_launch(jobs, block_job, total_blocks, lr, beta1, beta2, eps, weight_decay, step, nullptr, st);
+}
+/* hn_adam_step that obeys the record hn_grad_guard wrote earlier on the same stream; the gradient tensors are read, never written */
+extern "C" int hn_adam_step_guarded(const long* jobs, const int* block_job, long total_blocks, double lr, double beta1, double beta2, double eps,
+                                    double weight_decay, long step, const void* record, hipStream_t st) {
+    HN_CHECK_ARG(jobs && block_job && total_blocks > 0 && step >= 1 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && record);
+    return adam_launch(jobs, block_job, total_blocks, lr, beta1, beta2, eps, weight_decay, step, (const GuardRecord*)record, st);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Global gradient norm + the step's decision, on the device (torch.nn.utils.clip_grad_norm_'s coefficient; a skip mask in place of the
+// reference's host-side sys.exit() guard).  Three launches over the job tables of hn_adam_step, no atomics, no workgroup waits on another:
+//   1. grad_sq_block_kernel: one fp32 value per 1024-element block.  Thread: g0*g0 + g1*g1 + g2*g2 + g3*g3 left to right, every product
+//      and sum rounded (absent elements are +0, which adds exactly); block: wave_sum's fixed DPP tree, then (w0 + w1) + (w2 + w3).
+//   2. grad_sq_job_kernel: one workgroup per job, in double: thread t adds the job's blocks t, t + 256, ... in ascending order, then
+//      block_sum_f64's fixed tree.  3. grad_guard_final_kernel: one workgroup adds the job sums the same way and writes the record.
+// The order of every addition is a function of the job table alone, so equal gradients give equal bits, run after run and whether the
+// gradients are separate allocations or views at odd offsets of a bucket.
+// ---------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void grad_sq_block_kernel(const long* jobs, const int* block_job, float* block_sq) {
+    __shared__ float red[4];
+    const long* jb = jobs + (long)block_job[blockIdx.x] * 6;
+    const float* g = reinterpret_cast<const float*>(jb[1]);
+    const long n = jb[4];
+    const long i0 = (((long)blockIdx.x - jb[5]) * 256 + threadIdx.x) * 4;
+    // ONE arithmetic instruction stream for both operand forms, as in adam_step_kernel
+    float gv[4] = {0.f, 0.f, 0.f, 0.f};
+    if (i0 + 4 <= n && (reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+        const f32x4 b = *reinterpret_cast<const f32x4*>(g + i0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) gv[k] = b[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (i0 + k < n) gv[k] = g[i0 + k];
+    }
+    float s = __fmul_rn(gv[0], gv[0]);
+#pragma unroll
+    for (int k = 1; k < 4; ++k) s = __fadd_rn(s, __fmul_rn(gv[k], gv[k]));
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) block_sq[blockIdx.x] = __fadd_rn(__fadd_rn(red[0], red[1]), __fadd_rn(red[2], red[3]));
+}
+
+// sum of 256 doubles in a fixed tree (xor butterflies inside each wave, then the four waves through LDS); thread 0's value is used
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = __dadd_rn(v, __shfl_xor(v, o));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return __dadd_rn(__dadd_rn(red[0], red[1]), __dadd_rn(red[2], red[3]));
+}
+
+__global__ __launch_bounds__(256) void grad_sq_job_kernel(const long* jobs, const float* block_sq, double* job_sum, double* job_sq) {
+    __shared__ double red[4];
+    const long* jb = jobs + (long)blockIdx.x * 6;
+    const long nb = (jb[4] + 1023) / 1024;
+    const float* bs = block_sq + jb[5];
+    double s = 0.0;
+    for (long b = threadIdx.x; b < nb; b += 256) s = __dadd_rn(s, (double)bs[b]);
+    s = block_sum_f64(s, red);
+    if (threadIdx.x == 0) {
+        job_sum[blockIdx.x] = s;
+        if (job_sq) job_sq[blockIdx.x] = s;
+    }
+}
+
+struct GuardArgs {
+    const double* job_sum;
+    long n_jobs;
+    float max_norm;
+    int flags, n_losses, n_words;
+    const float* losses[8];
+    const int* words[4];
+    GuardRecord* rec;
+};
+__global__ __launch_bounds__(256) void grad_guard_final_kernel(GuardArgs a) {
+    __shared__ double red[4];
+    double s = 0.0;
+    for (long j = threadIdx.x; j < a.n_jobs; j += 256) s = __dadd_rn(s, a.job_sum[j]);
+    s = block_sum_f64(s, red);
+    if (threadIdx.x != 0) return;
+    const float norm = (float)sqrt(s);
+    float coef = 1.0f;
+    if (a.max_norm > 0.f) {
+        // clip_grad_norm_: clamp(max_norm / (total_norm + 1e-6), max = 1.0); a NaN stays a NaN, as torch.clamp leaves it
+        const float c = __fdiv_rn(a.max_norm, __fadd_rn(norm, 1e-6f));
+        coef = c < 1.0f || c != c ? c : 1.0f;
+    }
+    int skip = 0;
+    if (a.flags & 1) {
+        if (!(s <= (double)__FLT_MAX__)) skip |= 1;                    // NaN, inf, or past fp32's range (torch's fp32 norm is inf there)
+        for (int i = 0; i < a.n_losses; ++i)
+            if (!(fabsf(a.losses[i][0]) <= __FLT_MAX__)) skip |= 2;
+    }
+    for (int i = 0; i < a.n_words; ++i)
+        if (a.words[i][0] != 0) skip |= 4;
+    GuardRecord* r = a.rec;
+    r->norm = norm;
+    r->coef = coef;
+    r->skip = skip;
+    r->steps += 1;
+    if (skip) { r->skipped += 1; r->skipped_consecutive += 1; }
+    else r->skipped_consecutive = 0;
+}
+
+static inline long align16(long x) { return (x + 15) & ~15L; }
+extern "C" long hn_grad_guard_ws_bytes(long total_blocks, long n_jobs) {
+    if (total_blocks < 1 || total_blocks > 0x7fffffffL || n_jobs < 1 || n_jobs > total_blocks) return -1;
+    return align16(total_blocks * 4) + align16(n_jobs * 8);
+}
+extern "C" int hn_grad_guard(const long* jobs, const int* block_job, long total_blocks, long n_jobs, double max_norm, int flags,
+                             const void* const* losses, int n_losses, const void* const* words, int n_words, void* ws, long ws_bytes,
+                             double* job_sq, void* record, hipStream_t st) {
+    const long need = hn_grad_guard_ws_bytes(total_blocks, n_jobs);
+    HN_CHECK_ARG(jobs && block_job && need > 0 && ws && ws_bytes >= need && (reinterpret_cast<uintptr_t>(ws) & 15) == 0 && record &&
+                 (reinterpret_cast<uintptr_t>(record) & 3) == 0 && max_norm == max_norm && n_losses >= 0 && n_losses <= 8 && n_words >= 0 &&
+                 n_words <= 4 && (n_losses == 0 || losses) && (n_words == 0 || words));
+    GuardArgs a = {};
+    for (int i = 0; i < n_losses; ++i) { HN_CHECK_ARG(losses[i]); a.losses[i] = (const float*)losses[i]; }
+    for (int i = 0; i < n_words; ++i) { HN_CHECK_ARG(words[i]); a.words[i] = (const int*)words[i]; }
+    float* block_sq = (float*)ws;
+    double* job_sum = (double*)((char*)ws + align16(total_blocks * 4));
+    a.job_sum = job_sum; a.n_jobs = n_jobs; a.max_norm = (float)max_norm; a.flags = flags; a.n_losses = n_losses; a.n_words = n_words;
+    a.rec = (GuardRecord*)record;
+    hipLaunchKernelGGL(grad_sq_block_kernel, dim3((unsigned)total_blocks), dim3(256), 0, st, jobs, block_job, block_sq);
+    hipLaunchKernelGGL(grad_sq_job_kernel, dim3((unsigned)n_jobs), dim3(256), 0, st, jobs, (const float*)block_sq, job_sum, job_sq);
+    hipLaunchKernelGGL(grad_guard_final_kernel, dim3(1), dim3(256), 0, st, a);
     HN_LAUNCH_CHECK();
 }
 

@@ -37,6 +37,13 @@ def xstage_status(dev) -> int:
     return int(xstage_ws(dev)[1].item())
 
 
+def xstage_status_word(dev):
+    """the status word itself (int32 view on the device, no synchronisation) for consumers that act on it inside the stream -- the
+    optimizer's step guard; None while the device has no workspace (no persistent launch has run there)"""
+    w = _WS.get(dev.index if dev.index is not None else torch.cuda.current_device())
+    return None if w is None else w[1]
+
+
 def xstage_assert_ok(dev=None):
     """raise if a persistent launch on `dev` (default: every device that has a workspace) ended with an expired wait (synchronises).  The
     launches themselves never hang: a wait that expires raises the status word and the workgroups retire, leaving invalid outputs -- callers
@@ -219,4 +226,4 @@ def xstage_apply(x, group, eps, momentum, params):
 
 
 __all__ = ["XSTAGE", "XSTAGE_BWD", "XStageFn", "xstage_apply", "xstage_ok", "xstage_forward_raw", "xstage_backward_raw", "xstage_ws",
-           "xstage_status", "xstage_assert_ok", "PER_BLOCK"]
+           "xstage_status", "xstage_status_word", "xstage_assert_ok", "PER_BLOCK"]

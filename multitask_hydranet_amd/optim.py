@@ -5,9 +5,15 @@ tensors: the foreach implementation issues ~10 multi-tensor launches and takes 3
 forward + loss + backward.  One pass over (p, g, m, v) moves 1.2 GB: ~0.35 ms.  Same update rule, same state layout (`step`, `exp_avg`,
 `exp_avg_sq` per parameter -- state_dict() / load_state_dict() are interchangeable with torch.optim.Adam's), same operation order (so it tracks torch's result to
 the last bit or two of fp32); LR schedulers work on `param_groups[i]["lr"]` as usual.  fp32 CUDA parameters only; not amsgrad / maximize.
+
+Opt-in, decided on the device with no host synchronisation (hn_grad_guard + hn_adam_step_guarded, include/hydranet_hip.h):
+`max_grad_norm` = torch.nn.utils.clip_grad_norm_ over every parameter that has a gradient, in every param group; `skip_nonfinite` = a step
+whose gradient norm (or one of the `losses` handed to step()) is not finite leaves parameters and moments untouched.  With both off, step()
+issues exactly the launches it always did.
 """
 from __future__ import annotations
 
+import ctypes
 import weakref
 
 import torch
@@ -17,12 +23,50 @@ from .ops.core import bump_mutation_epoch, mutation_cells
 
 
 class Adam(torch.optim.Optimizer):
-    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0):
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, max_grad_norm=None,
+                 skip_nonfinite: bool = False):
+        """max_grad_norm: clip the global L2 norm of all gradients to it (None or <= 0: off).  The clipping coefficient is applied inside
+        the Adam launch: the gradient tensors themselves are NOT modified (no extra pass over them), `p.grad` after step() is what backward
+        left.  skip_nonfinite: a non-finite gradient norm or loss skips the step on the device.  On a skipped step the per-parameter
+        `step` count (host side; the bias corrections are computed from it on the host in double) and any LR scheduler still advance --
+        torch's GradScaler-style skip would not bump them."""
         if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or lr < 0.0 or eps < 0.0 or weight_decay < 0.0:
             raise ValueError("invalid Adam hyper-parameter")
+        if max_grad_norm is not None and max_grad_norm != max_grad_norm:
+            raise ValueError("invalid Adam hyper-parameter")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        self._plans = {}                # (group index, step value) -> (pointer signature, jobs, block_job, blocks)
+        self._plans = {}                # (group index, step value) -> (pointer signature, jobs, block_job, blocks, parameters)
         self._fast = {}                 # group index -> (gradient tensors of the last step, shared step scalar, plan)
+        self.max_grad_norm = float(max_grad_norm) if max_grad_norm is not None and max_grad_norm > 0 else None
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._guard_plan = None         # (plans of the last guarded step, jobs, block_job, blocks, n_jobs, workspace)
+        self._record = None             # 8 int32 words on the device: hn_grad_guard's record
+        self.grad_sq_by_param = None    # device double [n]: sum of squares of every gradient of the last guarded step (see guard_params)
+        self.guard_params = []          # the parameters grad_sq_by_param's entries belong to, in order
+
+    @property
+    def guarded(self) -> bool:
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    @property
+    def guard_record(self):
+        """hn_grad_guard's record on the device (int32 [8]; words 0 and 1 hold fp32 bits): norm, coef, skip, steps, skipped,
+        skipped_consecutive, pad, pad.  None when neither option is on.  The counters are not part of state_dict()."""
+        if self._record is None and self.guarded:
+            dev = next(p.device for g in self.param_groups for p in g["params"])
+            self._record = torch.zeros((8,), dtype=torch.int32, device=dev)
+        return self._record
+
+    def grad_guard_record(self) -> dict:
+        """the record as a dict (this call synchronises): norm, coef of the last step, its skip mask (1: gradient norm not finite, 2: a
+        loss not finite, 4: a guard word raised), and the counters since construction"""
+        rec = self.guard_record
+        if rec is None:
+            raise RuntimeError("multitask_hydranet_amd.optim.Adam: neither max_grad_norm nor skip_nonfinite is set")
+        host = rec.cpu()
+        norm, coef = host[:2].view(torch.float32).tolist()
+        skip, steps, skipped, consecutive = host[2:6].tolist()
+        return dict(norm=norm, coef=coef, skip=skip, steps=steps, skipped=skipped, skipped_consecutive=consecutive)
 
     def state_dict(self):
         """torch.optim.Adam's layout.  Internally all parameters of a cohort share ONE host `step` scalar (one increment per step instead of
@@ -37,10 +81,15 @@ class Adam(torch.optim.Optimizer):
         super().load_state_dict(state_dict)
         self._plans.clear()
         self._fast.clear()
+        self._guard_plan = None
+
+    def __getstate__(self):
+        return {**super().__getstate__(), "max_grad_norm": self.max_grad_norm, "skip_nonfinite": self.skip_nonfinite}
 
     def __setstate__(self, state):
         super().__setstate__(state)
-        self._plans, self._fast = {}, {}
+        self._plans, self._fast, self._guard_plan = {}, {}, None
+        self._record, self.grad_sq_by_param, self.guard_params = None, None, []    # (a copy counts its own steps)
 
     def _plan(self, key, ps):
         sig = tuple((p.data_ptr(), p.grad.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr()) for p in ps)
@@ -55,31 +104,77 @@ class Adam(torch.optim.Optimizer):
             owner += [i] * nb
             blk += nb
         dev = ps[0].device
-        pl = (sig, torch.tensor(rows, dtype=torch.int64).to(dev), torch.tensor(owner, dtype=torch.int32).to(dev), blk)
+        pl = (sig, torch.tensor(rows, dtype=torch.int64).to(dev), torch.tensor(owner, dtype=torch.int32).to(dev), blk, list(ps))
         self._plans[key] = pl
         return pl
 
+    def _run_guard(self, plans, losses, guard_words):
+        """ONE hn_grad_guard over the gradients of every launch of this step (the norm is global, as clip_grad_norm_'s is).  A single
+        launch's tables serve as they are; several (param groups, step cohorts) are concatenated once and cached while the plans live."""
+        gd = self._guard_plan
+        if gd is None or len(gd[0]) != len(plans) or any(a is not b for a, b in zip(gd[0], plans)):
+            if len(plans) == 1:
+                _, jobs, owner, blocks, ps = plans[0]
+            else:
+                jobs, owner, ps, blocks, nj = [], [], [], 0, 0
+                for _, j, o, b, q in plans:
+                    j = j.clone()
+                    j[:, 5] += blocks
+                    jobs.append(j)
+                    owner.append(o + nj)
+                    ps += q
+                    blocks += b
+                    nj += len(q)
+                jobs, owner = torch.cat(jobs), torch.cat(owner)
+            nbytes = lib().query("hn_grad_guard_ws_bytes", blocks, len(ps))
+            if nbytes < 0:
+                raise RuntimeError("multitask_hydranet_amd.optim.Adam: gradient tables out of hn_grad_guard's range")
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=jobs.device)
+            self.grad_sq_by_param = torch.zeros((len(ps),), dtype=torch.float64, device=jobs.device)
+            self.guard_params = ps
+            gd = self._guard_plan = (list(plans), jobs, owner, blocks, len(ps), ws)
+        _, jobs, owner, blocks, nj, ws = gd
+        ls = [t for t in (losses or ()) if t is not None]
+        ws_ = [t for t in (guard_words or ()) if t is not None]
+        for t in ls:
+            if not (t.is_cuda and t.dtype == torch.float32 and t.numel() == 1):
+                raise RuntimeError("multitask_hydranet_amd.optim.Adam.step: losses are fp32 device scalars")
+        for t in ws_:
+            if not (t.is_cuda and t.dtype == torch.int32 and t.numel() == 1):
+                raise RuntimeError("multitask_hydranet_amd.optim.Adam.step: guard_words are int32 device words")
+        la = (ctypes.c_void_p * max(len(ls), 1))(*[t.data_ptr() for t in ls])
+        wa = (ctypes.c_void_p * max(len(ws_), 1))(*[t.data_ptr() for t in ws_])
+        lib().call("hn_grad_guard", jobs.data_ptr(), owner.data_ptr(), blocks, nj, self.max_grad_norm or 0.0, 1 if self.skip_nonfinite else 0,
+                   ctypes.addressof(la), len(ls), ctypes.addressof(wa), len(ws_), ws.data_ptr(), ws.numel(), self.grad_sq_by_param.data_ptr(),
+                   self.guard_record.data_ptr())
+
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, *, losses=None, guard_words=None):
+        """losses: fp32 device scalars whose finiteness the guard checks (skip_nonfinite); guard_words: int32 device words, a non-zero one
+        skips the step (whenever either option is on).  Both need max_grad_norm or skip_nonfinite."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        guarded = self.guarded
+        if not guarded and (losses or guard_words):
+            raise ValueError("multitask_hydranet_amd.optim.Adam.step: losses / guard_words need max_grad_norm or skip_nonfinite")
         # hn_adam_step writes the parameters through raw pointers: eval-mode caches keyed on `_version` are stale -- those of the modules that own
         # these parameters (the owner cells are collected once per parameter list, not per step)
         sig = tuple(len(g["params"]) for g in self.param_groups)
         if getattr(self, "_mut_sig", None) != sig:
             self._mut_sig, self._mut_cells = sig, mutation_cells([p for g in self.param_groups for p in g["params"]])
         bump_mutation_epoch(self._mut_cells)
+        launches = []                   # (plan, lr, beta1, beta2, eps, weight decay, step) in issue order
         for gi, group in enumerate(self.param_groups):
             b1, b2 = group["betas"]
+            hyper = (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]))
             fast = self._fast.get(gi)
             if fast is not None and len(fast[0]) == len(group["params"]) and all((p.grad is None) if g is None else (p.grad is g()) for p, g in zip(group["params"], fast[0])):
                 # the same gradient tensors as last time (a captured step rewrites them in place): no per-parameter work on the host
-                _, step_t, (_, jobs, owner, blocks) = fast
+                _, step_t, plan = fast
                 step_t += 1
-                lib().call("hn_adam_step", jobs.data_ptr(), owner.data_ptr(), blocks, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                           float(group["weight_decay"]), int(step_t))
+                launches.append((plan, *hyper, int(step_t)))
                 continue
             by_step = {}
             for p in group["params"]:
@@ -100,9 +195,31 @@ class Adam(torch.optim.Optimizer):
                 for p in ps:
                     self.state[p]["step"] = shared
                 plan = self._plan((gi, len(by_step) > 1 and t), ps)
-                lib().call("hn_adam_step", plan[1].data_ptr(), plan[2].data_ptr(), plan[3], float(group["lr"]), float(b1), float(b2),
-                           float(group["eps"]), float(group["weight_decay"]), t + 1)
+                launches.append((plan, *hyper, t + 1))
                 if len(by_step) == 1:
                     # weak references: never keep a dropped gradient alive (its address could not be reused by the next backward)
                     self._fast[gi] = ([None if p.grad is None else weakref.ref(p.grad) for p in group["params"]], shared, plan)
+        if guarded and launches:
+            self._run_guard([l[0] for l in launches], losses, guard_words)
+        for plan, *args in launches:
+            if guarded:
+                lib().call("hn_adam_step_guarded", plan[1].data_ptr(), plan[2].data_ptr(), plan[3], *args, self._record.data_ptr())
+            else:
+                lib().call("hn_adam_step", plan[1].data_ptr(), plan[2].data_ptr(), plan[3], *args)
         return loss
+
+
+def grad_norms_by_prefix(optimizer: Adam, named_parameters, prefixes):
+    """per-submodule gradient norms of the optimizer's last guarded step (the multitask-balance view: prefixes such as "backbone", "neck",
+    "segheader", "detectheader", "laneheader") -> {prefix: device double scalar}, from grad_sq_by_param; no synchronisation.  A prefix
+    matches the parameter names that equal it or start with it + "."."""
+    if optimizer.grad_sq_by_param is None:
+        raise RuntimeError("grad_norms_by_prefix: the optimizer has not run a guarded step (max_grad_norm / skip_nonfinite)")
+    index = {id(p): i for i, p in enumerate(optimizer.guard_params)}
+    named = [(n, index[id(p)]) for n, p in named_parameters if id(p) in index]
+    sq = optimizer.grad_sq_by_param
+    out = {}
+    for pre in prefixes:
+        idx = [i for n, i in named if n == pre or n.startswith(pre + ".")]
+        out[pre] = sq[torch.tensor(idx, dtype=torch.long, device=sq.device)].sum().sqrt() if idx else torch.zeros((), dtype=sq.dtype, device=sq.device)
+    return out

@@ -15,6 +15,7 @@ Launch for N GPUs of one node:  python -m torch.distributed.run --nproc-per-node
 from __future__ import annotations
 
 import os
+import sys
 from typing import Dict, Iterable, Optional
 
 import torch
@@ -62,7 +63,7 @@ def run_training(trainer: "HydraTrainer", valid_every_epoch: bool = True, log=pr
     log("============== finish training ==============")
 
 
-from .ops.xstage import xstage_assert_ok as K_xstage_assert_ok
+from .ops.xstage import xstage_assert_ok as K_xstage_assert_ok, xstage_status_word as K_xstage_status_word
 
 
 class HydraTrainer:
@@ -75,7 +76,10 @@ class HydraTrainer:
         appears, ddp.capture_exchange_step -- the form bench.py times; other backends, whose collectives cannot be captured: the graph holds
         forward + loss + backward and the buckets are exchanged right after each replay).
         force_distribute: run the data-parallel machinery (process group, bucketed all-reduce, in-graph exchange) at world size 1 too --
-        the N > 1 code path on a single GPU (tests; the average over one rank is the identity)."""
+        the N > 1 code path on a single GPU (tests; the average over one rank is the identity).
+        cfgs["train"]["grad_clip_norm"] / ["skip_nonfinite"] (optional, hip_adam only): global-norm clipping and a non-finite step guard,
+        decided on the device inside the Adam step (optim.Adam).  With skip_nonfinite the reference's host-side divergence guard
+        (HydraNet.check_finite) is off: a bad batch is skipped, and train_one_epoch ends the run only when a whole print interval was."""
         self.cfgs = cfgs
         self.capture_step = capture_step
         self._cap = None                       # (shape key, graph, static batch, static loss dict)
@@ -85,6 +89,12 @@ class HydraTrainer:
         t = cfgs["train"]
         self.train_detect, self.train_seg, self.train_lane = t["train_detect"], t["train_seg"], t["train_lane"]
         self.print_interval = t.get("print_interval", 10)
+        # train.grad_clip_norm (absent or <= 0: off) / train.skip_nonfinite: decided on the device inside the HIP Adam step (optim.py)
+        clip = t.get("grad_clip_norm")
+        self.grad_clip_norm = float(clip) if clip is not None and float(clip) > 0 else None
+        self.skip_nonfinite = bool(t.get("skip_nonfinite", False))
+        if (self.grad_clip_norm is not None or self.skip_nonfinite) and not hip_adam:
+            raise ValueError("train.grad_clip_norm / train.skip_nonfinite are applied inside the HIP Adam step: they need hip_adam=True")
         self.trainloader, self.validloader = trainloader, validloader
         self.rank = int(os.environ.get("RANK", "0"))
         self.world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -132,8 +142,16 @@ class HydraTrainer:
         self.total_iters = max(1, n_iter * self.epoch)
         # torch.optim.Adam's update rule and state layout (train.py:147); hip_adam: all 693 tensors in one launch (optim.py) instead of the
         # foreach implementation's ~10 multi-tensor launches (3.9 -> 0.4 ms per step)
-        opt_cls = Adam if hip_adam else torch.optim.Adam
-        self.optimizer = opt_cls(self.hydranet.parameters(), self.lr, weight_decay=self.weight_decay)
+        if hip_adam:
+            self.optimizer = Adam(self.hydranet.parameters(), self.lr, weight_decay=self.weight_decay, max_grad_norm=self.grad_clip_norm,
+                                  skip_nonfinite=self.skip_nonfinite)
+        else:
+            self.optimizer = torch.optim.Adam(self.hydranet.parameters(), self.lr, weight_decay=self.weight_decay)
+        self._guarded = self.grad_clip_norm is not None or self.skip_nonfinite
+        if self.skip_nonfinite:
+            # the device guard replaces the reference's host guard (HydraNet._guard: seven synchronising reads of device scalars per step,
+            # sys.exit() on the first bad batch): a non-finite step is skipped, and only a whole print interval of them ends the run
+            self.hydranet.check_finite = False
         self.scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(self.optimizer, self.total_iters, eta_min=1e-8)     # iteration based
 
         self._one = torch.ones((), device=self.device)            # root gradient, allocated once
@@ -181,6 +199,15 @@ class HydraTrainer:
                 self.reducer = self._reducers[phase]
         self.phase = phase
         self.hydranet.grad_scope = None if phase == "joint" else phase
+
+    def _optimizer_step(self, total_loss: torch.Tensor):
+        """Adam step; with train.skip_nonfinite the guard also sees the total loss and the persistent stage kernels' status word (a replayed
+        step whose persistent launch expired must not reach Adam).  With more than one rank only the exchanged gradients are identical
+        everywhere, so only they may decide: every rank then takes the same decision without exchanging it."""
+        if self.skip_nonfinite and self.world == 1:
+            self.optimizer.step(losses=[total_loss.detach()], guard_words=[K_xstage_status_word(self.device)])
+        else:
+            self.optimizer.step()
 
     def cal_total_loss(self, loss_dict: Dict[str, torch.Tensor]):
         """train.py:192-203: the weighted sum of the task losses (same weights, same association order); on the device it is one launch
@@ -319,7 +346,7 @@ class HydraTrainer:
             self._eager_iters = 0
         if self.capture_step and self._eager_iters >= 2:
             loss_dict = self._captured_fwd_bwd(batch_data)
-            self.optimizer.step()
+            self._optimizer_step(self._cap[3]["total_loss"])         # (the replayed graph's static tensor)
             self.scheduler.step()
             return loss_dict
         self._eager_iters += 1
@@ -337,7 +364,7 @@ class HydraTrainer:
         loss_total.backward(self._one)
         if self.reducer is not None:
             self.reducer.finish()
-        self.optimizer.step()
+        self._optimizer_step(loss_total)
         self.scheduler.step()
         # detached: the losses are for logging; a caller that keeps them must not keep this iteration's autograd nodes alive (stale
         # AccumulateGrad nodes bound to another stream break a later capture)
@@ -350,13 +377,18 @@ class HydraTrainer:
             if iter_idx % self.print_interval == 0:
                 if self.device.type == "cuda":
                     K_xstage_assert_ok(self.device)          # (a replayed step cannot check its persistent launches itself: ops/xstage.py)
+                guard = self.optimizer.grad_guard_record() if self._guarded else None
                 if self.rank == 0:
-                    self.print_loss_info(loss_dict, epoch, iter_idx)
+                    self.print_loss_info(loss_dict, epoch, iter_idx, guard=guard)
+                if guard is not None and guard["skipped_consecutive"] >= self.print_interval:
+                    print("training diverged")                   # every step since the last print was skipped
+                    sys.exit()
 
-    def print_loss_info(self, loss_dict, epoch, batch_idx, mode="train"):
+    def print_loss_info(self, loss_dict, epoch, batch_idx, mode="train", guard=None):
         lr = self.optimizer.param_groups[0]["lr"]
         print("%s Epoch [%i|%i] Iter [%i] Lr %.5f  " % (mode.upper(), epoch, self.epoch, batch_idx, lr) +
-              "  ".join("%s %.3f" % (k, float(v.detach())) for k, v in loss_dict.items()))
+              "  ".join("%s %.3f" % (k, float(v.detach())) for k, v in loss_dict.items()) +
+              ("" if guard is None else "  grad_norm %.3f  coef %.3f  skipped %i" % (guard["norm"], guard["coef"], guard["skipped"])))
 
     @torch.no_grad()
     def valid(self, epoch: int = 0, eval_dir: Optional[str] = None, lane_coder=None, det_conf_thres: float = 0.3, det_iou_thres: float = 0.3,
