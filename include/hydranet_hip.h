@@ -556,6 +556,22 @@ int hn_det_postprocess(const float* anchors, const float* regression, const floa
 int hn_lane_decode_nms(const float* predict_cls, const float* predict_loc, int N, int W, int H, int stride, int ppl, float exist_threshold,
                        float nms_threshold, int use_mean, float margin, float* X, float* prob, int* start, int* end, int* order, int* keep,
                        int* counts, hipStream_t stream);
+/* Lane filter by the seg head's marking class (deploy/src/model/hydranet_model.cpp:546-607; hn_lane_filter.hip, DESIGN.md 4n), on
+ * hn_lane_decode_nms's device outputs as they are.  Per image: the first top_k (1 .. 64) entries of order[0 .. counts[n]) with keep != 0 are
+ * selected (n_sel[n] of them; every other candidate is dropped).  A selected candidate of anchor a has the points (rn(X[n][a][p]), H - 1 -
+ * p * interval), start[a] <= p < end[a]: x rounded to nearest, ties to even, clamped to +-16383; fewer than two points or a non-finite x
+ * paint nothing.  Its mask is the union of its segments painted with thickness line_width by hn_draw's kind 0 rule (pixel centres within
+ * line_width / 2 of the segment, the integer distance test), clipped to the image; area = its pixels, inter = those where mask == lane_class
+ * (mask: int64 [N][H][W] arg-max class map of the net input size).  Kept iff (float)inter / (float)area > min_ratio (one fp32 division;
+ * 0 / 0 drops).  stats int32 [N][top_k][4] = {position j in order, area, inter, kept} (rows from n_sel[n] on: zero); keep_out int32 [N][hw],
+ * hw = (W/stride)*(H/stride): 1 at the positions j of the kept candidates, 0 everywhere else.  All three outputs are written completely.
+ * ws: hn_lane_seg_filter_ws_bytes(N, top_k, ppl) bytes (-1: N < 1, top_k outside 1 .. 64 or ppl outside 1 .. 1024).  Returns 1 before any
+ * HIP call for a null pointer, top_k or line_width (1 .. 16384) out of range, W or H not a multiple of stride or above 16384, interval < 1
+ * or a workspace that is too small.  Three launches, no memset, no allocation, no synchronisation. */
+long hn_lane_seg_filter_ws_bytes(int N, int top_k, int ppl);
+int hn_lane_seg_filter(const float* X, const int* start, const int* end, const int* order, const int* keep, const int* counts, int N, int W,
+                       int H, int stride, int ppl, int interval, const long* mask, int lane_class, int line_width, float min_ratio, int top_k,
+                       void* ws, long ws_bytes, int* keep_out, int* stats, int* n_sel, hipStream_t stream);
 
 /* Input pre-processing (demo.py:26-50,186-196; dataset/utility.py:213-227): uint8 BGR frames [N][Hs][Ws][3] -> bilinear resize (cv2.resize
  * INTER_LINEAR fixed-point form for 8-bit images) -> RGB -> (v/255 - mean)/std -> fp32 [N][3][Hd][Wd]. */

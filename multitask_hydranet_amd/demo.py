@@ -24,7 +24,12 @@ the decoded lanes and boxes are returned as data (Demo.process).
 is painted from, nearest-resized to the frame's original size and written as an 8-bit label PNG per frame (<image stem>.png, or
 frame_%06d.png for a video) -- the format MultitaskData reads its seg labels from.  Filter and deflate run on the device (png_encode,
 hn_png_enc.hip); --seg-palette writes colour type 3 with the demo's colours instead of grey, the same index bytes; --seg-huffman dynamic
-deflates with a Huffman code per block instead of the fixed one: the same pixels, smaller files."""
+deflates with a Huffman code per block instead of the fixed one: the same pixels, smaller files.
+--lane-seg-filter [--lane-top-k N --lane-seg-ratio R --lane-seg-width T --lane-seg-class C] (any mode) adds the one step of the reference's
+deploy path that uses two heads together (deploy/src/model/hydranet_model.cpp:546-607): the lanes the NMS leaves are capped at 14 and each
+is kept only when more than 1 % of its pixels, painted 20 wide, lie on the seg arg-max map's class 2 (marking_area).  It runs on the device
+between the lane decode and its readback (hn_lane_seg_filter); only the survivors are drawn and results.json gains every
+selected lane's score, painted area, overlap and verdict.  Off by default."""
 from __future__ import annotations
 
 import argparse
@@ -47,7 +52,10 @@ def seg_palette(colors: dict) -> dict:
 class Demo:
     """the state demo.py sets up before its frame loop (demo.py:68-134)"""
 
-    def __init__(self, cfgs: dict, weights: Optional[str] = None, device="cuda:0", fold_batchnorm: bool = True):
+    def __init__(self, cfgs: dict, weights: Optional[str] = None, device="cuda:0", fold_batchnorm: bool = True, lane_seg_filter=None):
+        """lane_seg_filter: True (the deploy header's constants) or a lane_codec.LaneSegFilter -- every process* call then caps the decoded
+        lanes and filters them by the seg head's marking class on the device; each call's own lane_seg_filter argument
+        overrides it (False: off for that call).  Needs a configuration that runs the seg head and the lane head."""
         from . import HydraNet
         from .lane_codec import LaneCodec
         self.cfgs = cfgs
@@ -63,6 +71,7 @@ class Demo:
         self.colors = dict(SEG_CLASS_COLOR_ID)
         self.lane_conf, self.lane_nms = 0.90, 80          # demo.py:212-213 (hard-coded there, not the cfg's values)
         self.det_conf, self.det_iou = 0.4, 0.3            # demo.py:241
+        self.lane_seg_filter = self._lane_filter(lane_seg_filter, None)
         self.device = torch.device(device)
         self.net = HydraNet(cfgs=cfgs, onnx_export=False).to(self.device)
         if weights:
@@ -71,11 +80,28 @@ class Demo:
         if fold_batchnorm:
             self.net.prepare_inference()
 
+    def _lane_filter(self, asked, default):
+        """the LaneSegFilter a call runs with: its own argument (True: the deploy defaults, False: none), else the constructor's"""
+        from .lane_codec import LaneSegFilter
+        if asked is None:
+            return default
+        if asked is False:
+            return None
+        flt = LaneSegFilter() if asked is True else asked
+        if not isinstance(flt, LaneSegFilter):
+            raise ValueError("lane_seg_filter is True or a LaneSegFilter, not %r" % (asked,))
+        if not (self.train_seg and self.train_lane):
+            raise ValueError("the lane seg filter needs the seg head and the lane head, but this configuration runs train_seg=%s, "
+                             "train_lane=%s" % (self.train_seg, self.train_lane))
+        return flt
+
     @torch.no_grad()
-    def process(self, input_img: np.ndarray) -> Dict[str, object]:
-        """one iteration of demo.py's loop (demo.py:176-246) for one BGR frame [H, W, 3] uint8"""
+    def process(self, input_img: np.ndarray, lane_seg_filter=None) -> Dict[str, object]:
+        """one iteration of demo.py's loop (demo.py:176-246) for one BGR frame [H, W, 3] uint8.  lane_seg_filter: see __init__;
+        "lane_filter" then holds the selected lanes' statistics and "lanes" only the survivors."""
         from .preprocess import preprocess_bgr
         net = self.net
+        flt = self._lane_filter(lane_seg_filter, self.lane_seg_filter)
         org_h, org_w = input_img.shape[:2]
         org_size = (org_w, org_h)
         tic = time.time()
@@ -86,8 +112,14 @@ class Demo:
         if self.train_lane:                                                                   # demo.py:209-228
             cls_preds, loc_preds = outputs["lane"]["predict_cls"], outputs["lane"]["predict_loc"]
             lanes = []
+            mask = self._seg_mask(outputs["seg"]) if flt is not None else None
             for b in range(len(imgs)):
-                nms_set = net.laneheader.decode(cls_preds[b], loc_preds[b], self.lane_coder, self.lane_conf, self.lane_nms, False)
+                if flt is None:
+                    nms_set = net.laneheader.decode(cls_preds[b], loc_preds[b], self.lane_coder, self.lane_conf, self.lane_nms, False)
+                else:
+                    nms_set, stats = net.laneheader.decode(cls_preds[b], loc_preds[b], self.lane_coder, self.lane_conf, self.lane_nms, False,
+                                                           seg_mask=mask[b], seg_filter=flt, return_stats=True)
+                    res.setdefault("lane_filter", []).append(stats)
                 lanes.append(net.laneheader.scale_to_org(nms_set, self.net_w, self.net_h, org_size[0], org_size[1])["Lines"])
             res["lanes"] = lanes
         if self.train_seg:                                                                    # demo.py:230-233
@@ -114,17 +146,19 @@ class Demo:
 
     @torch.no_grad()
     def process_device(self, frames: dict, quality: int = 95, subsampling: str = "4:2:0", entropy: str = "host", seg_png: bool = False,
-                       seg_palette: Optional[dict] = None, seg_huffman: str = "fixed") -> Dict[str, object]:
+                       seg_palette: Optional[dict] = None, seg_huffman: str = "fixed", lane_seg_filter=None) -> Dict[str, object]:
         """the same iteration for ONE frame that is already on the device in the packed layout of jpeg.imread_bgr_device, with the
         reference's drawing (demo.py:230, 235, 244) and its cv2.imwrite (demo.py:261): "jpeg" holds the annotated frame's JFIF bytes,
         "visual" the annotated frame in the packed device layout.  The frame is not copied to the host.  entropy: "host" | "device", where
         the Huffman stage of the encode runs (jpeg_encode.encode_batch); the bytes are the same.  seg_png: "seg_png" holds the PNG file
         bytes of the arg-max class map at the frame's original size (png_encode.encode_batch; colour type 3 with seg_palette = {id: (r, g,
         b)}, grey without; seg_huffman: "fixed" | "dynamic", png_encode's huffman -- the same pixels in a smaller file); everything else is
-        what the call gives without it."""
+        what the call gives without it.  lane_seg_filter: see __init__ -- the lanes are capped and filtered by the arg-max map this call
+        paints its overlay from, before the one readback of the decode; "lanes" holds the survivors, "lane_filter" the statistics."""
         from . import draw, jpeg_encode, png_encode
         if seg_png:
             self._need_seg()
+        flt = self._lane_filter(lane_seg_filter, self.lane_seg_filter)
         from .preprocess import preprocess_bgr
         from .visual import seg_decode_device
         net = self.net
@@ -140,11 +174,17 @@ class Demo:
         res: Dict[str, object] = {"org_size": org_size}
         if self.train_lane:
             cls_preds, loc_preds = outputs["lane"]["predict_cls"], outputs["lane"]["predict_loc"]
-            nms_set = net.laneheader.decode(cls_preds[0], loc_preds[0], self.lane_coder, self.lane_conf, self.lane_nms, False)
+            if flt is None:
+                nms_set = net.laneheader.decode(cls_preds[0], loc_preds[0], self.lane_coder, self.lane_conf, self.lane_nms, False)
+            else:
+                mask = self._seg_mask(outputs["seg"])
+                nms_set, stats = net.laneheader.decode(cls_preds[0], loc_preds[0], self.lane_coder, self.lane_conf, self.lane_nms, False,
+                                                       seg_mask=mask[0], seg_filter=flt, return_stats=True)
+                res["lane_filter"] = [stats]
             res["lanes"] = [net.laneheader.scale_to_org(nms_set, self.net_w, self.net_h, org_w, org_h)["Lines"]]
             frames = net.laneheader.visual(frames, res["lanes"], org_w, filter_vertical=True)
         if self.train_seg:
-            seg = self._seg_mask(outputs["seg"]) if seg_png else outputs["seg"]
+            seg = mask if flt is not None else self._seg_mask(outputs["seg"]) if seg_png else outputs["seg"]
             blended = seg_decode_device(frame, seg, self.colors)
             frames = {"data": blended.view(-1), "offsets": np.zeros(1, np.int64), "shapes": np.array([[org_h, org_w]], np.int64)}
             if seg_png:
@@ -163,7 +203,8 @@ class Demo:
 
     @torch.no_grad()
     def process_device_batch(self, frames: dict, quality: int = 95, subsampling: str = "4:2:0", entropy: str = "host", out_hw=None,
-                             seg_png: bool = False, seg_palette: Optional[dict] = None, seg_huffman: str = "fixed") -> Dict[str, object]:
+                             seg_png: bool = False, seg_palette: Optional[dict] = None, seg_huffman: str = "fixed",
+                             lane_seg_filter=None) -> Dict[str, object]:
         """process_device for the B frames of a packed batch that all have one size (a video's): one preprocess_bgr and one forward over
         the batch, the lane and box decodes of the batch read back at ONE point (the drawing primitives are built from them on the host),
         one draw_packed per drawing stage, one seg overlay, an optional resize_bgr of the annotated frames to out_hw = (height, width),
@@ -171,10 +212,13 @@ class Demo:
         that frame alone, as long as the forward's arithmetic for an image does not depend on the batch it runs in --
         and "visual" the annotated (and resized) frames in the packed device layout.  Like process_device it paints into `frames`.
         seg_png: "seg_png" holds one PNG file per frame, the arg-max class maps at the frames' ORIGINAL size (out_hw does not apply),
-        encoded for the whole batch in one png_encode.encode_batch (seg_huffman: its huffman)."""
+        encoded for the whole batch in one png_encode.encode_batch (seg_huffman: its huffman).  lane_seg_filter: see __init__ -- the
+        filter's launches follow the lane decode's and its results come back at the same one point; "lanes" holds every frame's
+        survivors, "lane_filter" every frame's statistics."""
         from . import jpeg_encode, png_encode
         if seg_png:
             self._need_seg()
+        flt = self._lane_filter(lane_seg_filter, self.lane_seg_filter)
         from .postprocess import postprocess, postprocess_device
         from .preprocess import preprocess_bgr, resize_bgr
         from .visual import seg_decode_device
@@ -203,7 +247,12 @@ class Demo:
             launched = postprocess_device(*det_args)
         if self.train_lane:
             cls_preds, loc_preds = outputs["lane"]["predict_cls"], outputs["lane"]["predict_loc"]
-            nms_sets = net.laneheader.decode_batch(cls_preds, loc_preds, self.lane_coder, self.lane_conf, self.lane_nms, False)
+            if flt is None:
+                nms_sets = net.laneheader.decode_batch(cls_preds, loc_preds, self.lane_coder, self.lane_conf, self.lane_nms, False)
+            else:
+                mask = self._seg_mask(outputs["seg"])
+                nms_sets, res["lane_filter"] = net.laneheader.decode_batch(cls_preds, loc_preds, self.lane_coder, self.lane_conf, self.lane_nms,
+                                                                           False, seg_mask=mask, seg_filter=flt, return_stats=True)
             res["lanes"] = [net.laneheader.scale_to_org(s, self.net_w, self.net_h, org_w, org_h)["Lines"] for s in nms_sets]
         if self.train_detect:
             res["detections"] = postprocess(*det_args, launched=launched)
@@ -211,7 +260,7 @@ class Demo:
         if self.train_lane:
             frames = net.laneheader.visual(frames, res["lanes"], org_w, filter_vertical=True)
         if self.train_seg:
-            seg = self._seg_mask(outputs["seg"]) if seg_png else outputs["seg"]
+            seg = mask if flt is not None else self._seg_mask(outputs["seg"]) if seg_png else outputs["seg"]
             blended = seg_decode_device(batch, seg, self.colors)
             frames = {"data": blended.view(-1), "offsets": nbytes * np.arange(B, dtype=np.int64), "shapes": shapes.copy()}
             if seg_png:
@@ -257,6 +306,8 @@ def run_images(demo: "Demo", folder: str, out_dir: str, quality: int = 95, subsa
         nl = sum(len(l) for l in r.get("lanes", []))
         print("frame %d (%s): total process time is %i ms, %d lanes, %d boxes" % (t, os.path.basename(path), r["ms"], nl, nd))
         summary.append({"frame": t, "file": os.path.basename(path), "ms": r["ms"], "lanes": nl, "boxes": nd})
+        if "lane_filter" in r:
+            summary[-1]["lane_filter"] = r["lane_filter"][0]
     json.dump(summary, open(os.path.join(out_dir, "results.json"), "w"), indent=1)
     return summary
 
@@ -324,6 +375,8 @@ def run_video(demo: "Demo", src: str, dst: str, batch: int = 8, quality: int = 9
                     nd = len(r["detections"][k]["rois"]) if "detections" in r else 0
                     nl = len(r["lanes"][k]) if "lanes" in r else 0
                     summary.append({"frame": p, "file": os.path.basename(src), "ms": r["ms"] / B, "lanes": nl, "boxes": nd})
+                    if "lane_filter" in r:
+                        summary[-1]["lane_filter"] = r["lane_filter"][k]
                     p += 1
                 done += B
                 print("frames %d-%d: total process time is %i ms" % (done - B, done - 1, r["ms"]))
@@ -368,6 +421,12 @@ def main(argv=None):
     ap.add_argument("--seg-palette", action="store_true", help="write the class maps of --save-seg as palette PNGs with the demo's colours")
     ap.add_argument("--seg-huffman", choices=("fixed", "dynamic"), default=None, help="the deflate code of the --save-seg PNGs: fixed (the default), "
                     "or dynamic -- a Huffman code per block of 16 chunks, the same pixels in less than half the bytes")
+    ap.add_argument("--lane-seg-filter", action="store_true", help="the deploy path's lane filter: at most --lane-top-k lanes, each kept when "
+                    "more than --lane-seg-ratio of its painted pixels lie on the seg head's marking class; results.json gains the statistics")
+    ap.add_argument("--lane-top-k", type=int, default=None, help="lanes kept after the NMS at most (--lane-seg-filter; 14)")
+    ap.add_argument("--lane-seg-ratio", type=float, default=None, help="the overlap a lane needs, exclusive (--lane-seg-filter; 0.01)")
+    ap.add_argument("--lane-seg-width", type=int, default=None, help="thickness the lanes are painted with, pixels (--lane-seg-filter; 20)")
+    ap.add_argument("--lane-seg-class", type=int, default=None, help="the seg class id that counts as marking (--lane-seg-filter; 2)")
     ap.add_argument("--count", type=int, default=4)
     ap.add_argument("--out", default=None, help="directory for the annotated JPEGs (--images) or frame_%%04d.npy (blended frames), and results.json; "
                     "the annotated AVI (--video)")
@@ -379,11 +438,19 @@ def main(argv=None):
     if args.seg_huffman and not args.save_seg:
         ap.error("--seg-huffman needs --save-seg")
     huffman = args.seg_huffman or "fixed"
+    lane_opts = {"top_k": args.lane_top_k, "min_ratio": args.lane_seg_ratio, "line_width": args.lane_seg_width, "lane_class": args.lane_seg_class}
+    lane_opts = {k: v for k, v in lane_opts.items() if v is not None}
+    if lane_opts and not args.lane_seg_filter:
+        ap.error("--lane-top-k / --lane-seg-ratio / --lane-seg-width / --lane-seg-class need --lane-seg-filter")
+    lane_filter = None
+    if args.lane_seg_filter:
+        from .lane_codec import LaneSegFilter
+        lane_filter = LaneSegFilter(**lane_opts)
     cfgs = yaml.safe_load(open(args.cfg))
     if args.save_seg and not cfgs["train"]["train_seg"]:
         raise ValueError("--save-seg: %s runs no seg head (train.train_seg is off)" % args.cfg)
     torch.manual_seed(0)
-    demo = Demo(cfgs, args.weights)
+    demo = Demo(cfgs, args.weights, lane_seg_filter=lane_filter)
     if not args.weights:
         # random initialisation: every anchor scores ~0.5, far more candidates than any real frame has (the device NMS holds 32 768)
         print("no --weights: random initialisation, detection threshold raised to 0.95 for this run")
@@ -407,6 +474,8 @@ def main(argv=None):
         nl = sum(len(l) for l in r.get("lanes", []))
         print("frame %d: total process time is %i ms, %d lanes, %d boxes" % (t, r["ms"], nl, nd))
         summary.append({"frame": t, "ms": r["ms"], "lanes": nl, "boxes": nd})
+        if "lane_filter" in r:
+            summary[-1]["lane_filter"] = r["lane_filter"][0]
         if args.out:
             np.save(os.path.join(args.out, "frame_%04d.npy" % t), r["visual"])
     if args.out:

@@ -10,9 +10,14 @@ host-side bookkeeping on the handful of surviving lanes, restated.
 `LaneCodec.encode_lane` / `encode_lanes` (reference: head_lane/lane_codec.py:53-114,221-366, lane_spline_interp.py, and the dataset's
 division, dataset/dataloader.py:343-352): the host parses and packs the annotations (`pack_lanes`), hn_lane_encode does the rest for the
 whole batch.
+
+`LaneSegFilter` with `decode(..., seg_mask=, seg_filter=)` / `decode_batch`: the deploy path's cross-head step (deploy/src/model/
+hydranet_model.cpp:546-607) -- the NMS survivors capped at top_k and filtered by their overlap with the seg head's marking class -- on the
+device between the decode and its one readback (hn_lane_seg_filter).  Off unless a filter is passed.
 """
 from __future__ import annotations
 
+import dataclasses
 import json
 from typing import List
 
@@ -200,8 +205,82 @@ def pack_lanes(lane_objects, org_sizes, W, H, interval, interpolate, P):
     return pts, np.concatenate([lane_off, img_lane]).astype(np.int32), len(lanes)
 
 
-def _decode_batch(cls, loc, codec, conf_thres, nms_thres, use_mean, margin=100.0, keep_all=False) -> List[List[Lane]]:
+@dataclasses.dataclass(frozen=True)
+class LaneSegFilter:
+    """the deploy path's filter of the lanes the NMS leaves (deploy/src/model/hydranet_model.cpp:546-607; the defaults are the constants
+    of hydranet_model.h:68-75): at most top_k lanes, each painted line_width thick and kept when more than min_ratio of its painted
+    pixels lie on the seg arg-max map's lane_class (marking_area in the shipped cfgs).  DESIGN.md 4n."""
+    lane_class: int = 2
+    line_width: int = 20
+    min_ratio: float = 0.01
+    top_k: int = 14
+
+    def __post_init__(self):
+        for name in ("lane_class", "line_width", "top_k"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError("LaneSegFilter.%s is an integer, not %r" % (name, v))
+        if self.lane_class < 0:
+            raise ValueError("LaneSegFilter.lane_class is a class id >= 0, not %d" % self.lane_class)
+        if not 1 <= self.line_width <= 16384:
+            raise ValueError("LaneSegFilter.line_width is 1 .. 16384 pixels, not %d" % self.line_width)
+        if not 1 <= self.top_k <= 64:
+            raise ValueError("LaneSegFilter.top_k is 1 .. 64 lanes, not %d" % self.top_k)
+        r = self.min_ratio
+        if isinstance(r, bool) or not isinstance(r, (int, float, np.floating, np.integer)) or not np.isfinite(float(r)):
+            raise ValueError("LaneSegFilter.min_ratio is a finite number, not %r" % (r,))
+
+
+def _check_seg_filter(seg_mask, seg_filter, return_stats, codec, n):
+    """the filter's arguments, checked before anything is launched -> the integer interval of the codec's rows"""
+    if seg_filter is None:
+        if return_stats:
+            raise ValueError("return_stats asks for the seg filter's statistics: pass a seg_filter")
+        return None
+    if not isinstance(seg_filter, LaneSegFilter):
+        raise ValueError("seg_filter is a LaneSegFilter (or None), not %r" % (seg_filter,))
+    if seg_mask is None or not torch.is_tensor(seg_mask):
+        raise ValueError("seg_filter needs seg_mask: the int64 [N, H, W] arg-max class map (or the [N, C, H, W] seg logits) as a tensor")
+    W, H = int(codec.input_width), int(codec.input_height)
+    if seg_mask.dim() == 4:
+        ok = seg_mask.is_floating_point() and (seg_mask.shape[0], seg_mask.shape[2], seg_mask.shape[3]) == (n, H, W)
+    else:
+        ok = seg_mask.dim() == 3 and seg_mask.dtype == torch.int64 and tuple(seg_mask.shape) == (n, H, W)
+    if not ok:
+        raise ValueError("seg_mask is the int64 [%d, %d, %d] class map of the net input size or float [%d, C, %d, %d] logits, not %s %s"
+                         % (n, H, W, n, H, W, seg_mask.dtype, tuple(seg_mask.shape)))
+    interval = float(codec.interval)
+    if not (interval.is_integer() and interval >= 1):
+        raise ValueError("the seg filter paints on integer rows: the codec's interval %r is not a whole number of pixels" % codec.interval)
+    if H % int(codec.step_w) or W % int(codec.step_w):
+        raise ValueError("the seg filter needs an input size that is a multiple of the anchor stride, not %dx%d / %d" % (W, H, codec.step_w))
+    return int(interval)
+
+
+def _launch_seg_filter(X, ints, counts, n, W, H, stride, ppl, interval, seg_mask, f):
+    """hn_lane_seg_filter behind hn_lane_decode_nms on the same stream: ints [5, n, hw] holds start, end, order, keep and takes keep_out
+    as its fifth plane -> the int32 tensor stats [n, top_k, 4] ++ n_sel [n]"""
+    dev = X.device
+    seg_mask = seg_mask.to(dev)
+    if seg_mask.dim() == 4:
+        from . import ops as K
+        seg_mask = K.argmax_channels(seg_mask.detach().float())
+    seg_mask = seg_mask.contiguous()
+    need = lib().query("hn_lane_seg_filter_ws_bytes", n, f.top_k, ppl)
+    if need < 0:
+        raise ValueError("the seg filter holds 1 .. 1024 points per line and 1 .. 65535 images, not %d and %d" % (ppl, n))
+    ws = torch.empty((need,), device=dev, dtype=torch.uint8)
+    ext = torch.empty((n * f.top_k * 4 + n,), device=dev, dtype=torch.int32)
+    lib().call("hn_lane_seg_filter", X.data_ptr(), ints[0].data_ptr(), ints[1].data_ptr(), ints[2].data_ptr(), ints[3].data_ptr(),
+               counts.data_ptr(), n, W, H, stride, ppl, interval, seg_mask.data_ptr(), int(f.lane_class), int(f.line_width), float(f.min_ratio),
+               int(f.top_k), ws.data_ptr(), need, ints[4].data_ptr(), ext.data_ptr(), ext.data_ptr() + 4 * n * f.top_k * 4)
+    return ext
+
+
+def _decode_batch(cls, loc, codec, conf_thres, nms_thres, use_mean, margin=100.0, keep_all=False, seg_mask=None, seg_filter=None,
+                  return_stats=False):
     assert getattr(codec, "scale_invariance", True), "only the scale-invariant location encoding of the shipped cfgs is on the device path"
+    interval = _check_seg_filter(seg_mask, seg_filter, return_stats, codec, cls.shape[0])
     dev = cls.device if cls.is_cuda else torch.device("cuda", torch.cuda.current_device())
     cls = cls.detach().to(dev, torch.float32).contiguous()
     loc = loc.detach().to(dev, torch.float32).contiguous()
@@ -210,13 +289,23 @@ def _decode_batch(cls, loc, codec, conf_thres, nms_thres, use_mean, margin=100.0
     assert hw == (W // stride) * (H // stride) and loc.shape == (n, hw, 2 * ppl + 2), (cls.shape, loc.shape)
     X = torch.empty((n, hw, ppl), device=dev, dtype=torch.float32)
     prob = torch.empty((n, hw), device=dev, dtype=torch.float32)
-    ints = torch.empty((4, n, hw), device=dev, dtype=torch.int32)
+    ints = torch.empty((4 if seg_filter is None else 5, n, hw), device=dev, dtype=torch.int32)
     counts = torch.empty((n,), device=dev, dtype=torch.int32)
     lib().call("hn_lane_decode_nms", cls.data_ptr(), loc.data_ptr(), n, W, H, stride, ppl, float(conf_thres), float(nms_thres), 1 if use_mean else 0,
                float(margin), X.data_ptr(), prob.data_ptr(), ints[0].data_ptr(), ints[1].data_ptr(), ints[2].data_ptr(), ints[3].data_ptr(),
                counts.data_ptr())
+    if seg_filter is not None:             # the filter's launches follow on the same stream; its outputs come back with the decode's arrays
+        ext = _launch_seg_filter(X, ints, counts, n, W, H, stride, ppl, interval, seg_mask, seg_filter)
     counts, prob, ints, X = counts.cpu().numpy(), prob.cpu().numpy(), ints.cpu().numpy(), X.cpu().numpy()
-    start, end, order, keep = ints
+    start, end, order, keep = ints[:4]
+    stats = None
+    if seg_filter is not None:
+        ext = ext.cpu().numpy()
+        keep = ints[4]                     # keep_out: the NMS survivors minus the capped and the dropped
+        tk = seg_filter.top_k
+        rows, n_sel = ext[:n * tk * 4].reshape(n, tk, 4), ext[n * tk * 4:]
+        stats = [[{"score": float(prob[i, order[i, j]]), "area": int(ar), "overlap": int(ov), "kept": bool(kp)}
+                  for j, ar, ov, kp in rows[i, :int(n_sel[i])].tolist()] for i in range(n)]
     fw = W // stride
     out = []
     for i in range(n):
@@ -232,17 +321,30 @@ def _decode_batch(cls, loc, codec, conf_thres, nms_thres, use_mean, margin=100.0
         if keep_all:                       # decode_lane returns raster order
             lanes.sort(key=lambda l: (l.ay, l.ax))
         out.append(lanes)
-    return out
+    return (out, stats) if return_stats else out
 
 
-def decode(predict_cls, predict_loc, pointlane, conf_thres=0.5, nms_line_thres=100, use_mean=False):
-    """LaneHeader.decode (lanedetect.py:103-116) for ONE image: predict_cls [hw, 2] logits, predict_loc [hw, 2*ppl+2]"""
-    return _decode_batch(predict_cls[None], predict_loc[None], pointlane, conf_thres, nms_line_thres, use_mean)[0]
+def decode(predict_cls, predict_loc, pointlane, conf_thres=0.5, nms_line_thres=100, use_mean=False, seg_mask=None, seg_filter=None,
+           return_stats=False):
+    """LaneHeader.decode (lanedetect.py:103-116) for ONE image: predict_cls [hw, 2] logits, predict_loc [hw, 2*ppl+2].  seg_filter (a
+    LaneSegFilter) with seg_mask (the image's int64 [H, W] arg-max class map or its [C, H, W] seg logits): the deploy path's cap and
+    marking-class filter on the device, see decode_batch; return_stats: (lanes, stats of the selected lanes)."""
+    if seg_mask is not None and torch.is_tensor(seg_mask):
+        seg_mask = seg_mask[None]
+    r = _decode_batch(predict_cls[None], predict_loc[None], pointlane, conf_thres, nms_line_thres, use_mean, seg_mask=seg_mask,
+                      seg_filter=seg_filter, return_stats=return_stats)
+    return (r[0][0], r[1][0]) if return_stats else r[0]
 
 
-def decode_batch(predict_cls, predict_loc, pointlane, conf_thres=0.5, nms_line_thres=100, use_mean=False):
-    """the same for a whole batch [N, hw, 2] / [N, hw, L] in one launch"""
-    return _decode_batch(predict_cls, predict_loc, pointlane, conf_thres, nms_line_thres, use_mean)
+def decode_batch(predict_cls, predict_loc, pointlane, conf_thres=0.5, nms_line_thres=100, use_mean=False, seg_mask=None, seg_filter=None,
+                 return_stats=False):
+    """the same for a whole batch [N, hw, 2] / [N, hw, L] in one launch.  With seg_filter (a LaneSegFilter) and seg_mask (the int64
+    [N, H, W] arg-max class map of the net input size, or the [N, C, H, W] seg logits, reduced by argmax_channels) the lanes the NMS leaves
+    are capped and filtered by the seg head's marking class on the device (hn_lane_seg_filter) before the one readback, and
+    only the survivors are returned; return_stats: (lanes, stats), stats[i] = one {"score", "area", "overlap", "kept"} per selected lane of
+    image i in descending-score order.  Without seg_filter nothing is launched or returned beyond the decode."""
+    return _decode_batch(predict_cls, predict_loc, pointlane, conf_thres, nms_line_thres, use_mean, seg_mask=seg_mask, seg_filter=seg_filter,
+                         return_stats=return_stats)
 
 
 # ---- host-side bookkeeping on the surviving lanes (lane_codec_utils.py:66-124,185-282) ----------------------------------------------
