@@ -663,10 +663,27 @@ int hn_grad_guard(const long* jobs, const int* block_job, long total_blocks, lon
 int hn_adam_step_guarded(const long* jobs, const int* block_job, long total_blocks, double lr, double beta1, double beta2, double eps,
                          double weight_decay, long step, const void* record, hipStream_t stream);
 
+/* hn_adam_step (record == NULL) or hn_adam_step_guarded (record = hn_grad_guard's) that also keeps an exponential moving average of every
+ * parameter, in the same launch and the same kernel body: p, m and v come out bit-identical to those entry points.  jobs / block_job /
+ * total_blocks are hn_adam_step's tables, unchanged; ema (DEVICE long [n_jobs]) = one fp32 pointer per job, numel elements each, not
+ * overlapping p, g, m or v.  With the new parameter value p' in its register, e' = e + w * (p' - e), w = (float)(1.0 - ema_decay) formed
+ * in double on the host and rounded once; subtraction, product and sum are each rounded (no fused multiply-add), and whole aligned float4s
+ * (p, g, m, v and e all 16-byte aligned) and single elements go through one instruction stream.  A skipped step (record->skip != 0) returns
+ * before any store: e stays untouched too.  HN_ERR "bad argument" unless 0 <= ema_decay < 1 (a NaN fails) and ema is non-NULL.  Plain
+ * vector loads and stores only; no workgroup waits on another, nothing is allocated or synchronised: graph-capturable. */
+int hn_adam_step_ema(const long* jobs, const int* block_job, long total_blocks, const long* ema, double lr, double beta1, double beta2,
+                     double eps, double weight_decay, long step, double ema_decay, const void* record, hipStream_t stream);
+
 /* Many contiguous tensors copied in one launch (the gather of a gradient bucket before its all-reduce, train.py:130-137's DDP buckets):
  * jobs (DEVICE) = n x 4 int64 {src, dst, numel, first_block}, block = 256 threads x 4 elements, block_job (DEVICE int32) = job of every
  * block; kind 0: fp32 -> fp32, 1: fp32 -> bf16 (reduced-precision payload), 2: bf16 -> fp32. */
 int hn_copy_many(const long* jobs, const int* block_job, long total_blocks, int kind, hipStream_t stream);
+
+/* Many pairs of contiguous fp32 tensors exchanged in one launch: jobs / block_job in hn_copy_many's layout, n x 4 int64 {a, b, numel,
+ * first_block}; afterwards a holds what b held and b what a held.  32-bit words are moved, not floats (NaN payloads and -0 survive), 16
+ * bytes at a time where both pointers allow.  a and b of one job must NOT overlap, and no tensor may appear in two jobs.  Plain vector
+ * loads and stores; no workgroup waits on another, nothing is allocated or synchronised: graph-capturable. */
+int hn_swap_many(const long* jobs, const int* block_job, long total_blocks, hipStream_t stream);
 
 /* COCO box mAP (pycocotools COCOeval(..., 'bbox') evaluate + accumulate; hn_coco.hip, parity rules in its header comment).
  * hn_coco_match: one workgroup per (image, category) cell.  cells (DEVICE int32 [n_cells][4]) = {gt cell = image order * K + category,

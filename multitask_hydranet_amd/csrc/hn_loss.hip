@@ -1186,18 +1186,36 @@ extern "C" int hn_weighted_sum(const void* const* xs, const float* w, const floa
 // The step's decision, written by hn_grad_guard (below) and obeyed by hn_adam_step_guarded: 32 bytes on the device, zeroed once by the caller.
 struct GuardRecord { float norm, coef; int skip, steps, skipped, skipped_consecutive, pad[2]; };
 
+// The average's update __fadd_rn(e, __fmul_rn(w, __fsub_rn(p, e))) with each of the three operations really rounded on its own.  To this
+// compiler the __f*_rn intrinsics are the plain operators, compiled with HIP's default -ffp-contract=fast-honor-pragmas: once inlined, a
+// product and the sum that takes it become one fused multiply-add (seen as a last-bit difference against three numpy float32
+// operations).  Operators written under the pragma carry no licence to contract, so they stay a subtract, a multiply and an add.
+__device__ __forceinline__ float ema_lerp_rn(float e, float p, float w) {
+#pragma clang fp contract(off)
+    const float d = p - e;
+    const float t = w * d;
+    return e + t;
+}
+
 // GUARDED = false is hn_adam_step.  GUARDED = true (hn_adam_step_guarded) reads the record first: a flagged step returns before its first
 // store; otherwise the gradient is scaled by the clipping coefficient before the weight-decay term, i.e. clip in place, then step --
 // without writing the gradient.  x * 1.0f == x, so coef == 1.0f gives hn_adam_step's bits.
-template <bool GUARDED>
+// EMA = true (hn_adam_step_ema) also keeps an exponential moving average e of the parameter (ema: one fp32 pointer per job): once the new
+// parameter value p' is in its register, e' = e + w * (p' - e) in rounded operations -- one more read and one more write per element, no
+// second pass over p.  p, m and v are formed by the same instructions as without it; a skipped step leaves e untouched as well.
+template <bool GUARDED, bool EMA>
 __global__ __launch_bounds__(256) void adam_step_kernel(const long* jobs, const int* block_job, float lr_over_bc1, float w1, float b2, float w2,
-                                                        float eps, float wd, float bc2_sqrt, const GuardRecord* rec) {
+                                                        float eps, float wd, float bc2_sqrt, const GuardRecord* rec, const long* ema,
+                                                        float ema_w) {
     float coef = 1.f;
     if constexpr (GUARDED) {
         if (rec->skip != 0) return;
         coef = rec->coef;
     }
-    const long* jb = jobs + (long)block_job[blockIdx.x] * 6;
+    const int job = block_job[blockIdx.x];
+    const long* jb = jobs + (long)job * 6;
+    float* e = nullptr;
+    if constexpr (EMA) e = reinterpret_cast<float*>(ema[job]);
     float* p = reinterpret_cast<float*>(jb[0]);
     const float* g = reinterpret_cast<const float*>(jb[1]);
     float* m = reinterpret_cast<float*>(jb[2]);
@@ -1217,51 +1235,77 @@ __global__ __launch_bounds__(256) void adam_step_kernel(const long* jobs, const 
     // branch used to carry their own copies of `one`, and the two compiled forms differed by an ulp on a few elements per tensor -- a
     // data-parallel run (gradients = views at arbitrary offsets of a flat bucket) then drifted from the single-GPU run bit by bit
     const bool vec = i0 + 4 <= n && ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                                      reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+                                      reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(e)) & 15) == 0;
     float pv[4] = {0.f, 0.f, 0.f, 0.f}, gv[4] = {0.f, 0.f, 0.f, 0.f}, mv[4] = {0.f, 0.f, 0.f, 0.f}, vv[4] = {0.f, 0.f, 0.f, 0.f};
+    float ev[4] = {0.f, 0.f, 0.f, 0.f};
     if (vec) {
         const f32x4 a = *reinterpret_cast<const f32x4*>(p + i0), b = *reinterpret_cast<const f32x4*>(g + i0);
         const f32x4 c = *reinterpret_cast<const f32x4*>(m + i0), d = *reinterpret_cast<const f32x4*>(v + i0);
 #pragma unroll
         for (int k = 0; k < 4; ++k) { pv[k] = a[k]; gv[k] = b[k]; mv[k] = c[k]; vv[k] = d[k]; }
+        if constexpr (EMA) {
+            const f32x4 f = *reinterpret_cast<const f32x4*>(e + i0);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) ev[k] = f[k];
+        }
     } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-            if (i0 + k < n) { pv[k] = p[i0 + k]; gv[k] = g[i0 + k]; mv[k] = m[i0 + k]; vv[k] = v[i0 + k]; }
+            if (i0 + k < n) {
+                pv[k] = p[i0 + k]; gv[k] = g[i0 + k]; mv[k] = m[i0 + k]; vv[k] = v[i0 + k];
+                if constexpr (EMA) ev[k] = e[i0 + k];
+            }
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) pv[k] = one(pv[k], gv[k], mv[k], vv[k]);
+    for (int k = 0; k < 4; ++k) {
+        pv[k] = one(pv[k], gv[k], mv[k], vv[k]);
+        if constexpr (EMA) ev[k] = ema_lerp_rn(ev[k], pv[k], ema_w);
+    }
     if (vec) {
         *reinterpret_cast<f32x4*>(p + i0) = (f32x4){pv[0], pv[1], pv[2], pv[3]};
         *reinterpret_cast<f32x4*>(m + i0) = (f32x4){mv[0], mv[1], mv[2], mv[3]};
         *reinterpret_cast<f32x4*>(v + i0) = (f32x4){vv[0], vv[1], vv[2], vv[3]};
+        if constexpr (EMA) *reinterpret_cast<f32x4*>(e + i0) = (f32x4){ev[0], ev[1], ev[2], ev[3]};
     } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-            if (i0 + k < n) { p[i0 + k] = pv[k]; m[i0 + k] = mv[k]; v[i0 + k] = vv[k]; }
+            if (i0 + k < n) {
+                p[i0 + k] = pv[k]; m[i0 + k] = mv[k]; v[i0 + k] = vv[k];
+                if constexpr (EMA) e[i0 + k] = ev[k];
+            }
     }
 }
 
 static int adam_launch(const long* jobs, const int* block_job, long total_blocks, double lr, double beta1, double beta2, double eps,
-                       double weight_decay, long step, const GuardRecord* rec, hipStream_t st) {
+                       double weight_decay, long step, const GuardRecord* rec, const long* ema, double ema_decay, hipStream_t st) {
     // the scalars as torch forms them from Python doubles: 1 - beta, 1 - beta ** step, lr / bias_correction1, sqrt(bias_correction2) in
-    // double, rounded to fp32 once (1.0f - 0.999f differs from float(0.001) by 1.3e-5)
+    // double, rounded to fp32 once (1.0f - 0.999f differs from float(0.001) by 1.3e-5); the average's weight 1 - decay likewise
     const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    auto kern = rec ? adam_step_kernel<true> : adam_step_kernel<false>;
+    auto kern = ema ? (rec ? adam_step_kernel<true, true> : adam_step_kernel<false, true>)
+                    : (rec ? adam_step_kernel<true, false> : adam_step_kernel<false, false>);
     hipLaunchKernelGGL(kern, dim3((unsigned)total_blocks), dim3(256), 0, st, jobs, block_job, (float)(lr / bc1), (float)(1.0 - beta1),
-                       (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)sqrt(bc2), rec);
+                       (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)sqrt(bc2), rec, ema,
+                       (float)(1.0 - ema_decay));
     HN_LAUNCH_CHECK();
 }
 extern "C" int hn_adam_step(const long* jobs, const int* block_job, long total_blocks, double lr, double beta1, double beta2, double eps,
                             double weight_decay, long step, hipStream_t st) {
     HN_CHECK_ARG(jobs && block_job && total_blocks > 0 && step >= 1 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0);
-    return adam_launch(jobs, block_job, total_blocks, lr, beta1, beta2, eps, weight_decay, step, nullptr, st);
+    return adam_launch(jobs, block_job, total_blocks, lr, beta1, beta2, eps, weight_decay, step, nullptr, nullptr, 0.0, st);
 }
 /* hn_adam_step that obeys the record hn_grad_guard wrote earlier on the same stream; the gradient tensors are read, never written */
 extern "C" int hn_adam_step_guarded(const long* jobs, const int* block_job, long total_blocks, double lr, double beta1, double beta2, double eps,
                                     double weight_decay, long step, const void* record, hipStream_t st) {
     HN_CHECK_ARG(jobs && block_job && total_blocks > 0 && step >= 1 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && record);
-    return adam_launch(jobs, block_job, total_blocks, lr, beta1, beta2, eps, weight_decay, step, (const GuardRecord*)record, st);
+    return adam_launch(jobs, block_job, total_blocks, lr, beta1, beta2, eps, weight_decay, step, (const GuardRecord*)record, nullptr, 0.0, st);
+}
+/* hn_adam_step (record == NULL) or hn_adam_step_guarded (record given) that also updates one moving average per job in the same launch */
+extern "C" int hn_adam_step_ema(const long* jobs, const int* block_job, long total_blocks, const long* ema, double lr, double beta1,
+                                double beta2, double eps, double weight_decay, long step, double ema_decay, const void* record,
+                                hipStream_t st) {
+    HN_CHECK_ARG(jobs && block_job && total_blocks > 0 && step >= 1 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && ema &&
+                 ema_decay >= 0.0 && ema_decay < 1.0);
+    return adam_launch(jobs, block_job, total_blocks, lr, beta1, beta2, eps, weight_decay, step, (const GuardRecord*)record, ema, ema_decay, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -1418,5 +1462,38 @@ __global__ __launch_bounds__(256) void copy_many_kernel(const long* jobs, const 
 extern "C" int hn_copy_many(const long* jobs, const int* block_job, long total_blocks, int kind, hipStream_t st) {
     HN_CHECK_ARG(jobs && block_job && total_blocks > 0 && kind >= 0 && kind <= 2);
     hipLaunchKernelGGL(copy_many_kernel, dim3((unsigned)total_blocks), dim3(256), 0, st, jobs, block_job, kind);
+    HN_LAUNCH_CHECK();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Many pairs of fp32 tensors exchanged element by element in ONE launch (optim.Adam.swap_ema: the averaged weights in, the live ones out,
+// through the same addresses -- a captured step, the optimizer's tables and the eval-mode caches keep their pointers).  hn_copy_many's
+// tables: jobs (device) n x {a, b, numel, first_block}.  32-bit words are moved, never floats: NaN payloads and -0 survive.  a and b of a
+// job do not overlap; every thread reads its own elements of both before it writes either, and no thread touches another's.
+// ---------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void swap_many_kernel(const long* jobs, const int* block_job) {
+    const long* jb = jobs + (long)block_job[blockIdx.x] * 4;
+    const long n = jb[2];
+    const long i0 = (((long)blockIdx.x - jb[3]) * 256 + threadIdx.x) * 4;
+    if (i0 >= n) return;
+    const int cnt = n - i0 < 4 ? (int)(n - i0) : 4;
+    unsigned* a = reinterpret_cast<unsigned*>(jb[0]) + i0;
+    unsigned* b = reinterpret_cast<unsigned*>(jb[1]) + i0;
+    if (cnt == 4 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0) {
+        const uint4 x = *reinterpret_cast<const uint4*>(a), y = *reinterpret_cast<const uint4*>(b);
+        *reinterpret_cast<uint4*>(a) = y;
+        *reinterpret_cast<uint4*>(b) = x;
+    } else {
+        for (int k = 0; k < cnt; ++k) {
+            const unsigned x = a[k], y = b[k];
+            a[k] = y;
+            b[k] = x;
+        }
+    }
+}
+
+extern "C" int hn_swap_many(const long* jobs, const int* block_job, long total_blocks, hipStream_t st) {
+    HN_CHECK_ARG(jobs && block_job && total_blocks > 0);
+    hipLaunchKernelGGL(swap_many_kernel, dim3((unsigned)total_blocks), dim3(256), 0, st, jobs, block_job);
     HN_LAUNCH_CHECK();
 }

@@ -10,9 +10,15 @@ Opt-in, decided on the device with no host synchronisation (hn_grad_guard + hn_a
 `max_grad_norm` = torch.nn.utils.clip_grad_norm_ over every parameter that has a gradient, in every param group; `skip_nonfinite` = a step
 whose gradient norm (or one of the `losses` handed to step()) is not finite leaves parameters and moments untouched.  With both off, step()
 issues exactly the launches it always did.
+
+Opt-in as well: `ema_decay` keeps an exponential moving average of every stepped parameter, updated INSIDE the Adam launch
+(hn_adam_step_ema: e' = e + (1 - decay) * (p' - e) while the new value p' is in its register), and exchanges averaged and live VALUES in
+place in one launch (hn_swap_many: swap_ema() / averaged()), so that every raw pointer held elsewhere -- a captured training step, the job
+tables here, eval-mode caches -- stays valid.  With ema_decay=None step() issues exactly the launches it issues without the option.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import weakref
 
@@ -22,21 +28,43 @@ from ._lib import lib
 from .ops.core import bump_mutation_epoch, mutation_cells
 
 
+def ema_decay_at(n: int, decay: float, warmup: bool = True) -> float:
+    """the average's decay at its step number n (0-based: the number of EMA steps already issued), in double:
+    min(decay, (1 + n) / (10 + n)) with warm-up -- 0.1 at first, so that a young average follows the weights instead of its start -- else
+    `decay`"""
+    decay = float(decay)
+    return min(decay, (1.0 + n) / (10.0 + n)) if warmup else decay
+
+
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, max_grad_norm=None,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, ema_decay=None, ema_warmup: bool = True):
         """max_grad_norm: clip the global L2 norm of all gradients to it (None or <= 0: off).  The clipping coefficient is applied inside
         the Adam launch: the gradient tensors themselves are NOT modified (no extra pass over them), `p.grad` after step() is what backward
         left.  skip_nonfinite: a non-finite gradient norm or loss skips the step on the device.  On a skipped step the per-parameter
         `step` count (host side; the bias corrections are computed from it on the host in double) and any LR scheduler still advance --
-        torch's GradScaler-style skip would not bump them."""
+        torch's GradScaler-style skip would not bump them.
+        ema_decay (None: off; else 0 <= ema_decay < 1), ema_warmup: the weight average.  `state[p]["ema"]` is created at the parameter's
+        first EMA step as a clone of p taken before that step's update, next to `state[p]["ema_start"]` (a Python int: the parameter's
+        `step` count at that moment), so both travel in state_dict() / load_state_dict(); torch.optim.Adam loads such a state dict and
+        ignores the two keys.  The decay of a step is ema_decay_at(n, ema_decay, ema_warmup), n = the number of EMA steps already issued
+        for the parameter = its `step` count before the update - ema_start: it advances on skipped steps too, as the bias corrections do
+        (the average itself is untouched by a skipped step).  Only tensors that a step's launch actually steps get an average and have
+        it updated: a parameter outside the current param group (a head-only fine-tuning phase), or one without a gradient (the model's
+        four p5_to_p6 tensors never get one), is left alone -- and is not exchanged by swap_ema() unless an earlier phase gave it an
+        average.  BatchNorm running statistics are buffers, not parameters: they are neither averaged nor exchanged."""
         if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or lr < 0.0 or eps < 0.0 or weight_decay < 0.0:
             raise ValueError("invalid Adam hyper-parameter")
         if max_grad_norm is not None and max_grad_norm != max_grad_norm:
             raise ValueError("invalid Adam hyper-parameter")
+        if ema_decay is not None and not 0.0 <= ema_decay < 1.0:
+            raise ValueError("invalid Adam hyper-parameter")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        self._plans = {}                # (group index, step value) -> (pointer signature, jobs, block_job, blocks, parameters)
-        self._fast = {}                 # group index -> (gradient tensors of the last step, shared step scalar, plan)
+        self._plans = {}                # (group index, cohort) -> (pointer signature, jobs, block_job, blocks, parameters, ema pointers)
+        self._fast = {}                 # group index -> (gradient tensors of the last step, shared step scalar, plan, ema_start)
+        self.ema_decay = float(ema_decay) if ema_decay is not None else None
+        self.ema_warmup = bool(ema_warmup)
+        self._swap_plan = None          # (pointer signature, jobs, block_job, blocks, mutation cells) of swap_ema()
         self.max_grad_norm = float(max_grad_norm) if max_grad_norm is not None and max_grad_norm > 0 else None
         self.skip_nonfinite = bool(skip_nonfinite)
         self._guard_plan = None         # (plans of the last guarded step, jobs, block_job, blocks, n_jobs, workspace)
@@ -82,17 +110,23 @@ class Adam(torch.optim.Optimizer):
         self._plans.clear()
         self._fast.clear()
         self._guard_plan = None
+        self._swap_plan = None
 
     def __getstate__(self):
-        return {**super().__getstate__(), "max_grad_norm": self.max_grad_norm, "skip_nonfinite": self.skip_nonfinite}
+        return {**super().__getstate__(), "max_grad_norm": self.max_grad_norm, "skip_nonfinite": self.skip_nonfinite,
+                "ema_decay": self.ema_decay, "ema_warmup": self.ema_warmup}
 
     def __setstate__(self, state):
         super().__setstate__(state)
-        self._plans, self._fast, self._guard_plan = {}, {}, None
+        self._plans, self._fast, self._guard_plan, self._swap_plan = {}, {}, None, None
+        self.__dict__.setdefault("ema_decay", None)
+        self.__dict__.setdefault("ema_warmup", True)
         self._record, self.grad_sq_by_param, self.guard_params = None, None, []    # (a copy counts its own steps)
 
-    def _plan(self, key, ps):
+    def _plan(self, key, ps, ema=False):
         sig = tuple((p.data_ptr(), p.grad.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr()) for p in ps)
+        if ema:
+            sig += tuple(self.state[p]["ema"].data_ptr() for p in ps)
         pl = self._plans.get(key)
         if pl is not None and pl[0] == sig:
             return pl
@@ -104,7 +138,9 @@ class Adam(torch.optim.Optimizer):
             owner += [i] * nb
             blk += nb
         dev = ps[0].device
-        pl = (sig, torch.tensor(rows, dtype=torch.int64).to(dev), torch.tensor(owner, dtype=torch.int32).to(dev), blk, list(ps))
+        # the rows stay 6 wide (hn_grad_guard reads the same tables): the averages' pointers are a table of their own, one per job
+        etab = torch.tensor([self.state[p]["ema"].data_ptr() for p in ps], dtype=torch.int64).to(dev) if ema else None
+        pl = (sig, torch.tensor(rows, dtype=torch.int64).to(dev), torch.tensor(owner, dtype=torch.int32).to(dev), blk, list(ps), etab)
         self._plans[key] = pl
         return pl
 
@@ -114,10 +150,10 @@ class Adam(torch.optim.Optimizer):
         gd = self._guard_plan
         if gd is None or len(gd[0]) != len(plans) or any(a is not b for a, b in zip(gd[0], plans)):
             if len(plans) == 1:
-                _, jobs, owner, blocks, ps = plans[0]
+                _, jobs, owner, blocks, ps, _ = plans[0]
             else:
                 jobs, owner, ps, blocks, nj = [], [], [], 0, 0
-                for _, j, o, b, q in plans:
+                for _, j, o, b, q, _ in plans:
                     j = j.clone()
                     j[:, 5] += blocks
                     jobs.append(j)
@@ -165,16 +201,17 @@ class Adam(torch.optim.Optimizer):
         if getattr(self, "_mut_sig", None) != sig:
             self._mut_sig, self._mut_cells = sig, mutation_cells([p for g in self.param_groups for p in g["params"]])
         bump_mutation_epoch(self._mut_cells)
-        launches = []                   # (plan, lr, beta1, beta2, eps, weight decay, step) in issue order
+        ema = self.ema_decay is not None
+        launches = []                   # (plan, lr, beta1, beta2, eps, weight decay, step, the average's decay or None) in issue order
         for gi, group in enumerate(self.param_groups):
             b1, b2 = group["betas"]
             hyper = (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]))
             fast = self._fast.get(gi)
-            if fast is not None and len(fast[0]) == len(group["params"]) and all((p.grad is None) if g is None else (p.grad is g()) for p, g in zip(group["params"], fast[0])):
+            if fast is not None and (fast[2][5] is not None) == ema and len(fast[0]) == len(group["params"]) and all((p.grad is None) if g is None else (p.grad is g()) for p, g in zip(group["params"], fast[0])):
                 # the same gradient tensors as last time (a captured step rewrites them in place): no per-parameter work on the host
-                _, step_t, plan = fast
+                _, step_t, plan, start = fast
                 step_t += 1
-                launches.append((plan, *hyper, int(step_t)))
+                launches.append((plan, *hyper, int(step_t), ema_decay_at(int(step_t) - 1 - start, self.ema_decay, self.ema_warmup) if ema else None))
                 continue
             by_step = {}
             for p in group["params"]:
@@ -188,25 +225,79 @@ class Adam(torch.optim.Optimizer):
                     st["step"] = torch.zeros((), dtype=torch.float32)                      # host scalar, as torch.optim.Adam keeps it
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                by_step.setdefault(int(st["step"]), []).append(p)
+                if not ema:
+                    by_step.setdefault(int(st["step"]), []).append(p)
+                    continue
+                if "ema" not in st:                                                        # the parameter's first EMA step: the value before it
+                    st["ema"] = p.detach().clone(memory_format=torch.preserve_format)
+                    st["ema_start"] = int(st["step"])
+                    self._swap_plan = None
+                by_step.setdefault((int(st["step"]), int(st["ema_start"])), []).append(p)  # a cohort shares its step count AND its decay
             self._fast.pop(gi, None)
             for t, ps in by_step.items():
+                t, start = t if ema else (t, 0)
                 shared = torch.full((), float(t + 1), dtype=torch.float32)                 # one host scalar for the whole cohort
                 for p in ps:
                     self.state[p]["step"] = shared
-                plan = self._plan((gi, len(by_step) > 1 and t), ps)
-                launches.append((plan, *hyper, t + 1))
+                plan = self._plan((gi, len(by_step) > 1 and ((t, start) if ema else t)), ps, ema)
+                launches.append((plan, *hyper, t + 1, ema_decay_at(t - start, self.ema_decay, self.ema_warmup) if ema else None))
                 if len(by_step) == 1:
                     # weak references: never keep a dropped gradient alive (its address could not be reused by the next backward)
-                    self._fast[gi] = ([None if p.grad is None else weakref.ref(p.grad) for p in group["params"]], shared, plan)
+                    self._fast[gi] = ([None if p.grad is None else weakref.ref(p.grad) for p in group["params"]], shared, plan, start)
         if guarded and launches:
             self._run_guard([l[0] for l in launches], losses, guard_words)
-        for plan, *args in launches:
-            if guarded:
+        for plan, *args, decay in launches:
+            if ema:
+                lib().call("hn_adam_step_ema", plan[1].data_ptr(), plan[2].data_ptr(), plan[3], plan[5].data_ptr(), *args, decay,
+                           self._record.data_ptr() if guarded else None)
+            elif guarded:
                 lib().call("hn_adam_step_guarded", plan[1].data_ptr(), plan[2].data_ptr(), plan[3], *args, self._record.data_ptr())
             else:
                 lib().call("hn_adam_step", plan[1].data_ptr(), plan[2].data_ptr(), plan[3], *args)
         return loss
+
+    # ------------------------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def swap_ema(self):
+        """exchange live and averaged VALUES of every parameter that has an average, in one launch (hn_swap_many): no tensor object and
+        no address changes, so a captured step, the job tables and every cache keyed on a pointer stay valid; eval-mode caches keyed on
+        the values are dropped (the same mutation cells step() bumps, plus those of averaged parameters outside the current param
+        groups).  Calling it twice restores every bit.  Not for use between a captured step's replay and its optimizer step."""
+        ps = [p for p, st in self.state.items() if "ema" in st]
+        if not ps:
+            raise RuntimeError("multitask_hydranet_amd.optim.Adam.swap_ema: no parameter has an average yet (ema_decay, and one step)")
+        sig = tuple((p.data_ptr(), self.state[p]["ema"].data_ptr()) for p in ps)
+        sp = self._swap_plan
+        if sp is None or sp[0] != sig:
+            rows, owner, blk = [], [], 0
+            for i, p in enumerate(ps):
+                e = self.state[p]["ema"]
+                if not (e.is_cuda and e.dtype == torch.float32 and e.is_contiguous() and e.numel() == p.numel() and p.is_contiguous()):
+                    raise RuntimeError("multitask_hydranet_amd.optim.Adam: fp32 contiguous CUDA parameters / averages only")
+                nb = (p.numel() + 1023) // 1024
+                rows.append([p.data_ptr(), e.data_ptr(), p.numel(), blk])
+                owner += [i] * nb
+                blk += nb
+            dev = ps[0].device
+            cells = mutation_cells(ps + [p for g in self.param_groups for p in g["params"]])
+            sp = self._swap_plan = (sig, torch.tensor(rows, dtype=torch.int64).to(dev), torch.tensor(owner, dtype=torch.int32).to(dev), blk, cells)
+        lib().call("hn_swap_many", sp[1].data_ptr(), sp[2].data_ptr(), sp[3])
+        bump_mutation_epoch(sp[4])
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """`with optimizer.averaged():` the parameters hold their averages inside the block and the live values again after it, also
+        when the block raises"""
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
+
+    def ema_named(self, named_parameters) -> dict:
+        """{name: average tensor} of the parameters among `named_parameters` that have an average (the optimizer's own tensors, not
+        copies)"""
+        return {n: self.state[p]["ema"] for n, p in named_parameters if p in self.state and "ema" in self.state[p]}
 
 
 def grad_norms_by_prefix(optimizer: Adam, named_parameters, prefixes):

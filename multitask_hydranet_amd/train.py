@@ -14,6 +14,7 @@ Launch for N GPUs of one node:  python -m torch.distributed.run --nproc-per-node
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import sys
 from typing import Dict, Iterable, Optional
@@ -79,7 +80,11 @@ class HydraTrainer:
         the N > 1 code path on a single GPU (tests; the average over one rank is the identity).
         cfgs["train"]["grad_clip_norm"] / ["skip_nonfinite"] (optional, hip_adam only): global-norm clipping and a non-finite step guard,
         decided on the device inside the Adam step (optim.Adam).  With skip_nonfinite the reference's host-side divergence guard
-        (HydraNet.check_finite) is off: a bad batch is skipped, and train_one_epoch ends the run only when a whole print interval was."""
+        (HydraNet.check_finite) is off: a bad batch is skipped, and train_one_epoch ends the run only when a whole print interval was.
+        cfgs["train"]["ema_decay"] (absent or <= 0: off) / ["ema_warmup"] (default True), hip_adam only: an exponential moving average of
+        the weights, kept inside the Adam launch (optim.Adam); valid() then scores the averaged weights and save(path, ema=True)
+        writes them.  BatchNorm running statistics are not averaged.  Every rank holds the same parameters after the gradient exchange and
+        therefore the same average: nothing is communicated for it."""
         self.cfgs = cfgs
         self.capture_step = capture_step
         self._cap = None                       # (shape key, graph, static batch, static loss dict)
@@ -95,6 +100,11 @@ class HydraTrainer:
         self.skip_nonfinite = bool(t.get("skip_nonfinite", False))
         if (self.grad_clip_norm is not None or self.skip_nonfinite) and not hip_adam:
             raise ValueError("train.grad_clip_norm / train.skip_nonfinite are applied inside the HIP Adam step: they need hip_adam=True")
+        ema = t.get("ema_decay")
+        self.ema_decay = float(ema) if ema is not None and float(ema) > 0 else None
+        self.ema_warmup = bool(t.get("ema_warmup", True))
+        if self.ema_decay is not None and not hip_adam:
+            raise ValueError("train.ema_decay is kept inside the HIP Adam step: it needs hip_adam=True")
         self.trainloader, self.validloader = trainloader, validloader
         self.rank = int(os.environ.get("RANK", "0"))
         self.world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -144,7 +154,8 @@ class HydraTrainer:
         # foreach implementation's ~10 multi-tensor launches (3.9 -> 0.4 ms per step)
         if hip_adam:
             self.optimizer = Adam(self.hydranet.parameters(), self.lr, weight_decay=self.weight_decay, max_grad_norm=self.grad_clip_norm,
-                                  skip_nonfinite=self.skip_nonfinite)
+                                  skip_nonfinite=self.skip_nonfinite, **({} if self.ema_decay is None else
+                                                                         dict(ema_decay=self.ema_decay, ema_warmup=self.ema_warmup)))
         else:
             self.optimizer = torch.optim.Adam(self.hydranet.parameters(), self.lr, weight_decay=self.weight_decay)
         self._guarded = self.grad_clip_norm is not None or self.skip_nonfinite
@@ -390,9 +401,26 @@ class HydraTrainer:
               "  ".join("%s %.3f" % (k, float(v.detach())) for k, v in loss_dict.items()) +
               ("" if guard is None else "  grad_norm %.3f  coef %.3f  skipped %i" % (guard["norm"], guard["coef"], guard["skipped"])))
 
-    @torch.no_grad()
     def valid(self, epoch: int = 0, eval_dir: Optional[str] = None, lane_coder=None, det_conf_thres: float = 0.3, det_iou_thres: float = 0.3,
-              coco_gt=None):
+              coco_gt=None, use_ema: Optional[bool] = None):
+        """_valid() (below) on the live weights or, with use_ema (None: on when train.ema_decay is on and a step has been taken), on the averaged ones: the whole
+        validation loop then runs inside optimizer.averaged(), which exchanges the VALUES of live and averaged parameters in one launch
+        and exchanges them back when the loop ends or raises -- parameter addresses never change, so a captured training step replays
+        correctly afterwards.  BatchNorm running statistics are the live ones either way.  With train.ema_decay on, last_valid["ema"] says which
+        weights were scored."""
+        if use_ema is None:                     # (before the first optimizer step there is no average yet: the live weights)
+            use_ema = self.ema_decay is not None and bool(self.optimizer.ema_named(self.hydranet.named_parameters()))
+        if use_ema and self.ema_decay is None:
+            raise ValueError("valid(use_ema=True) needs train.ema_decay")
+        with (self.optimizer.averaged() if use_ema else contextlib.nullcontext()):
+            scores = self._valid(epoch, eval_dir, lane_coder, det_conf_thres, det_iou_thres, coco_gt)
+        if self.ema_decay is not None:           # (without the option last_valid keeps exactly its keys)
+            self.last_valid["ema"] = use_ema
+        return scores
+
+    @torch.no_grad()
+    def _valid(self, epoch: int = 0, eval_dir: Optional[str] = None, lane_coder=None, det_conf_thres: float = 0.3, det_iou_thres: float = 0.3,
+               coco_gt=None):
         """train.py:271-438 without the third-party evaluators: eval-mode forward + the six losses per batch, streaming mIoU on the device
         (train.py:293-306), detection results through the device post-process in COCO-json form (train.py:308-364; written to
         `eval_dir`/val_bbox_results.json like train.py:416-421 -- the file COCOeval reads), lane decode + NMS on the device and the
@@ -483,11 +511,18 @@ class HydraTrainer:
             self.last_valid["det_eval"] = res
         return scores
 
-    def save(self, path: str):
-        """checkpoint in the reference's format: a DDP-wrapped module's state_dict carries "module." prefixes (train.py:437)"""
+    def save(self, path: str, ema: bool = False):
+        """checkpoint in the reference's format: a DDP-wrapped module's state_dict carries "module." prefixes (train.py:437).  ema: every
+        parameter that has an average (optim.Adam.ema_named) is written as its average; buffers (BatchNorm running statistics among them)
+        and parameters without one as they are.  Nothing is exchanged for it."""
+        if ema and self.ema_decay is None:
+            raise ValueError("save(ema=True) needs train.ema_decay")
         if self.rank != 0:
             return
         sd = self.hydranet.state_dict()
+        if ema:
+            avg = self.optimizer.ema_named(self.hydranet.named_parameters())
+            sd = {k: (avg[k].detach() if k in avg else v) for k, v in sd.items()}
         if self.use_distribute:
             sd = {"module." + k: v for k, v in sd.items()}
         torch.save(sd, path)
