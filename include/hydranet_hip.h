@@ -685,6 +685,27 @@ int hn_copy_many(const long* jobs, const int* block_job, long total_blocks, int 
  * loads and stores; no workgroup waits on another, nothing is allocated or synchronised: graph-capturable. */
 int hn_swap_many(const long* jobs, const int* block_job, long total_blocks, hipStream_t stream);
 
+/* State a training step writes outside the optimizer (BatchNorm running statistics and their batch counters), kept in step with
+ * hn_grad_guard's decision and averaged next to the weights; one launch over many small tensors (hn_state.hip).  jobs (DEVICE) = n x 6
+ * int64 {live, shadow, avg, words, first_block, kind}: `words` counts 32-bit words (an fp32 statistic of C channels: C; an int64 counter:
+ * 2), a block = 256 threads x 4 consecutive words of one job, block_job (DEVICE int32) = job of every block (hn_copy_many's idiom);
+ * kind 0: fp32 values, kind 1: raw words, never read as floats; a shadow / avg pointer of 0: the job has none and is not touched for it.
+ * live, shadow and avg of a job do not overlap, and no tensor appears in two jobs.
+ *   mode 0, snapshot: shadow = live for every job that has a shadow; record and ema_decay are ignored.
+ *   mode 1, settle: record = hn_grad_guard's 32-byte record, written earlier on the same stream, or NULL = "not skipped"; every thread
+ *     reads skip first.  skip != 0: live = shadow for every job that has a shadow, and nothing else is written (averages stay untouched,
+ *     as hn_adam_step_ema leaves e); skip == 0: nothing is written.
+ *   mode 2, settle and average: as mode 1 when skipped; otherwise, for every job that has an average, kind 0: avg' = avg + w * (live -
+ *     avg), w = (float)(1.0 - ema_decay) formed in double on the host and rounded once, subtraction, product and sum each rounded (no fused
+ *     multiply-add; hn_adam_step_ema's formulation), aligned float4s and single elements through one instruction stream; kind 1: avg =
+ *     live (the average of a counter is the counter).
+ * Snapshots and restores move 32-bit words (NaN payloads, -0 and denormals survive), 16 bytes at a time where both pointers allow.
+ * HN_ERR "bad argument", before any HIP call: NULL jobs / block_job, total_blocks outside 1 .. 2^31 - 1, mode outside {0, 1, 2}, and in
+ * mode 2 ema_decay outside [0, 1) (a NaN fails).  Plain vector loads and stores only; no workgroup waits on another, nothing is allocated
+ * or synchronised: graph-capturable. */
+int hn_state_guard(const long* jobs, const int* block_job, long total_blocks, int mode, const void* record, double ema_decay,
+                   hipStream_t stream);
+
 /* COCO box mAP (pycocotools COCOeval(..., 'bbox') evaluate + accumulate; hn_coco.hip, parity rules in its header comment).
  * hn_coco_match: one workgroup per (image, category) cell.  cells (DEVICE int32 [n_cells][4]) = {gt cell = image order * K + category,
  * first detection, detection count, first output record}; dets fp64 [n][5] = x, y, w, h, score (an fp32 value); gt_off int32

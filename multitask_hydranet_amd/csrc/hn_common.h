@@ -24,6 +24,18 @@ __device__ __forceinline__ float bf2f(bf16 v) { return (float)v; }
 __device__ __forceinline__ bf16 f2bf(float v) { return (bf16)v; }
 __device__ __forceinline__ float bfround(float v) { return (float)((bf16)v); }
 
+// A moving average's update __fadd_rn(e, __fmul_rn(w, __fsub_rn(p, e))) with each of the three operations really rounded on its own
+// (hn_adam_step_ema in hn_loss.hip, hn_state_guard in hn_state.hip).  To this compiler the __f*_rn intrinsics are the plain operators,
+// compiled with HIP's default -ffp-contract=fast-honor-pragmas: once inlined, a product and the sum that takes it become one fused
+// multiply-add (seen as a last-bit difference against three numpy float32 operations).  Operators written under the pragma carry no
+// licence to contract, so they stay a subtract, a multiply and an add.
+__device__ __forceinline__ float ema_lerp_rn(float e, float p, float w) {
+#pragma clang fp contract(off)
+    const float d = p - e;
+    const float t = w * d;
+    return e + t;
+}
+
 __device__ __forceinline__ bf16x8 ld8(const bf16* p) { return *reinterpret_cast<const bf16x8*>(p); }
 __device__ __forceinline__ void st8(bf16* p, bf16x8 v) { *reinterpret_cast<bf16x8*>(p) = v; }
 __device__ __forceinline__ bf16x8 zero8() {

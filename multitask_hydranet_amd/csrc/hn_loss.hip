@@ -1186,16 +1186,7 @@ extern "C" int hn_weighted_sum(const void* const* xs, const float* w, const floa
 // The step's decision, written by hn_grad_guard (below) and obeyed by hn_adam_step_guarded: 32 bytes on the device, zeroed once by the caller.
 struct GuardRecord { float norm, coef; int skip, steps, skipped, skipped_consecutive, pad[2]; };
 
-// The average's update __fadd_rn(e, __fmul_rn(w, __fsub_rn(p, e))) with each of the three operations really rounded on its own.  To this
-// compiler the __f*_rn intrinsics are the plain operators, compiled with HIP's default -ffp-contract=fast-honor-pragmas: once inlined, a
-// product and the sum that takes it become one fused multiply-add (seen as a last-bit difference against three numpy float32
-// operations).  Operators written under the pragma carry no licence to contract, so they stay a subtract, a multiply and an add.
-__device__ __forceinline__ float ema_lerp_rn(float e, float p, float w) {
-#pragma clang fp contract(off)
-    const float d = p - e;
-    const float t = w * d;
-    return e + t;
-}
+// (the average's update, ema_lerp_rn: hn_common.h)
 
 // GUARDED = false is hn_adam_step.  GUARDED = true (hn_adam_step_guarded) reads the record first: a flagged step returns before its first
 // store; otherwise the gradient is scaled by the clipping coefficient before the weight-decay term, i.e. clip in place, then step --

@@ -52,7 +52,8 @@ class Adam(torch.optim.Optimizer):
         (the average itself is untouched by a skipped step).  Only tensors that a step's launch actually steps get an average and have
         it updated: a parameter outside the current param group (a head-only fine-tuning phase), or one without a gradient (the model's
         four p5_to_p6 tensors never get one), is left alone -- and is not exchanged by swap_ema() unless an earlier phase gave it an
-        average.  BatchNorm running statistics are buffers, not parameters: they are neither averaged nor exchanged."""
+        average.  BatchNorm running statistics are buffers, not parameters: the optimizer neither averages nor exchanges them
+        (bn_state.BufferKeeper does, next to it)."""
         if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or lr < 0.0 or eps < 0.0 or weight_decay < 0.0:
             raise ValueError("invalid Adam hyper-parameter")
         if max_grad_norm is not None and max_grad_norm != max_grad_norm:

@@ -22,6 +22,7 @@ from typing import Dict, Iterable, Optional
 import torch
 import torch.distributed as dist
 
+from .bn_state import BufferKeeper, options as bn_state_options
 from .ddp import GradReducer, broadcast_state, capture_exchange_step, unused_parameters
 from .metrics import IntersectionOverUnion
 from .model import HydraNet
@@ -83,8 +84,14 @@ class HydraTrainer:
         (HydraNet.check_finite) is off: a bad batch is skipped, and train_one_epoch ends the run only when a whole print interval was.
         cfgs["train"]["ema_decay"] (absent or <= 0: off) / ["ema_warmup"] (default True), hip_adam only: an exponential moving average of
         the weights, kept inside the Adam launch (optim.Adam); valid() then scores the averaged weights and save(path, ema=True)
-        writes them.  BatchNorm running statistics are not averaged.  Every rank holds the same parameters after the gradient exchange and
-        therefore the same average: nothing is communicated for it."""
+        writes them.  Every rank holds the same parameters after the gradient exchange and therefore the same average: nothing is
+        communicated for it.
+        cfgs["train"]["protect_bn_stats"] (needs grad_clip_norm or skip_nonfinite) / ["ema_buffers"] (needs ema_decay), hip_adam only
+        (bn_state.BufferKeeper): the BatchNorm running statistics and batch counters are snapshotted before every forward
+        and restored on the device when the guard skips the step; and they are averaged next to the weights with the same decay
+        schedule, exchanged with them in valid() and written by save(path, ema=True).  Two small launches per step around the (eager or
+        replayed) step; with both keys absent none is issued and `buffer_keeper` stays None.  Every rank keeps its own statistics, as
+        without the keys: nothing is communicated."""
         self.cfgs = cfgs
         self.capture_step = capture_step
         self._cap = None                       # (shape key, graph, static batch, static loss dict)
@@ -105,6 +112,8 @@ class HydraTrainer:
         self.ema_warmup = bool(t.get("ema_warmup", True))
         if self.ema_decay is not None and not hip_adam:
             raise ValueError("train.ema_decay is kept inside the HIP Adam step: it needs hip_adam=True")
+        self.protect_bn_stats, self.ema_buffers = bn_state_options(t, hip_adam)
+        self.buffer_keeper = None              # bn_state.BufferKeeper, built at the first training step when either key is on
         self.trainloader, self.validloader = trainloader, validloader
         self.rank = int(os.environ.get("RANK", "0"))
         self.world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -219,6 +228,14 @@ class HydraTrainer:
             self.optimizer.step(losses=[total_loss.detach()], guard_words=[K_xstage_status_word(self.device)])
         else:
             self.optimizer.step()
+
+    def _keeper(self):
+        """the BufferKeeper of train.protect_bn_stats / train.ema_buffers (None with both off), built at the first training step: the
+        model is on its device by then, and a load_state_dict() since construction is what the shadows and averages start from"""
+        if self.buffer_keeper is None and (self.protect_bn_stats or self.ema_buffers):
+            self.buffer_keeper = BufferKeeper(self.hydranet.named_buffers(), self.protect_bn_stats,
+                                              ema_decay=self.ema_decay if self.ema_buffers else None, ema_warmup=self.ema_warmup)
+        return self.buffer_keeper
 
     def cal_total_loss(self, loss_dict: Dict[str, torch.Tensor]):
         """train.py:192-203: the weighted sum of the task losses (same weights, same association order); on the device it is one launch
@@ -349,6 +366,9 @@ class HydraTrainer:
 
     def _train_step(self, batch_data: dict) -> Dict[str, torch.Tensor]:
         batch_data = self.to_gpu(batch_data)
+        keeper = self._keeper()
+        if keeper is not None:
+            keeper.snapshot()                  # eager, before the forward (or the replay) that writes the running statistics
         if self.capture_step and self._eager_iters >= 2 and self._cap is not None and self._cap[0] != self._batch_sig(batch_data):
             # A different batch shape than the captured one (the loaders' short last batch: drop_last=False, model/train.py:71,81).  The step is
             # NOT captured again on the spot (with the exchange in the graph that would be a second capture of RCCL collectives with no
@@ -358,6 +378,8 @@ class HydraTrainer:
         if self.capture_step and self._eager_iters >= 2:
             loss_dict = self._captured_fwd_bwd(batch_data)
             self._optimizer_step(self._cap[3]["total_loss"])         # (the replayed graph's static tensor)
+            if keeper is not None:
+                keeper.settle(self.optimizer.guard_record)
             self.scheduler.step()
             return loss_dict
         self._eager_iters += 1
@@ -376,6 +398,8 @@ class HydraTrainer:
         if self.reducer is not None:
             self.reducer.finish()
         self._optimizer_step(loss_total)
+        if keeper is not None:
+            keeper.settle(self.optimizer.guard_record)          # a skipped step: the statistics back; a taken one: their average
         self.scheduler.step()
         # detached: the losses are for logging; a caller that keeps them must not keep this iteration's autograd nodes alive (stale
         # AccumulateGrad nodes bound to another stream break a later capture)
@@ -406,13 +430,16 @@ class HydraTrainer:
         """_valid() (below) on the live weights or, with use_ema (None: on when train.ema_decay is on and a step has been taken), on the averaged ones: the whole
         validation loop then runs inside optimizer.averaged(), which exchanges the VALUES of live and averaged parameters in one launch
         and exchanges them back when the loop ends or raises -- parameter addresses never change, so a captured training step replays
-        correctly afterwards.  BatchNorm running statistics are the live ones either way.  With train.ema_decay on, last_valid["ema"] says which
-        weights were scored."""
+        correctly afterwards.  BatchNorm running statistics are the live ones either way, unless train.ema_buffers is on: then the loop
+        also runs inside buffer_keeper.averaged(), with the averaged statistics and counters.  With train.ema_decay on, last_valid["ema"]
+        says which weights were scored."""
         if use_ema is None:                     # (before the first optimizer step there is no average yet: the live weights)
             use_ema = self.ema_decay is not None and bool(self.optimizer.ema_named(self.hydranet.named_parameters()))
         if use_ema and self.ema_decay is None:
             raise ValueError("valid(use_ema=True) needs train.ema_decay")
-        with (self.optimizer.averaged() if use_ema else contextlib.nullcontext()):
+        buffers = self.buffer_keeper if use_ema and self.ema_buffers else None
+        with (self.optimizer.averaged() if use_ema else contextlib.nullcontext()), \
+                (buffers.averaged() if buffers is not None else contextlib.nullcontext()):
             scores = self._valid(epoch, eval_dir, lane_coder, det_conf_thres, det_iou_thres, coco_gt)
         if self.ema_decay is not None:           # (without the option last_valid keeps exactly its keys)
             self.last_valid["ema"] = use_ema
@@ -514,7 +541,8 @@ class HydraTrainer:
     def save(self, path: str, ema: bool = False):
         """checkpoint in the reference's format: a DDP-wrapped module's state_dict carries "module." prefixes (train.py:437).  ema: every
         parameter that has an average (optim.Adam.ema_named) is written as its average; buffers (BatchNorm running statistics among them)
-        and parameters without one as they are.  Nothing is exchanged for it."""
+        and parameters without one as they are -- with train.ema_buffers the BatchNorm running statistics and counters are written as
+        their averages too (buffer_keeper.ema_named).  Nothing is exchanged for it."""
         if ema and self.ema_decay is None:
             raise ValueError("save(ema=True) needs train.ema_decay")
         if self.rank != 0:
@@ -522,6 +550,8 @@ class HydraTrainer:
         sd = self.hydranet.state_dict()
         if ema:
             avg = self.optimizer.ema_named(self.hydranet.named_parameters())
+            if self.buffer_keeper is not None:
+                avg.update(self.buffer_keeper.ema_named())
             sd = {k: (avg[k].detach() if k in avg else v) for k, v in sd.items()}
         if self.use_distribute:
             sd = {"module." + k: v for k, v in sd.items()}
