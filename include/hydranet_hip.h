@@ -706,6 +706,28 @@ int hn_swap_many(const long* jobs, const int* block_job, long total_blocks, hipS
 int hn_state_guard(const long* jobs, const int* block_job, long total_blocks, int mode, const void* record, double ema_decay,
                    hipStream_t stream);
 
+/* Gradient accumulation over several backward passes: the running mean of a group's micro-batch gradients, one launch per micro-batch
+ * over all gradient tensors (hn_accum.hip).  jobs (DEVICE) = n x 4 int64 {g, acc, numel, first_block} in hn_copy_many's layout (fp32
+ * pointers; a block = 256 threads x 4 consecutive elements of one tensor; block_job (DEVICE int32) = job of every block); g and acc of a
+ * job do not overlap and no tensor appears in two jobs.  j = 1-based index of this micro-batch within its group:
+ *   j == 1: acc = g, moved as 32-bit words (NaN payloads, -0 and denormals survive); acc is NOT read.
+ *   j  > 1: acc' = acc + w * (g - acc), w = (float)(1.0 / j) formed in double on the host and rounded once; subtraction, product and sum
+ *           are each rounded (no fused multiply-add; hn_adam_step_ema's formulation).
+ * After every call acc holds the mean of the micro-batches seen so far.  Whole float4s where g and acc are both 16-byte aligned, single
+ * elements otherwise, through one instruction stream: the bits do not depend on alignment.  g is only read.  A NaN or Inf of any
+ * micro-batch leaves a non-finite value in acc at that element.
+ * One thread of block 0, with plain stores: loss_mean[i] (DEVICE float [n_losses]) follows the same rule over losses (HOST array of
+ * n_losses <= 8 DEVICE fp32 scalars, read at launch time into the kernel's arguments, as hn_grad_guard takes them); sticky (DEVICE int32)
+ * = bits when j == 1, else sticky | bits, where bits = 2 if any of losses is not finite, | 4 if any of words (HOST array of n_words <= 4
+ * DEVICE int32 words) is non-zero -- the word to hand to hn_grad_guard's `words` at the group's end.  n_losses == 0 and n_words == 0 are
+ * allowed; loss_mean (n_losses == 0) and sticky (both counts 0) may then be NULL; a non-NULL sticky is written even then.
+ * HN_ERR "bad argument", before any HIP call: NULL jobs / block_job, total_blocks outside 1 .. 2^31 - 1, j < 1, n_losses outside 0 .. 8,
+ * n_words outside 0 .. 4, NULL losses / loss_mean with n_losses > 0, NULL words with n_words > 0, NULL sticky with either count > 0, a
+ * NULL entry of losses / words.  Plain vector loads and stores only; no atomics, no workgroup waits on another, nothing is allocated
+ * or synchronised: graph-capturable (j is baked into a captured launch). */
+int hn_grad_accum(const long* jobs, const int* block_job, long total_blocks, long j, const void* const* losses, int n_losses,
+                  float* loss_mean, const void* const* words, int n_words, int* sticky, hipStream_t stream);
+
 /* COCO box mAP (pycocotools COCOeval(..., 'bbox') evaluate + accumulate; hn_coco.hip, parity rules in its header comment).
  * hn_coco_match: one workgroup per (image, category) cell.  cells (DEVICE int32 [n_cells][4]) = {gt cell = image order * K + category,
  * first detection, detection count, first output record}; dets fp64 [n][5] = x, y, w, h, score (an fp32 value); gt_off int32

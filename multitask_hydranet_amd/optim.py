@@ -124,8 +124,10 @@ class Adam(torch.optim.Optimizer):
         self.__dict__.setdefault("ema_warmup", True)
         self._record, self.grad_sq_by_param, self.guard_params = None, None, []    # (a copy counts its own steps)
 
-    def _plan(self, key, ps, ema=False):
-        sig = tuple((p.data_ptr(), p.grad.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr()) for p in ps)
+    def _plan(self, key, ps, ema=False, gof=None):
+        """gof: parameter -> its gradient tensor (None: p.grad; step(grads=accumulator): the accumulator's view)"""
+        gof = gof or (lambda p: p.grad)
+        sig = tuple((p.data_ptr(), gof(p).data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr()) for p in ps)
         if ema:
             sig += tuple(self.state[p]["ema"].data_ptr() for p in ps)
         pl = self._plans.get(key)
@@ -135,7 +137,7 @@ class Adam(torch.optim.Optimizer):
         for i, p in enumerate(ps):
             st = self.state[p]
             nb = (p.numel() + 1023) // 1024
-            rows.append([p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(), blk])
+            rows.append([p.data_ptr(), gof(p).data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(), blk])
             owner += [i] * nb
             blk += nb
         dev = ps[0].device
@@ -186,9 +188,16 @@ class Adam(torch.optim.Optimizer):
                    self.guard_record.data_ptr())
 
     @torch.no_grad()
-    def step(self, closure=None, *, losses=None, guard_words=None):
+    def step(self, closure=None, *, losses=None, guard_words=None, grads=None):
         """losses: fp32 device scalars whose finiteness the guard checks (skip_nonfinite); guard_words: int32 device words, a non-zero one
-        skips the step (whenever either option is on).  Both need max_grad_norm or skip_nonfinite."""
+        skips the step (whenever either option is on).  Both need max_grad_norm or skip_nonfinite.
+        grads: a GradAccumulator with micro-batches pending -- the step's gradients are the accumulator's means (grads.grad(p)) instead
+        of p.grad: the job tables' g column and the guard's tables point at the accumulator's views, the kernels are the same.  Only
+        parameters that are in the accumulated group are stepped.  p.grad is neither read, rebound nor written (a captured step owns
+        those tensors).  Without it every path is as it always was."""
+        if grads is not None and grads.pending < 1:
+            raise RuntimeError("multitask_hydranet_amd.optim.Adam.step: grads= is an accumulator without a pending micro-batch")
+        gof = (lambda p: p.grad) if grads is None else grads.grad
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -208,7 +217,9 @@ class Adam(torch.optim.Optimizer):
             b1, b2 = group["betas"]
             hyper = (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]))
             fast = self._fast.get(gi)
-            if fast is not None and (fast[2][5] is not None) == ema and len(fast[0]) == len(group["params"]) and all((p.grad is None) if g is None else (p.grad is g()) for p, g in zip(group["params"], fast[0])):
+            if fast is not None and (fast[2][5] is not None) == ema and len(fast[0]) == len(group["params"]) and (
+                    all((p.grad is None) if g is None else (p.grad is g()) for p, g in zip(group["params"], fast[0])) if grads is None else
+                    all((gof(p) is None) if g is None else (gof(p) is g()) for p, g in zip(group["params"], fast[0]))):
                 # the same gradient tensors as last time (a captured step rewrites them in place): no per-parameter work on the host
                 _, step_t, plan, start = fast
                 step_t += 1
@@ -216,10 +227,11 @@ class Adam(torch.optim.Optimizer):
                 continue
             by_step = {}
             for p in group["params"]:
-                if p.grad is None or p.numel() == 0:
+                g = gof(p)
+                if g is None or p.numel() == 0:
                     continue
-                if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.grad.dtype == torch.float32 and
-                        p.grad.is_contiguous() and not p.grad.is_sparse):
+                if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and g.dtype == torch.float32 and
+                        g.is_contiguous() and not g.is_sparse):
                     raise RuntimeError("multitask_hydranet_amd.optim.Adam: fp32 contiguous CUDA parameters / gradients only")
                 st = self.state[p]
                 if not st:
@@ -240,11 +252,11 @@ class Adam(torch.optim.Optimizer):
                 shared = torch.full((), float(t + 1), dtype=torch.float32)                 # one host scalar for the whole cohort
                 for p in ps:
                     self.state[p]["step"] = shared
-                plan = self._plan((gi, len(by_step) > 1 and ((t, start) if ema else t)), ps, ema)
+                plan = self._plan((gi, len(by_step) > 1 and ((t, start) if ema else t)), ps, ema, gof)
                 launches.append((plan, *hyper, t + 1, ema_decay_at(t - start, self.ema_decay, self.ema_warmup) if ema else None))
                 if len(by_step) == 1:
                     # weak references: never keep a dropped gradient alive (its address could not be reused by the next backward)
-                    self._fast[gi] = ([None if p.grad is None else weakref.ref(p.grad) for p in group["params"]], shared, plan, start)
+                    self._fast[gi] = ([None if gof(p) is None else weakref.ref(gof(p)) for p in group["params"]], shared, plan, start)
         if guarded and launches:
             self._run_guard([l[0] for l in launches], losses, guard_words)
         for plan, *args, decay in launches:
@@ -299,6 +311,125 @@ class Adam(torch.optim.Optimizer):
         """{name: average tensor} of the parameters among `named_parameters` that have an average (the optimizer's own tensors, not
         copies)"""
         return {n: self.state[p]["ema"] for n, p in named_parameters if p in self.state and "ema" in self.state[p]}
+
+
+class GradAccumulator:
+    """The running mean of several backward passes' gradients (train.accum_steps; hn_grad_accum, include/hydranet_hip.h).
+
+    add() after every backward folds the parameters' current `p.grad` into the accumulator's own flat fp32 buffer in ONE launch:
+    micro-batch 1 of a group copies (the buffer is not read), micro-batch j gives acc + (g - acc) * (float)(1 / j) in three rounded
+    operations, so the buffer holds the mean of the group so far after every call, and Adam.step(grads=accumulator) can be taken after
+    any number of micro-batches.  `p.grad` is only read: a captured step's static gradients, the eager path's fresh tensors and a
+    reducer's bucket views all serve.  The same launch keeps the means of up to 8 loss scalars and a sticky word (2: a loss of some
+    micro-batch was not finite, 4: a guard word of some micro-batch was raised) to hand to Adam.step(guard_words=[...]) at the group's
+    end.  Nothing is synchronised."""
+
+    def __init__(self, params):
+        ps, seen = [], set()
+        for p in params:
+            if id(p) in seen or p.numel() == 0:
+                continue
+            seen.add(id(p))
+            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+                raise RuntimeError("multitask_hydranet_amd.optim.GradAccumulator: fp32 contiguous CUDA parameters only")
+            ps.append(p)
+        if not ps:
+            raise ValueError("multitask_hydranet_amd.optim.GradAccumulator: no parameters")
+        self.params = ps
+        # every parameter's slot starts on a 16-byte boundary of the flat buffer (ddp.GradReducer._close's layout rule)
+        offs, off = [], 0
+        for p in ps:
+            offs.append(off)
+            off += (p.numel() + 3) // 4 * 4
+        dev = ps[0].device
+        self.flat = torch.zeros(off, device=dev, dtype=torch.float32)
+        self.offsets = offs
+        self._views = {p: self.flat[o:o + p.numel()].view_as(p) for o, p in zip(offs, ps)}
+        self._means = torch.zeros(8, device=dev, dtype=torch.float32)
+        self._sticky = torch.zeros(1, device=dev, dtype=torch.int32)
+        self.pending = 0                # micro-batches in the current group
+        self._n_losses = 0
+        self._member_ids = frozenset()  # the parameters (by id) of the current (or last) group's jobs
+        self._table = None              # (pointer signature, jobs, block_job, blocks)
+        self._fast = None               # weak references to the gradient tensors of the table (None where there was none)
+
+    @property
+    def sticky_word(self) -> torch.Tensor:
+        """int32 [1] on the device: the group's sticky word (written by every add())"""
+        return self._sticky
+
+    def loss_means(self) -> torch.Tensor:
+        """fp32 view of the means of the losses handed to add(), in their order (the accumulator's own memory: clone to keep)"""
+        return self._means[:self._n_losses]
+
+    def grad(self, p):
+        """the accumulator's view for p (p's shape) if p has a job in the current group -- the last one after reset() -- else None"""
+        return self._views[p] if id(p) in self._member_ids else None
+
+    def reset(self):
+        """start a new group: the next add() is micro-batch 1 (and overwrites the buffer without reading it)"""
+        self.pending = 0
+
+    def invalidate(self):
+        """drop the job table (the set of parameters that get gradients changes: another training phase)"""
+        self._table, self._fast = None, None
+
+    def _jobs(self):
+        fast = self._fast
+        # (a dropped gradient's reference is dead: None, which a parameter that lost its gradient must not match)
+        if fast is not None and all((p.grad is None) if g is None else (p.grad is not None and p.grad is g()) for p, g in zip(self.params, fast)):
+            return self._table                                     # a captured step's static gradients, a reducer's bucket views
+        ps = [p for p in self.params if p.grad is not None]
+        if not ps:
+            raise RuntimeError("multitask_hydranet_amd.optim.GradAccumulator.add: no parameter has a gradient")
+        for p in ps:
+            g = p.grad
+            if not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and not g.is_sparse and g.numel() == p.numel()):
+                raise RuntimeError("multitask_hydranet_amd.optim.GradAccumulator: fp32 contiguous CUDA gradients only")
+        ids = frozenset(id(p) for p in ps)
+        if self.pending > 0 and ids != self._member_ids:
+            raise RuntimeError("multitask_hydranet_amd.optim.GradAccumulator.add: the parameters that have a gradient differ from those of "
+                               "the group's first micro-batch")
+        sig = tuple((id(p), p.grad.data_ptr()) for p in ps)
+        tb = self._table
+        if tb is None or tb[0] != sig:                             # (fresh tensors at the old addresses, the eager path's usual case: kept)
+            rows, owner, blk = [], [], 0
+            for i, p in enumerate(ps):
+                nb = (p.numel() + 1023) // 1024
+                rows.append([p.grad.data_ptr(), self._views[p].data_ptr(), p.numel(), blk])
+                owner += [i] * nb
+                blk += nb
+            dev = self.flat.device
+            tb = self._table = (sig, torch.tensor(rows, dtype=torch.int64).to(dev), torch.tensor(owner, dtype=torch.int32).to(dev), blk)
+        self._member_ids = ids
+        # weak references: never keep a dropped gradient alive (its address could not be reused by the next backward)
+        self._fast = [None if p.grad is None else weakref.ref(p.grad) for p in self.params]
+        return tb
+
+    @torch.no_grad()
+    def add(self, losses=None, guard_words=None):
+        """fold the parameters' current gradients in as micro-batch `pending + 1` of the group.  losses: <= 8 fp32 device scalars (the
+        same number in every micro-batch of a group); guard_words: <= 4 int32 device words.  Parameters without a gradient get no job; the
+        set of parameters that have one must not change inside a group."""
+        ls = [t for t in (losses or ()) if t is not None]
+        ws = [t for t in (guard_words or ()) if t is not None]
+        if len(ls) > 8 or len(ws) > 4:
+            raise ValueError("multitask_hydranet_amd.optim.GradAccumulator.add: at most 8 losses and 4 guard words")
+        for t in ls:
+            if not (t.is_cuda and t.dtype == torch.float32 and t.numel() == 1):
+                raise RuntimeError("multitask_hydranet_amd.optim.GradAccumulator.add: losses are fp32 device scalars")
+        for t in ws:
+            if not (t.is_cuda and t.dtype == torch.int32 and t.numel() == 1):
+                raise RuntimeError("multitask_hydranet_amd.optim.GradAccumulator.add: guard_words are int32 device words")
+        if self.pending > 0 and len(ls) != self._n_losses:
+            raise RuntimeError("multitask_hydranet_amd.optim.GradAccumulator.add: the number of losses changed inside a group")
+        _, jobs, owner, blocks = self._jobs()
+        la = (ctypes.c_void_p * max(len(ls), 1))(*[t.data_ptr() for t in ls])
+        wa = (ctypes.c_void_p * max(len(ws), 1))(*[t.data_ptr() for t in ws])
+        lib().call("hn_grad_accum", jobs.data_ptr(), owner.data_ptr(), blocks, self.pending + 1, ctypes.addressof(la), len(ls),
+                   self._means.data_ptr(), ctypes.addressof(wa), len(ws), self._sticky.data_ptr())
+        self._n_losses = len(ls)
+        self.pending += 1
 
 
 def grad_norms_by_prefix(optimizer: Adam, named_parameters, prefixes):

@@ -26,7 +26,7 @@ from .bn_state import BufferKeeper, options as bn_state_options
 from .ddp import GradReducer, broadcast_state, capture_exchange_step, unused_parameters
 from .metrics import IntersectionOverUnion
 from .model import HydraNet
-from .optim import Adam
+from .optim import Adam, GradAccumulator
 
 
 PHASES = ("joint", "lane", "det", "seg")
@@ -46,6 +46,25 @@ def tuning_phase(epoch: int, epoch_all: int, epoch_tuning: int, tuning_turn: int
     if e < epoch_joint + 2 * epoch_tuning:
         return turn, "det"
     return turn, "seg"
+
+
+def accum_options(train_cfg: dict, hip_adam: bool) -> int:
+    """cfgs["train"]["accum_steps"] -> k, the number of micro-batches per optimizer step (absent: 1 = off).  An int >= 1; the
+    accumulated mean is handed to the HIP Adam step (optim.Adam.step(grads=)), so k > 1 needs hip_adam=True."""
+    k = train_cfg.get("accum_steps")
+    if k is None:
+        return 1
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError("train.accum_steps is an integer >= 1, not %r" % (k,))
+    if k > 1 and not hip_adam:
+        raise ValueError("train.accum_steps > 1 steps the HIP Adam on the accumulated gradients: it needs hip_adam=True")
+    return k
+
+
+def optimizer_steps_per_epoch(n_iter: int, k: int) -> int:
+    """optimizer steps of an epoch of n_iter loader batches with k micro-batches per step: ceil(n_iter / k) -- a trailing partial group
+    is stepped at the epoch's end (HydraTrainer.flush_accumulated)"""
+    return (int(n_iter) + int(k) - 1) // int(k)
 
 
 def run_training(trainer: "HydraTrainer", valid_every_epoch: bool = True, log=print):
@@ -91,7 +110,18 @@ class HydraTrainer:
         and restored on the device when the guard skips the step; and they are averaged next to the weights with the same decay
         schedule, exchanged with them in valid() and written by save(path, ema=True).  Two small launches per step around the (eager or
         replayed) step; with both keys absent none is issued and `buffer_keeper` stays None.  Every rank keeps its own statistics, as
-        without the keys: nothing is communicated."""
+        without the keys: nothing is communicated.
+        cfgs["train"]["accum_steps"] = k (absent or 1: off; hip_adam only; optim.GradAccumulator): train_step still takes one
+        loader batch -- a micro-batch -- per call; the optimizer step, the LR step, the weight average's update and the BufferKeeper's
+        settle happen once per group of k micro-batches, on the MEAN of the group's gradients (one hn_grad_accum launch per micro-batch
+        keeps it; train_step returns the group's loss means so far).  train_one_epoch steps a trailing partial group at the epoch's end
+        (flush_accumulated); total_iters counts optimizer steps, so the cosine schedule ends where training ends.  Every micro-batch of
+        a group weighs the same whatever its size (a short last batch included); the detection and lane losses normalise by per-batch
+        positive counts, so k micro-batches of B images are not bit for bit one batch of k * B; BatchNorm statistics are per
+        micro-batch (and are snapshotted once per group: a skipped group restores what they were before its first micro-batch).
+        Data parallel: nothing in the reducer changes -- every micro-batch's backward is a complete exchange and the accumulator reads
+        the exchanged gradients (the mean of the averages is the average of the means), which is k times the traffic of exchanging
+        once per group; that form is not built."""
         self.cfgs = cfgs
         self.capture_step = capture_step
         self._cap = None                       # (shape key, graph, static batch, static loss dict)
@@ -114,6 +144,8 @@ class HydraTrainer:
             raise ValueError("train.ema_decay is kept inside the HIP Adam step: it needs hip_adam=True")
         self.protect_bn_stats, self.ema_buffers = bn_state_options(t, hip_adam)
         self.buffer_keeper = None              # bn_state.BufferKeeper, built at the first training step when either key is on
+        self.accum_steps = accum_options(t, hip_adam)
+        self.accumulator = None                # optim.GradAccumulator when train.accum_steps > 1
         self.trainloader, self.validloader = trainloader, validloader
         self.rank = int(os.environ.get("RANK", "0"))
         self.world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -158,7 +190,7 @@ class HydraTrainer:
 
         self.lr, self.weight_decay, self.epoch = t["lr"], t["weight_decay"], t["epoch"]
         n_iter = iters_per_epoch if iters_per_epoch is not None else (len(trainloader) if hasattr(trainloader, "__len__") else 1)
-        self.total_iters = max(1, n_iter * self.epoch)
+        self.total_iters = max(1, optimizer_steps_per_epoch(n_iter, self.accum_steps) * self.epoch)
         # torch.optim.Adam's update rule and state layout (train.py:147); hip_adam: all 693 tensors in one launch (optim.py) instead of the
         # foreach implementation's ~10 multi-tensor launches (3.9 -> 0.4 ms per step)
         if hip_adam:
@@ -168,6 +200,8 @@ class HydraTrainer:
         else:
             self.optimizer = torch.optim.Adam(self.hydranet.parameters(), self.lr, weight_decay=self.weight_decay)
         self._guarded = self.grad_clip_norm is not None or self.skip_nonfinite
+        if self.accum_steps > 1:
+            self.accumulator = GradAccumulator(self.hydranet.parameters())
         if self.skip_nonfinite:
             # the device guard replaces the reference's host guard (HydraNet._guard: seven synchronising reads of device scalars per step,
             # sys.exit() on the first bad batch): a non-finite step is skipped, and only a whole print interval of them ends the run
@@ -205,11 +239,15 @@ class HydraTrainer:
         assert phase in PHASES
         if self._phase_module(phase) is None:
             raise ValueError("phase %r needs the %s head (cfgs['train'])" % (phase, phase))
+        if self.accumulator is not None and self.accumulator.pending:
+            raise RuntimeError("set_phase with %i accumulated micro-batch(es) pending: call flush_accumulated() first" % self.accumulator.pending)
         self.optimizer.param_groups[0]["params"] = list(self._phase_module(phase).parameters())
         if phase != self.phase:
             self.hydranet.zero_grad(set_to_none=True)               # gradients of parameters leaving the group must not linger (or feed Adam later)
             self._cap = None                                         # a captured step belongs to one phase
             self._eager_iters = 0
+            if self.accumulator is not None:
+                self.accumulator.invalidate()                        # another set of gradients: a fresh job table
             if self.use_distribute:
                 self.reducer.remove()
                 if phase not in self._reducers:
@@ -228,6 +266,53 @@ class HydraTrainer:
             self.optimizer.step(losses=[total_loss.detach()], guard_words=[K_xstage_status_word(self.device)])
         else:
             self.optimizer.step()
+
+    def _finish_step(self, loss_dict: Dict[str, torch.Tensor], keeper, out: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """what follows a forward + backward (eager or replayed, gradients exchanged).  Without train.accum_steps: Adam step, the
+        keeper's settle, LR step, and `out` is returned.  With it: the gradients, the losses and the persistent stage kernels' status
+        word are folded into the accumulator (one launch), and the k-th micro-batch of a group steps on the means; the losses returned
+        are the group's means so far.  loss_dict: tensors that are valid now (a replayed graph's static ones serve)."""
+        acc = self.accumulator
+        if acc is None:
+            self._optimizer_step(loss_dict["total_loss"])
+            if keeper is not None:
+                keeper.settle(self.optimizer.guard_record)          # a skipped step: the statistics back; a taken one: their average
+            self.scheduler.step()
+            return out
+        names = [k for k in loss_dict if k != "total_loss"] + ["total_loss"]       # (the total last: _accumulated_step hands it to the guard)
+        acc.add(losses=[loss_dict[k].detach() for k in names], guard_words=[K_xstage_status_word(self.device)])
+        means = acc.loss_means().clone()                             # (the accumulator's own are rewritten by the next micro-batch)
+        if acc.pending >= self.accum_steps:
+            self._accumulated_step()
+        by_name = {k: means[i] for i, k in enumerate(names)}
+        return {k: by_name[k] for k in loss_dict}
+
+    def _accumulated_step(self):
+        """the optimizer step of a group, on the accumulator's means; the guard sees the group's mean total loss and its sticky word
+        where _optimizer_step hands it the loss and the status word (train.skip_nonfinite at world size 1)"""
+        acc = self.accumulator
+        if self.skip_nonfinite and self.world == 1:
+            self.optimizer.step(grads=acc, losses=[acc.loss_means()[-1:]], guard_words=[K_xstage_status_word(self.device), acc.sticky_word])
+        else:
+            self.optimizer.step(grads=acc)
+        if self.buffer_keeper is not None:
+            self.buffer_keeper.settle(self.optimizer.guard_record)
+        self.scheduler.step()
+        acc.reset()
+
+    def flush_accumulated(self):
+        """step with the micro-batches accumulated so far (a group cut short: the accumulator holds their mean already); a no-op with
+        none pending or without train.accum_steps.  train_one_epoch calls it after its loop, so that a trailing partial group is not
+        carried into the next epoch or phase."""
+        if self.accumulator is None or self.accumulator.pending == 0:
+            return
+        if self._stream is None:
+            return self._accumulated_step()
+        cur = torch.cuda.current_stream()
+        self._stream.wait_stream(cur)
+        with torch.cuda.stream(self._stream):
+            self._accumulated_step()
+        cur.wait_stream(self._stream)
 
     def _keeper(self):
         """the BufferKeeper of train.protect_bn_stats / train.ema_buffers (None with both off), built at the first training step: the
@@ -304,8 +389,9 @@ class HydraTrainer:
     def _batch_sig(batch_data: dict):
         return tuple((k, tuple(v.shape), v.dtype) for k, v in batch_data.items() if isinstance(v, torch.Tensor) and v.is_cuda)
 
-    def _captured_fwd_bwd(self, batch_data: dict) -> Dict[str, torch.Tensor]:
-        """forward + loss + backward (+ the gradient exchange) as one hipGraph replay (built on first use for this batch shape)"""
+    def _captured_fwd_bwd(self, batch_data: dict, clone: bool = True) -> Dict[str, torch.Tensor]:
+        """forward + loss + backward (+ the gradient exchange) as one hipGraph replay (built on first use for this batch shape) -> the
+        losses, as clones of the graph's static tensors, or with clone=False those tensors themselves (valid until the next replay)"""
         keys = [k for k, v in batch_data.items() if isinstance(v, torch.Tensor) and v.is_cuda]
         sig = self._batch_sig(batch_data)
         if self._cap is None or self._cap[0] != sig:
@@ -350,6 +436,8 @@ class HydraTrainer:
         if self.hydranet.check_finite:
             for name, v in loss_dict.items():
                 self.hydranet._guard(v, "cal %s diverge!" % name, allow_zero=name.startswith("loss_det"))
+        if not clone:
+            return loss_dict
         return {k: v.detach().clone() for k, v in loss_dict.items()}      # the static tensors are rewritten by the next replay
 
     def train_step(self, batch_data: dict) -> Dict[str, torch.Tensor]:
@@ -367,7 +455,7 @@ class HydraTrainer:
     def _train_step(self, batch_data: dict) -> Dict[str, torch.Tensor]:
         batch_data = self.to_gpu(batch_data)
         keeper = self._keeper()
-        if keeper is not None:
+        if keeper is not None and (self.accumulator is None or self.accumulator.pending == 0):
             keeper.snapshot()                  # eager, before the forward (or the replay) that writes the running statistics
         if self.capture_step and self._eager_iters >= 2 and self._cap is not None and self._cap[0] != self._batch_sig(batch_data):
             # A different batch shape than the captured one (the loaders' short last batch: drop_last=False, model/train.py:71,81).  The step is
@@ -376,12 +464,9 @@ class HydraTrainer:
             # captures at the shape it sees.
             self._eager_iters = 0
         if self.capture_step and self._eager_iters >= 2:
-            loss_dict = self._captured_fwd_bwd(batch_data)
-            self._optimizer_step(self._cap[3]["total_loss"])         # (the replayed graph's static tensor)
-            if keeper is not None:
-                keeper.settle(self.optimizer.guard_record)
-            self.scheduler.step()
-            return loss_dict
+            # (accumulating: the means are formed from the replayed graph's static tensors, no per-loss clones)
+            loss_dict = self._captured_fwd_bwd(batch_data, clone=self.accumulator is None)
+            return self._finish_step(self._cap[3], keeper, loss_dict)      # (the guard reads the replayed graph's static total loss)
         self._eager_iters += 1
         if self._cap is not None:              # back on the eager path after captured steps: gradients must not stay in the graph's pool
             self.optimizer.zero_grad(set_to_none=True)
@@ -397,13 +482,10 @@ class HydraTrainer:
         loss_total.backward(self._one)
         if self.reducer is not None:
             self.reducer.finish()
-        self._optimizer_step(loss_total)
-        if keeper is not None:
-            keeper.settle(self.optimizer.guard_record)          # a skipped step: the statistics back; a taken one: their average
-        self.scheduler.step()
         # detached: the losses are for logging; a caller that keeps them must not keep this iteration's autograd nodes alive (stale
         # AccumulateGrad nodes bound to another stream break a later capture)
-        return {k: v.detach() for k, v in loss_dict.items()}
+        loss_dict = {k: v.detach() for k, v in loss_dict.items()}
+        return self._finish_step(loss_dict, keeper, loss_dict)
 
     def train_one_epoch(self, epoch: int):
         self.hydranet.train()
@@ -415,9 +497,12 @@ class HydraTrainer:
                 guard = self.optimizer.grad_guard_record() if self._guarded else None
                 if self.rank == 0:
                     self.print_loss_info(loss_dict, epoch, iter_idx, guard=guard)
+                # (the record counts optimizer steps, one per group under train.accum_steps: the run ends after print_interval consecutive
+                # skipped STEPS, that is print_interval * accum_steps micro-batches -- one skipped group never ends it)
                 if guard is not None and guard["skipped_consecutive"] >= self.print_interval:
                     print("training diverged")                   # every step since the last print was skipped
                     sys.exit()
+        self.flush_accumulated()
 
     def print_loss_info(self, loss_dict, epoch, batch_idx, mode="train", guard=None):
         lr = self.optimizer.param_groups[0]["lr"]
