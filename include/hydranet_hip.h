@@ -728,6 +728,33 @@ int hn_state_guard(const long* jobs, const int* block_job, long total_blocks, in
 int hn_grad_accum(const long* jobs, const int* block_job, long total_blocks, long j, const void* const* losses, int n_losses,
                   float* loss_mean, const void* const* words, int n_words, int* sticky, hipStream_t stream);
 
+/* Full-state training checkpoints: many tensors gathered into a staging buffer with a checksum per tensor, verified, and scattered back
+ * in place (hn_ckpt.hip; checkpoint.StatePacker).  jobs (DEVICE) = n_jobs x 4 int64 {src, dst, words, first_block} in hn_copy_many's
+ * layout: `words` counts 32-bit words (an int64 counter is two), a block = 256 threads x 4 consecutive words of one job, block_job
+ * (DEVICE int32 [total_blocks]) = job of every block.  Words are moved, never floats: NaN payloads, -0 and denormals survive.  Whole
+ * 16-byte vectors where a pointer allows and single words otherwise, into the same registers: the bits do not depend on alignment.
+ * src and dst of a job do not overlap, and no dst appears in two jobs.
+ * Checksum of a job with words w[0 .. W-1], each a uint32 zero-extended to 64 bits:
+ *     s1 = sum of w[i] mod 2^64          s2 = sum of (i + 1) * w[i] mod 2^64
+ * Integer arithmetic: the value does not depend on the order of the additions.  Formed without atomics: one {s1, s2} partial per block in
+ * ws (DEVICE, 8-byte aligned, total_blocks * 16 bytes; every block writes its own, so nothing is zeroed by the caller), folded per job by
+ * a second launch of n_jobs workgroups.  sums / expect: DEVICE uint64 [n_jobs][2] = {s1, s2}, 8-byte aligned.
+ *   hn_state_pack:   dst = src for every job; sums receives the checksums of the words read.  src is only read.
+ *   hn_state_verify: no copy; the checksums of the src column go to sums and are compared with expect.  verdict (DEVICE int32 [4]) =
+ *     {number of jobs that differ, index of the first such job or -1, 0, 0}, written in full by every call (a third launch of one
+ *     workgroup): the caller zeroes nothing.
+ *   hn_state_unpack: dst = src for every job -- unless verdict (hn_state_verify's, written earlier on the same stream) is non-NULL and
+ *     verdict[0] != 0: every thread reads it first and returns before its first store, so every dst keeps its bits.
+ *   hn_state_checksum_host: the same {s1, s2} of n_words words of HOST memory (4-byte aligned) into out[2]; a host function, no GPU call.
+ * HN_ERR "bad argument", before any HIP call: NULL jobs / block_job, total_blocks or n_jobs outside 1 .. 2^31 - 1, a NULL or misaligned
+ * ws / sums / expect, a NULL verdict for hn_state_verify; for hn_state_checksum_host n_words < 0, NULL out, NULL words with n_words > 0.
+ * Plain vector loads and stores only; no atomics, no workgroup waits on another, nothing is allocated or synchronised: graph-capturable. */
+int hn_state_pack(const long* jobs, const int* block_job, long total_blocks, long n_jobs, void* ws, void* sums, hipStream_t stream);
+int hn_state_verify(const long* jobs, const int* block_job, long total_blocks, long n_jobs, const void* expect, void* ws, void* sums,
+                    int* verdict, hipStream_t stream);
+int hn_state_unpack(const long* jobs, const int* block_job, long total_blocks, const int* verdict, hipStream_t stream);
+int hn_state_checksum_host(const void* words, long n_words, unsigned long long* out);
+
 /* COCO box mAP (pycocotools COCOeval(..., 'bbox') evaluate + accumulate; hn_coco.hip, parity rules in its header comment).
  * hn_coco_match: one workgroup per (image, category) cell.  cells (DEVICE int32 [n_cells][4]) = {gt cell = image order * K + category,
  * first detection, detection count, first output record}; dets fp64 [n][5] = x, y, w, h, score (an fp32 value); gt_off int32

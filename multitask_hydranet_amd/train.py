@@ -72,15 +72,28 @@ def run_training(trainer: "HydraTrainer", valid_every_epoch: bool = True, log=pr
     t = trainer.cfgs["train"]
     epoch_all = t["epoch"]
     fine = t.get("fine_tuning", False)
-    for epoch in range(epoch_all):
-        if fine:
-            turn, phase = tuning_phase(epoch, epoch_all, t["epoch_tuning"], t["tuning_turn"])
-            log("======= TURN %i %s TRAINING =======" % (turn, phase.upper()))
-            trainer.set_phase(phase)
-        trainer.train_one_epoch(epoch)
-        if valid_every_epoch and trainer.validloader is not None:
-            log("=========================== VALIDATION %i ===========================" % epoch)
-            trainer.valid(epoch)
+    # train.state_file (absent: off): the full training state, written after every train.state_every-th epoch (default 1) and picked up
+    # again when the file exists at the start -- the loop then begins at the file's epoch; this wins over train.continue_train's weights
+    state_file, first = t.get("state_file"), 0
+    state_every = max(1, int(t.get("state_every", 1)))
+    if state_file and os.path.isfile(state_file):
+        first = int(trainer.load_state(state_file)["epoch"])
+        log("======= RESUMED %s: EPOCH %i =======" % (state_file, first))
+    try:
+        for epoch in range(first, epoch_all):
+            if fine:
+                turn, phase = tuning_phase(epoch, epoch_all, t["epoch_tuning"], t["tuning_turn"])
+                log("======= TURN %i %s TRAINING =======" % (turn, phase.upper()))
+                trainer.set_phase(phase)
+            trainer.train_one_epoch(epoch)
+            if state_file and (epoch + 1) % state_every == 0:
+                trainer.save_state(state_file, wait=False, epoch=epoch + 1)       # (the file is written while validation / the next epoch runs)
+            if valid_every_epoch and trainer.validloader is not None:
+                log("=========================== VALIDATION %i ===========================" % epoch)
+                trainer.valid(epoch)
+    finally:
+        if state_file:
+            trainer.checkpoint_wait()
     log("============== finish training ==============")
 
 
@@ -146,6 +159,10 @@ class HydraTrainer:
         self.buffer_keeper = None              # bn_state.BufferKeeper, built at the first training step when either key is on
         self.accum_steps = accum_options(t, hip_adam)
         self.accumulator = None                # optim.GradAccumulator when train.accum_steps > 1
+        self._packer = None                    # checkpoint.StatePacker of save_state / load_state, rebuilt when the set of state tensors changes
+        self._ckpt_thread = None               # the background writer of save_state(wait=False)
+        self._ckpt_error = None
+        self.next_epoch = 0                    # the epoch a state file written now would resume at (run_training / load_state set it)
         self.trainloader, self.validloader = trainloader, validloader
         self.rank = int(os.environ.get("RANK", "0"))
         self.world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -622,6 +639,239 @@ class HydraTrainer:
                     print("\n".join(det_eval.summary()))
             self.last_valid["det_eval"] = res
         return scores
+
+    # ------------------------------------------------------------------------------------------------------------------------------
+    # Full-state checkpoints (checkpoint.py, hn_ckpt.hip)
+    STATE_KEYS = ("grad_clip_norm", "skip_nonfinite", "ema_decay", "ema_warmup", "protect_bn_stats", "ema_buffers", "accum_steps")
+
+    def _state_keys(self) -> dict:
+        """the train keys that shape the state, as this trainer resolved them: a state file loads only where they agree"""
+        return dict(grad_clip_norm=self.grad_clip_norm, skip_nonfinite=self.skip_nonfinite, ema_decay=self.ema_decay,
+                    ema_warmup=self.ema_warmup if self.ema_decay is not None else None, protect_bn_stats=self.protect_bn_stats,
+                    ema_buffers=self.ema_buffers, accum_steps=self.accum_steps)
+
+    def _state_tensors(self):
+        """[(name, tensor)] of everything that travels in a state file's blob, in a fixed order: the model's parameters and persistent
+        buffers ("model/<state_dict key>"), Adam's moments and weight averages ("optim/<parameter>/exp_avg" ...), the guard's record,
+        the BufferKeeper's averages.  The keeper's shadows are rewritten before every forward, gradients and the accumulator's buffer
+        by every group's first micro-batch: they do not travel."""
+        net, opt = self.hydranet, self.optimizer
+        named = [("model/" + k, v.detach()) for k, v in net.state_dict(keep_vars=True).items()]
+        for n, p in net.named_parameters():
+            st = opt.state.get(p)
+            if st:
+                named += [("optim/%s/%s" % (n, k), st[k]) for k in ("exp_avg", "exp_avg_sq", "ema") if k in st]
+        if getattr(opt, "guarded", False):
+            named.append(("guard/record", opt.guard_record))
+        if self.buffer_keeper is not None and self.buffer_keeper.avg is not None:
+            named += [("keeper/avg/" + n, a) for n, a in zip(self.buffer_keeper.names, self.buffer_keeper.avg)]
+        return named
+
+    def _state_packer(self):
+        from .checkpoint import StatePacker
+        named = self._state_tensors()
+        pk = self._packer
+        if pk is None or [n for n, _ in pk.named] != [n for n, _ in named] or any(a is not b and a.data_ptr() != b.data_ptr()
+                                                                                     for (_, a), (_, b) in zip(pk.named, named)):
+            pk = self._packer = StatePacker(named)
+        return pk
+
+    def _host_state(self, epoch: int) -> dict:
+        """what travels in the manifest: JSON values only; floats come back bit for bit (json's shortest round-trip repr)"""
+        opt = self.optimizer
+        per = {}
+        for n, p in self.hydranet.named_parameters():
+            st = opt.state.get(p)
+            if st:
+                per[n] = dict(step=int(st["step"]), **({"ema_start": int(st["ema_start"])} if "ema_start" in st else {}))
+        groups = [{k: (list(v) if isinstance(v, tuple) else v) for k, v in g.items() if k != "params"} for g in opt.param_groups]
+        return dict(epoch=int(epoch), phase=self.phase, train=self._state_keys(), params=per, param_groups=groups,
+                    scheduler=self.scheduler.state_dict(), settles=None if self.buffer_keeper is None else int(self.buffer_keeper.settles),
+                    world=self.world)
+
+    def checkpoint_wait(self):
+        """join a save_state(wait=False) in flight (a no-op without one); an error of the background writer is raised here"""
+        th, self._ckpt_thread = self._ckpt_thread, None
+        if th is not None:
+            th.join()
+        err, self._ckpt_error = self._ckpt_error, None
+        if err is not None:
+            raise err
+
+    def save_state(self, path: str, wait: bool = True, epoch: Optional[int] = None):
+        """the full training state into `path` (checkpoint.py's format): ONE pack launch on the training stream gathers ~3 300 tensors
+        and their checksums into a staging buffer, one device-to-host copy on a side stream follows it, and the file is written from
+        the pinned buffer -- with wait=False by a background thread that launches nothing, while training goes on (later steps write
+        the live tensors, not the staging buffer).  A second save_state, load_state or checkpoint_wait() joins a write in flight
+        first.  epoch: the epoch a resumed run starts at (default: next_epoch).  Only rank 0 writes.  Raises RuntimeError with
+        micro-batches pending in the accumulator (flush_accumulated() first), as set_phase does."""
+        from .checkpoint import write_file
+        if not isinstance(self.optimizer, Adam):
+            raise RuntimeError("save_state carries the HIP Adam's state: it needs hip_adam=True")
+        if self.accumulator is not None and self.accumulator.pending:
+            raise RuntimeError("save_state with %i accumulated micro-batch(es) pending: call flush_accumulated() first" % self.accumulator.pending)
+        self.checkpoint_wait()
+        if epoch is not None:
+            self.next_epoch = int(epoch)
+        if self.rank != 0:
+            return
+        pk = self._state_packer()
+        if self._stream is None:
+            pk.pack()
+        else:                                   # the trainer's own stream, the way flush_accumulated steps on it
+            cur = torch.cuda.current_stream()
+            self._stream.wait_stream(cur)
+            with torch.cuda.stream(self._stream):
+                pk.pack()
+            cur.wait_stream(self._stream)
+        host = self._host_state(self.next_epoch)                     # (now: the thread must not see what later steps make of it)
+
+        def finish():
+            entries, blob = pk.wait_host()                           # an event wait; nothing is launched from here
+            write_file(path, entries, blob, host)
+        if wait:
+            return finish()
+
+        def run():
+            try:
+                finish()
+            except BaseException as e:                               # raised by checkpoint_wait()
+                self._ckpt_error = e
+        import threading
+        self._ckpt_thread = threading.Thread(target=run, name="hydranet-state-writer", daemon=True)
+        self._ckpt_thread.start()
+
+    def load_state(self, path: str) -> dict:
+        """continue from a save_state file: -> its host-side state (["epoch"] = the epoch to run next, also left in next_epoch).
+        The file is read and validated on the host (checkpoint.CheckpointError) and compared with this trainer -- the train keys that
+        shape the state, every tensor's name, shape and dtype: the first difference raises ValueError -- before anything is touched.
+        Then optimizer state (and the BufferKeeper) the file lists is allocated, the blob goes to the device in one copy, is verified
+        there and scattered IN PLACE under the verdict (no tensor object is replaced: captured graphs and cached pointers stay valid).
+        A tensor whose checksum fails raises checkpoint.CheckpointCorrupt naming it, with every device tensor and the optimizer's
+        state dict as they were.  Every rank loads the file (it holds rank 0's BatchNorm statistics, which is what broadcast_state
+        hands out at construction)."""
+        from .checkpoint import CheckpointCorrupt, read_file, _DTYPES
+        if not isinstance(self.optimizer, Adam):
+            raise RuntimeError("load_state carries the HIP Adam's state: it needs hip_adam=True")
+        if self.accumulator is not None and self.accumulator.pending:
+            raise RuntimeError("load_state with %i accumulated micro-batch(es) pending: call flush_accumulated() first" % self.accumulator.pending)
+        self.checkpoint_wait()
+        manifest, blob = read_file(path)
+        host, opt, net = manifest["host"], self.optimizer, self.hydranet
+        # ---- compare: nothing is touched before every check has passed
+        try:
+            theirs, per, phase = host["train"], host["params"], host["phase"]
+            groups, sched, epoch, settles = host["param_groups"], host["scheduler"], int(host["epoch"]), host["settles"]
+        except (KeyError, TypeError, ValueError) as e:
+            raise ValueError("%s: the manifest lacks host-side state (%s)" % (path, e))
+        mine = self._state_keys()
+        for k in self.STATE_KEYS:
+            if theirs.get(k) != mine[k]:
+                raise ValueError("%s was saved with train.%s = %r, this trainer has %r" % (path, k, theirs.get(k), mine[k]))
+        if phase not in PHASES or self._phase_module(phase) is None or len(groups) != len(opt.param_groups):
+            raise ValueError("%s: phase %r / %i param groups do not fit this trainer" % (path, phase, len(groups)))
+        params = dict(net.named_parameters())
+        want = [("model/" + k, v) for k, v in net.state_dict(keep_vars=True).items()]
+        for n, p in params.items():
+            if n in per:
+                want += [("optim/%s/%s" % (n, k), p) for k in ("exp_avg", "exp_avg_sq")]
+                if "ema_start" in per[n]:
+                    want.append(("optim/%s/ema" % n, p))
+        unknown = [n for n in per if n not in params]
+        if unknown:
+            raise ValueError("%s holds optimizer state of %s, which this model does not have" % (path, unknown[0]))
+        if opt.guarded:
+            want.append(("guard/record", torch.empty(8, dtype=torch.int32)))
+        if self.ema_buffers and settles is not None:
+            from .bn_state import SUFFIXES
+            want += [("keeper/avg/" + n, b) for n, b in net.named_buffers() if n.endswith(SUFFIXES)]
+        ents = manifest["tensors"]
+        for i in range(max(len(ents), len(want))):
+            if i >= len(ents) or i >= len(want):
+                raise ValueError("%s: %s" % (path, ("this trainer's state also has %s" % want[i][0]) if i >= len(ents) else
+                                             ("the file also holds %s" % ents[i]["name"])))
+            e, (n, t) = ents[i], want[i]
+            if e["name"] != n:
+                raise ValueError("%s: tensor %i is %s, this trainer's state has %s there" % (path, i, e["name"], n))
+            if tuple(e["shape"]) != tuple(t.shape) or _DTYPES[e["dtype"]] != t.dtype:
+                raise ValueError("%s: %s is %s %s, this trainer's is %s %s" % (path, n, e["dtype"], tuple(e["shape"]), t.dtype, tuple(t.shape)))
+        # ---- allocate what the file lists and this trainer lacks (remembered: a corrupt file takes it away again)
+        made, made_ema = [], []
+        keeper_was, record_was = self.buffer_keeper, opt._record
+        for n, p in params.items():
+            if n not in per:
+                continue
+            st = opt.state[p]
+            if not st:
+                st["step"] = torch.zeros((), dtype=torch.float32)
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                made.append(p)
+            if "ema_start" in per[n] and "ema" not in st:
+                st["ema"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["ema_start"] = int(per[n]["ema_start"])
+                made_ema.append(p)
+        if settles is not None:
+            self._keeper()
+        else:
+            self.buffer_keeper = None           # saved before the first step: the keeper is built at the next one, from the loaded statistics
+        # this trainer's own state that the file does not list leaves only after a good load: keep it aside
+        extra = {p: {k: st.pop(k) for k in ("ema", "ema_start") if k in st} for n, p in params.items()
+                 for st in [opt.state.get(p)] if st and n in per and "ema_start" not in per[n] and "ema" in st}
+        gone = {p: opt.state.pop(p) for n, p in params.items() if n not in per and opt.state.get(p)}
+
+        def undo():
+            for p, st in gone.items():
+                opt.state[p] = st
+            for p, kv in extra.items():
+                opt.state[p].update(kv)
+            fresh = {id(p) for p in made}
+            for p in made_ema:
+                if id(p) not in fresh:
+                    opt.state[p].pop("ema"), opt.state[p].pop("ema_start")
+            for p in made:
+                del opt.state[p]
+            self.buffer_keeper, opt._record = keeper_was, record_was
+            self._packer = None
+        try:
+            pk = self._state_packer()
+            pk.host_blob()[:] = blob
+            if self._stream is None:
+                bad = pk.restore(manifest)
+            else:
+                cur = torch.cuda.current_stream()
+                self._stream.wait_stream(cur)
+                with torch.cuda.stream(self._stream):
+                    bad = pk.restore(manifest)
+                cur.wait_stream(self._stream)
+        except BaseException:
+            undo()
+            raise
+        if bad >= 0:
+            undo()
+            raise CheckpointCorrupt("%s: the words of %s do not give the checksum its manifest records; nothing was loaded" %
+                                    (path, ents[bad]["name"]), tensor=ents[bad]["name"])
+        # ---- the host-side state
+        for n, p in params.items():
+            if n in per:
+                opt.state[p]["step"] = torch.full((), float(per[n]["step"]), dtype=torch.float32)   # (Adam.step's slow path regroups the cohorts)
+                if "ema_start" in per[n]:
+                    opt.state[p]["ema_start"] = int(per[n]["ema_start"])
+        opt._plans.clear()
+        opt._fast.clear()
+        opt._guard_plan = None
+        opt._swap_plan = None
+        self.scheduler.load_state_dict(sched)
+        for g, saved in zip(opt.param_groups, groups):
+            g.update({k: (tuple(v) if k == "betas" else v) for k, v in saved.items()})
+        if self.buffer_keeper is not None and settles is not None:
+            self.buffer_keeper.settles = int(settles)
+        self.set_phase(phase)
+        self.next_epoch = epoch
+        # parameters and statistics were rewritten through raw pointers: eval-mode caches are stale, as after swap_ema()
+        from .ops.core import bump_mutation_epoch, mutation_cells
+        bump_mutation_epoch(mutation_cells(list(net.parameters()) + list(net.buffers())))
+        return host
 
     def save(self, path: str, ema: bool = False):
         """checkpoint in the reference's format: a DDP-wrapped module's state_dict carries "module." prefixes (train.py:437).  ema: every
