@@ -517,6 +517,15 @@ int hn_det_loss_fwd(const float* cls, const float* reg, const float* anchors, co
                     float* part, float* npos, float* out, hipStream_t stream);
 int hn_det_loss_bwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
                     const void* assign, const float* npos, const float* gout, float* dcls, float* dreg, hipStream_t stream);
+/* The same loss with an IoU-family regression term (detection.loss_reg_type; hn_det_iou.hip): kind 1 GIoU, 2 DIoU, 3 CIoU between the
+ * deploy-mode decode of a positive anchor's (dy, dx, dh, dw) (exp clipped at log(1000/16)) and its annotation (sides clamped to >= 1),
+ * per image the mean over its positives, then the batch mean.  Assignment and the classification loss are hn_det_loss_fwd's, bit for bit.
+ * out[0] / out[1] = classification / regression loss, out[2] = mean IoU of the positives (reduced like the loss).  assign: int16 [N][A];
+ * part: fp32 [N][hn_det_loss_blocks(A)][4]; npos: fp32 [N].  gout[2] = gradients of out[0], out[1]. */
+int hn_det_loss_iou_fwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx, int kind,
+                        void* assign, float* part, float* npos, float* out, hipStream_t stream);
+int hn_det_loss_iou_bwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx, int kind,
+                        const void* assign, const float* npos, const float* gout, float* dcls, float* dreg, hipStream_t stream);
 /* torch.argmax(seg, dim=1) of deploy mode (model/model.py:197): fp32 NHWC logits -> int64 class ids, first maximum wins. */
 /* Lane losses (head_lane/lanedetect_loss.py:18-78).  cls: logits / one-hot target fp32 [M][2]; out[0] = positive term, out[1] = OHEM
  * negative term (NEGATIVE_RATIO 15, ALPHA 10: the k-th smallest background log-prob is found by a radix select, not a sort);

@@ -1,0 +1,103 @@
+// The half of the detection loss that does not depend on the regression term: IoU anchor assignment and the focal classification loss
+// (FocalLoss.forward, head_detect/detection_loss.py:132-267).  hn_loss.hip (smooth-L1 regression) and hn_det_iou.hip (GIoU / DIoU / CIoU
+// regression) both build their kernels from these pieces, so the two paths assign and classify with the same instructions.
+#pragma once
+#include "hn_common.h"
+
+#define HN_DET_MAXK 32
+
+// assign: >= 0 matched annotation, -1 background, -2 ignored (IoU: neg < 0.4, pos >= 0.5)
+__device__ __forceinline__ int det_assign(const float* anc, const float* ann, int Mx, float& best_iou) {
+    const float ay1 = anc[0], ax1 = anc[1], ay2 = anc[2], ax2 = anc[3];
+    const float aarea = (ay2 - ay1) * (ax2 - ax1);
+    float best = -1.f;
+    int arg = -1;
+    bool any = false;
+    for (int j = 0; j < Mx; ++j) {
+        const float* b = ann + j * 5;
+        if (b[4] == -1.f) continue;
+        any = true;
+        const float area = (b[2] - b[0]) * (b[3] - b[1]);
+        float iw = fminf(ax2, b[2]) - fmaxf(ax1, b[0]);
+        float ih = fminf(ay2, b[3]) - fmaxf(ay1, b[1]);
+        iw = fmaxf(iw, 0.f);
+        ih = fmaxf(ih, 0.f);
+        float ua = aarea + area - iw * ih;
+        ua = fmaxf(ua, 1e-8f);
+        const float iou = iw * ih / ua;
+        if (iou > best) { best = iou; arg = j; }                      // first maximum wins, like torch.max
+    }
+    best_iou = best;
+    if (!any) return -1;                                              // image without boxes: every anchor is background
+    if (best >= 0.5f) return arg;
+    if (best < 0.4f) return -1;
+    return -2;
+}
+
+// focal BCE (alpha 0.25, gamma 2) of one counted anchor's K probabilities, clamped to [1e-4, 1-1e-4]; cid = its class, -1 for background
+__device__ __forceinline__ float det_focal_sum(const float* c, int K, int cid) {
+    float s = 0.f;
+    for (int k = 0; k < K; ++k) {
+        const float p = fminf(fmaxf(c[k], 1e-4f), 1.f - 1e-4f);
+        if (k == cid) s += 0.25f * (1.f - p) * (1.f - p) * -__logf(p);
+        else s += 0.75f * p * p * -__logf(1.f - p);
+    }
+    return s;
+}
+
+// The classification half of the backward for one anchor: its K probabilities in c[] are replaced by fc * d(focal sum)/dp.  as = the
+// anchor's assignment, cid = its class (-1 for background).  The callers stage the block's 256 x K run through LDS and hand each thread
+// its own row.
+__device__ __forceinline__ void det_focal_grad_row(float* c, int K, int as, int cid, float fc) {
+    for (int k = 0; k < K; ++k) {
+        float g = 0.f;
+        const float p = c[k];
+        if (as != -2 && p > 1e-4f && p < 1.f - 1e-4f) {                // the clamp has zero slope outside its range
+            if (k == cid) g = 0.25f * (2.f * (1.f - p) * __logf(p) - (1.f - p) * (1.f - p) / p);
+            else g = 0.75f * (-2.f * p * __logf(1.f - p) + p * p / (1.f - p));
+        }
+        c[k] = fc * g;
+    }
+}
+
+// One block of 1024 threads folds the forward's partial rows part[N][blocks][COLS] = {cls, reg, #pos[, extra]}.  Per image:
+// cls = sum_cls / max(npos, 1), reg = sum_reg / (REG_PER_POS npos) and extra = sum_extra / npos (both 0 without positives);
+// out[0], out[1][, out[2]] = their batch means; npos kept for the backward.
+// One wave per image (16 images walked one after the other by a single wave took 30 us of dependent load rounds), images beyond 16 in
+// further passes; the batch means are summed in image order by one thread.
+template <int COLS, int REG_PER_POS>
+__global__ __launch_bounds__(1024) void det_loss_finalize_kernel(const float* part, int blocks, int N, float* npos, float* out /* [COLS - 1] */) {
+    static_assert(COLS == 3 || COLS == 4, "partial rows are {cls, reg, #pos} or {cls, reg, #pos, extra}");
+    __shared__ float pc[64], pr[64], px[64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    float tc = 0.f, tr = 0.f, tx = 0.f;
+    for (int n0 = 0; n0 < N; n0 += 16) {
+        const int n = n0 + wave;
+        float c = 0.f, r = 0.f, p = 0.f, x = 0.f;
+        if (n < N)
+            for (int b = lane; b < blocks; b += 64) {
+                const float* q = part + ((long)n * blocks + b) * COLS;
+                c += q[0]; r += q[1]; p += q[2];
+                if (COLS == 4) x += q[3];
+            }
+        c = wave_sum(c); r = wave_sum(r); p = wave_sum(p);
+        if (COLS == 4) x = wave_sum(x);
+        __syncthreads();
+        if (lane == 0 && n < N) {
+            npos[n] = p;
+            pc[wave] = c / fmaxf(p, 1.f);
+            pr[wave] = p > 0.f ? r / ((float)REG_PER_POS * p) : 0.f;
+            if (COLS == 4) px[wave] = p > 0.f ? x / p : 0.f;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int k = 0; k < 16 && n0 + k < N; ++k) {
+                tc += pc[k]; tr += pr[k];
+                if (COLS == 4) tx += px[k];
+            }
+    }
+    if (threadIdx.x == 0) {
+        out[0] = tc / N; out[1] = tr / N;
+        if (COLS == 4) out[2] = tx / N;
+    }
+}

@@ -1,0 +1,178 @@
+// Detection loss with an IoU-family regression term (detection.loss_reg_type = giou | diou | ciou).  Anchor assignment and the focal
+// classification loss are hn_loss.hip's (hn_det_common.h); only the regression term of the positive anchors differs: instead of smooth-L1
+// on (dy, dx, dh, dw) the anchor's prediction is decoded to a box the way deploy mode decodes it (BBoxTransform,
+// head_detect/detection_loss.py:19-33) and compared with its annotation.
+//
+//   predicted box  cy = dy ha + cya, cx = dx wa + cxa, h = exp(min(dh, C)) ha, w = exp(min(dw, C)) wa, C = log(1000/16)
+//   target box     the annotation's centre, gw = max(x2 - x1, 1), gh = max(y2 - y1, 1) (the clamp of the smooth-L1 targets)
+//   iou            inter / union, inter = max(0, iw) max(0, ih), union = w h + gw gh - inter + eps, eps = 1e-7
+//   enclosing box  sides cw, ch
+//   giou (kind 1)  1 - iou + (ac - union) / ac,        ac = cw ch + eps
+//   diou (kind 2)  1 - iou + rho2 / c2,                rho2 = (cx - gcx)^2 + (cy - gcy)^2, c2 = cw^2 + ch^2 + eps
+//   ciou (kind 3)  diou + alpha v,                     v = (4 / pi^2) (atan(gw / gh) - atan(w / h))^2, alpha = v / (1 - iou + v + eps),
+//                                                      alpha a constant in the backward
+//   per image sum_pos / npos (0 without positives), batch mean; the positives' mean iou is reduced the same way (out[2]).
+//
+// Same shape as the smooth-L1 kernels: one thread per (image, anchor), wave sums into per-block partial rows, a one-block finalize; no
+// atomics, a fixed summation order.  The backward recomputes the box from reg / anchors / ann / assign.
+#include "hn_common.h"
+#include "hn_det_common.h"
+
+extern "C" int hn_det_loss_blocks(int A);                             // hn_loss.hip: partial rows per image
+
+#define HN_DET_IOU_EPS 1e-7f
+#define HN_DET_IOU_CLIP 4.135166556742356f                             // log(1000 / 16)
+
+// loss and iou of one positive anchor; with GRAD also g[4] = d loss / d (dy, dx, dh, dw).  The gradient goes through the box corners
+// (x1, y1, x2, y2): a min / max passes it to the side that wins, w h and (for ciou) v add their direct dependence on the sides.
+// exp / atan are the precise ones: a few dozen positives per image pay for them, and the decode must not add error to a loss of ~1e-1.
+template <bool GRAD>
+__device__ __forceinline__ void det_iou_box(const float* r, const float* anc, const float* b, int kind, float& loss, float& iou, float* g) {
+    const float ha = anc[2] - anc[0], wa = anc[3] - anc[1];
+    const float cya = 0.5f * (anc[0] + anc[2]), cxa = 0.5f * (anc[1] + anc[3]);
+    const float cy = r[0] * ha + cya, cx = r[1] * wa + cxa;
+    const float h = expf(fminf(r[2], HN_DET_IOU_CLIP)) * ha, w = expf(fminf(r[3], HN_DET_IOU_CLIP)) * wa;
+    const float px1 = cx - 0.5f * w, px2 = cx + 0.5f * w, py1 = cy - 0.5f * h, py2 = cy + 0.5f * h;
+    float gw = b[2] - b[0], gh = b[3] - b[1];
+    const float gcx = b[0] + 0.5f * gw, gcy = b[1] + 0.5f * gh;
+    gw = fmaxf(gw, 1.f);
+    gh = fmaxf(gh, 1.f);
+    const float tx1 = gcx - 0.5f * gw, tx2 = gcx + 0.5f * gw, ty1 = gcy - 0.5f * gh, ty2 = gcy + 0.5f * gh;
+    const float iw = fminf(px2, tx2) - fmaxf(px1, tx1), ih = fminf(py2, ty2) - fmaxf(py1, ty1);
+    const float iwc = fmaxf(iw, 0.f), ihc = fmaxf(ih, 0.f);
+    const float inter = iwc * ihc;
+    const float uni = w * h + gw * gh - inter + HN_DET_IOU_EPS;
+    iou = inter / uni;
+    const float cw = fmaxf(px2, tx2) - fminf(px1, tx1), ch = fmaxf(py2, ty2) - fminf(py1, ty1);
+    // d loss / d {inter, w h (the predicted area), cw, ch, cx, cy, w, h}: the last four are the direct dependences only
+    float d_inter = -(uni + inter) / (uni * uni), d_area = inter / (uni * uni);
+    float d_cw = 0.f, d_ch = 0.f, d_cx = 0.f, d_cy = 0.f, d_w = 0.f, d_h = 0.f;
+    if (kind == 1) {
+        const float ac = cw * ch + HN_DET_IOU_EPS;
+        loss = 1.f - iou + (ac - uni) / ac;
+        if (GRAD) {
+            d_inter += 1.f / ac;
+            d_area -= 1.f / ac;
+            d_cw = uni / (ac * ac) * ch;
+            d_ch = uni / (ac * ac) * cw;
+        }
+    } else {
+        const float ex = cx - gcx, ey = cy - gcy;
+        const float rho2 = ex * ex + ey * ey;
+        const float c2 = cw * cw + ch * ch + HN_DET_IOU_EPS;
+        loss = 1.f - iou + rho2 / c2;
+        if (GRAD) {
+            d_cx = 2.f * ex / c2;
+            d_cy = 2.f * ey / c2;
+            d_cw = -2.f * rho2 / (c2 * c2) * cw;
+            d_ch = -2.f * rho2 / (c2 * c2) * ch;
+        }
+        if (kind == 3) {
+            const float k4 = 0.40528473456935109f;                     // 4 / pi^2
+            const float da = atanf(gw / gh) - atanf(w / h);
+            const float v = k4 * da * da;
+            const float alpha = v / (1.f - iou + v + HN_DET_IOU_EPS);
+            loss += alpha * v;
+            if (GRAD) {
+                const float s = alpha * 2.f * k4 * da / (w * w + h * h);  // d atan(w / h) = (h dw - w dh) / (w^2 + h^2)
+                d_w = -s * h;
+                d_h = s * w;
+            }
+        }
+    }
+    if (GRAD) {
+        const float d_iw = iw > 0.f ? d_inter * ihc : 0.f, d_ih = ih > 0.f ? d_inter * iwc : 0.f;
+        // iw = min(px2, tx2) - max(px1, tx1), cw = max(px2, tx2) - min(px1, tx1): each corner takes the gradient of the term it decides
+        const float g_x2 = (px2 < tx2 ? d_iw : 0.f) + (px2 > tx2 ? d_cw : 0.f);
+        const float g_x1 = -(px1 > tx1 ? d_iw : 0.f) - (px1 < tx1 ? d_cw : 0.f);
+        const float g_y2 = (py2 < ty2 ? d_ih : 0.f) + (py2 > ty2 ? d_ch : 0.f);
+        const float g_y1 = -(py1 > ty1 ? d_ih : 0.f) - (py1 < ty1 ? d_ch : 0.f);
+        const float G_cx = g_x1 + g_x2 + d_cx, G_cy = g_y1 + g_y2 + d_cy;
+        const float G_w = 0.5f * (g_x2 - g_x1) + d_area * h + d_w, G_h = 0.5f * (g_y2 - g_y1) + d_area * w + d_h;
+        g[0] = G_cy * ha;
+        g[1] = G_cx * wa;
+        g[2] = r[2] <= HN_DET_IOU_CLIP ? G_h * h : 0.f;                 // d h / d dh = h, 0 where the clip is active
+        g[3] = r[3] <= HN_DET_IOU_CLIP ? G_w * w : 0.f;
+    }
+}
+
+__global__ __launch_bounds__(256) void det_loss_iou_fwd_kernel(const float* cls, const float* reg, const float* anchors, const float* ann, int A,
+                                                               int K, int Mx, int kind, short* assign, float* part /* [N][blocks][4] */) {
+    __shared__ float red[4][4];
+    const int n = blockIdx.y;
+    const int a = blockIdx.x * 256 + threadIdx.x;
+    float s_cls = 0.f, s_reg = 0.f, s_pos = 0.f, s_iou = 0.f;
+    if (a < A) {
+        const float* anc = anchors + (long)a * 4;
+        const float* an = ann + (long)n * Mx * 5;
+        float biou;
+        const int as = det_assign(anc, an, Mx, biou);
+        assign[(long)n * A + a] = (short)as;
+        if (as != -2) s_cls = det_focal_sum(cls + ((long)n * A + a) * K, K, as >= 0 ? (int)an[as * 5 + 4] : -1);
+        if (as >= 0) {
+            s_pos = 1.f;
+            det_iou_box<false>(reg + ((long)n * A + a) * 4, anc, an + as * 5, kind, s_reg, s_iou, nullptr);
+        }
+    }
+    s_cls = wave_sum(s_cls); s_reg = wave_sum(s_reg); s_pos = wave_sum(s_pos); s_iou = wave_sum(s_iou);
+    if ((threadIdx.x & 63) == 0) {
+        red[threadIdx.x >> 6][0] = s_cls; red[threadIdx.x >> 6][1] = s_reg; red[threadIdx.x >> 6][2] = s_pos; red[threadIdx.x >> 6][3] = s_iou;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) part[((long)n * gridDim.x + blockIdx.x) * 4 + threadIdx.x] =
+        red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+__global__ __launch_bounds__(256) void det_loss_iou_bwd_kernel(const float* cls, const float* reg, const float* anchors, const float* ann, int N,
+                                                               int A, int K, int Mx, int kind, const short* assign, const float* npos,
+                                                               const float* gout /* [2] */, float* dcls, float* dreg) {
+    // the classification tile moves through LDS as in det_loss_bwd_kernel (hn_loss.hip)
+    extern __shared__ float tile[];                                    // [256][K]
+    const int n = blockIdx.y;
+    const int a0 = blockIdx.x * 256;
+    const int a = a0 + threadIdx.x;
+    const int nv = A - a0 < 256 ? A - a0 : 256;
+    const float* cblk = cls + ((long)n * A + a0) * K;
+    for (int i = threadIdx.x; i < nv * K; i += 256) tile[i] = cblk[i];
+    __syncthreads();
+    const float p_n = npos[n];
+    const float fc = gout[0] / (N * fmaxf(p_n, 1.f));
+    const float fr = p_n > 0.f ? gout[1] / (N * p_n) : 0.f;
+    const int as = a < A ? assign[(long)n * A + a] : -2;
+    const float* an = ann + (long)n * Mx * 5;
+    if (a < A)
+        det_focal_grad_row(tile + threadIdx.x * K, K, as, as >= 0 ? (int)an[as * 5 + 4] : -1, fc);
+    __syncthreads();
+    float* dblk = dcls + ((long)n * A + a0) * K;
+    for (int i = threadIdx.x; i < nv * K; i += 256) dblk[i] = tile[i];
+    if (a >= A) return;
+    float g[4] = {0.f, 0.f, 0.f, 0.f};
+    if (as >= 0) {
+        float loss, iou;
+        det_iou_box<true>(reg + ((long)n * A + a) * 4, anchors + (long)a * 4, an + as * 5, kind, loss, iou, g);
+    }
+    *reinterpret_cast<f32x4*>(dreg + ((long)n * A + a) * 4) = f32x4{fr * g[0], fr * g[1], fr * g[2], fr * g[3]};
+}
+
+// fwd: out[0] = classification loss, out[1] = regression loss, out[2] = mean IoU of the positives (batch means of per-image means);
+// assign int16 [N][A], part fp32 [N][blocks][4], npos fp32 [N]
+extern "C" int hn_det_loss_iou_fwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                                   int kind, void* assign, float* part, float* npos, float* out, hipStream_t st) {
+    HN_CHECK_ARG(cls && reg && anchors && ann && assign && part && npos && out && N > 0 && A > 0 && K > 0 && K <= HN_DET_MAXK && Mx > 0);
+    HN_CHECK_ARG(kind >= 1 && kind <= 3);
+    const int blocks = hn_det_loss_blocks(A);
+    hipLaunchKernelGGL(det_loss_iou_fwd_kernel, dim3(blocks, N), dim3(256), 0, st, cls, reg, anchors, ann, A, K, Mx, kind, (short*)assign, part);
+    hipLaunchKernelGGL((det_loss_finalize_kernel<4, 1>), dim3(1), dim3(1024), 0, st, part, blocks, N, npos, out);
+    HN_LAUNCH_CHECK();
+}
+
+extern "C" int hn_det_loss_iou_bwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                                   int kind, const void* assign, const float* npos, const float* gout, float* dcls, float* dreg,
+                                   hipStream_t st) {
+    HN_CHECK_ARG(cls && reg && anchors && ann && assign && npos && gout && dcls && dreg && N > 0 && A > 0 && K > 0 && Mx > 0);
+    HN_CHECK_ARG(K <= HN_DET_MAXK);                                     // 256 x K floats of LDS
+    HN_CHECK_ARG(kind >= 1 && kind <= 3);
+    hipLaunchKernelGGL(det_loss_iou_bwd_kernel, dim3(hn_det_loss_blocks(A), N), dim3(256), 256 * (size_t)K * sizeof(float), st, cls, reg, anchors,
+                       ann, N, A, K, Mx, kind, (const short*)assign, npos, gout, dcls, dreg);
+    HN_LAUNCH_CHECK();
+}

@@ -4,6 +4,7 @@
 //     so a 3-level (11+11+10 bit) radix select on the fp32 bit pattern replaces the sort: exact, deterministic (integer atomics only).
 //   * deploy-mode argmax over the class logits (model/model.py:197) -> int64 mask.
 #include "hn_common.h"
+#include "hn_det_common.h"      // det_assign, the focal forward / backward, the finalize kernel: shared with hn_det_iou.hip
 
 #define HN_SEG_MAXC 16
 
@@ -387,34 +388,6 @@ __global__ __launch_bounds__(256) void seg_count_ties_kernel(const float* loss, 
 // (dy, dx, dh, dw) averaged over positives x 4; batch mean.  One thread per (image, anchor); the per-image Python loop and the
 // A x M IoU matrix of the reference never exist.  assign[n][a]: >= 0 matched annotation, -1 background, -2 ignored.
 // ---------------------------------------------------------------------------------------------------------
-#define HN_DET_MAXK 32
-__device__ __forceinline__ int det_assign(const float* anc, const float* ann, int Mx, float& best_iou) {
-    const float ay1 = anc[0], ax1 = anc[1], ay2 = anc[2], ax2 = anc[3];
-    const float aarea = (ay2 - ay1) * (ax2 - ax1);
-    float best = -1.f;
-    int arg = -1;
-    bool any = false;
-    for (int j = 0; j < Mx; ++j) {
-        const float* b = ann + j * 5;
-        if (b[4] == -1.f) continue;
-        any = true;
-        const float area = (b[2] - b[0]) * (b[3] - b[1]);
-        float iw = fminf(ax2, b[2]) - fmaxf(ax1, b[0]);
-        float ih = fminf(ay2, b[3]) - fmaxf(ay1, b[1]);
-        iw = fmaxf(iw, 0.f);
-        ih = fmaxf(ih, 0.f);
-        float ua = aarea + area - iw * ih;
-        ua = fmaxf(ua, 1e-8f);
-        const float iou = iw * ih / ua;
-        if (iou > best) { best = iou; arg = j; }                      // first maximum wins, like torch.max
-    }
-    best_iou = best;
-    if (!any) return -1;                                              // image without boxes: every anchor is background
-    if (best >= 0.5f) return arg;
-    if (best < 0.4f) return -1;
-    return -2;
-}
-
 __global__ __launch_bounds__(256) void det_loss_fwd_kernel(const float* cls, const float* reg, const float* anchors, const float* ann, int A,
                                                            int K, int Mx, short* assign, float* part /* [N][blocks][3] */) {
     __shared__ float red[4][3];
@@ -427,15 +400,7 @@ __global__ __launch_bounds__(256) void det_loss_fwd_kernel(const float* cls, con
         float biou;
         const int as = det_assign(anc, an, Mx, biou);
         assign[(long)n * A + a] = (short)as;
-        if (as != -2) {
-            const float* c = cls + ((long)n * A + a) * K;
-            const int cid = as >= 0 ? (int)an[as * 5 + 4] : -1;
-            for (int k = 0; k < K; ++k) {
-                const float p = fminf(fmaxf(c[k], 1e-4f), 1.f - 1e-4f);
-                if (k == cid) s_cls += 0.25f * (1.f - p) * (1.f - p) * -__logf(p);
-                else s_cls += 0.75f * p * p * -__logf(1.f - p);
-            }
-        }
+        if (as != -2) s_cls = det_focal_sum(cls + ((long)n * A + a) * K, K, as >= 0 ? (int)an[as * 5 + 4] : -1);
         if (as >= 0) {
             s_pos = 1.f;
             const float* b = an + as * 5;
@@ -460,35 +425,6 @@ __global__ __launch_bounds__(256) void det_loss_fwd_kernel(const float* cls, con
         red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-// per image: cls = sum_cls / max(npos, 1), reg = sum_reg / max(4 npos, 1) (0 without positives); outputs = batch means; npos kept for bwd
-__global__ __launch_bounds__(1024) void det_loss_finalize_kernel(const float* part, int blocks, int N, float* npos, float* out /* [2] */) {
-    // one wave per image (16 images walked one after the other by a single wave took 30 us of dependent load rounds), images beyond 16
-    // in further passes; the batch means are summed in image order by one thread
-    __shared__ float pc[64], pr[64];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    float tc = 0.f, tr = 0.f;
-    for (int n0 = 0; n0 < N; n0 += 16) {
-        const int n = n0 + wave;
-        float c = 0.f, r = 0.f, p = 0.f;
-        if (n < N)
-            for (int b = lane; b < blocks; b += 64) {
-                const float* q = part + ((long)n * blocks + b) * 3;
-                c += q[0]; r += q[1]; p += q[2];
-            }
-        c = wave_sum(c); r = wave_sum(r); p = wave_sum(p);
-        __syncthreads();
-        if (lane == 0 && n < N) {
-            npos[n] = p;
-            pc[wave] = c / fmaxf(p, 1.f);
-            pr[wave] = p > 0.f ? r / (4.f * p) : 0.f;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0)
-            for (int k = 0; k < 16 && n0 + k < N; ++k) { tc += pc[k]; tr += pr[k]; }
-    }
-    if (threadIdx.x == 0) { out[0] = tc / N; out[1] = tr / N; }
-}
-
 __global__ __launch_bounds__(256) void det_loss_bwd_kernel(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A,
                                                            int K, int Mx, const short* assign, const float* npos, const float* gout /* [2] */,
                                                            float* dcls, float* dreg) {
@@ -507,19 +443,8 @@ __global__ __launch_bounds__(256) void det_loss_bwd_kernel(const float* cls, con
     const float fr = p_n > 0.f ? gout[1] / (N * 4.f * p_n) : 0.f;
     const int as = a < A ? assign[(long)n * A + a] : -2;
     const float* an = ann + (long)n * Mx * 5;
-    if (a < A) {
-        float* c = tile + threadIdx.x * K;                             // (K odd or not: stride-K rows, each thread only touches its own)
-        const int cid = as >= 0 ? (int)an[as * 5 + 4] : -1;
-        for (int k = 0; k < K; ++k) {
-            float g = 0.f;
-            const float p = c[k];
-            if (as != -2 && p > 1e-4f && p < 1.f - 1e-4f) {            // the clamp has zero slope outside its range
-                if (k == cid) g = 0.25f * (2.f * (1.f - p) * __logf(p) - (1.f - p) * (1.f - p) / p);
-                else g = 0.75f * (-2.f * p * __logf(1.f - p) + p * p / (1.f - p));
-            }
-            c[k] = fc * g;
-        }
-    }
+    if (a < A)                                                         // (K odd or not: stride-K rows, each thread only touches its own)
+        det_focal_grad_row(tile + threadIdx.x * K, K, as, as >= 0 ? (int)an[as * 5 + 4] : -1, fc);
     __syncthreads();
     float* dblk = dcls + ((long)n * A + a0) * K;
     for (int i = threadIdx.x; i < nv * K; i += 256) dblk[i] = tile[i];
@@ -759,7 +684,7 @@ extern "C" int hn_det_loss_fwd(const float* cls, const float* reg, const float* 
     HN_CHECK_ARG(cls && reg && anchors && ann && assign && part && npos && out && N > 0 && A > 0 && K > 0 && K <= HN_DET_MAXK && Mx > 0);
     const int blocks = hn_det_loss_blocks(A);
     hipLaunchKernelGGL(det_loss_fwd_kernel, dim3(blocks, N), dim3(256), 0, st, cls, reg, anchors, ann, A, K, Mx, (short*)assign, part);
-    hipLaunchKernelGGL(det_loss_finalize_kernel, dim3(1), dim3(1024), 0, st, part, blocks, N, npos, out);
+    hipLaunchKernelGGL((det_loss_finalize_kernel<3, 4>), dim3(1), dim3(1024), 0, st, part, blocks, N, npos, out);
     HN_LAUNCH_CHECK();
 }
 

@@ -10,6 +10,7 @@ without the shared library raises.
 from __future__ import annotations
 
 import contextlib
+import functools
 import itertools
 import math
 import sys
@@ -127,13 +128,22 @@ class HydraNet(nn.Module):
         self.pack_det_levels = True         # level-packed det towers when every level has a multiple of 128 rows
         self.levels_on_streams = False      # hipGraph branches cost more than they hide on gfx950 (55 vs 43 ms)
         self.grad_scope = None              # "lane" | "det" | "seg": head-only fine-tuning phase (see _forward)
+        self.det_pos_iou = None             # mean IoU of the positive anchors at the last cal_loss under an IoU loss_reg_type (device scalar)
 
         spec = _Spec(self)
         self._declare_backbone(spec)
         self._declare_neck(spec)
         if self.train_detect:
             self._declare_det(spec)
-            self.loss_detect = K.det_loss_hip            # HIP only (losses.det_loss is the torch form the tests use as a reference)
+            # detection.loss_reg_type: the regression term of the positive anchors.  smooth_l1 (or no key) is the reference's loss; giou /
+            # diou / ciou train the decoded box on the overlap measure mAP is made of (ops/losses.py det_iou_loss_hip).  HIP only.
+            self.loss_reg_type = cfgs["detection"].get("loss_reg_type", "smooth_l1")
+            if self.loss_reg_type == "smooth_l1":
+                self.loss_detect = K.det_loss_hip
+            elif self.loss_reg_type in K.DET_IOU_KINDS:
+                self.loss_detect = functools.partial(K.det_iou_loss_hip, kind=self.loss_reg_type)
+            else:
+                raise ValueError("detection.loss_reg_type must be one of 'smooth_l1', 'giou', 'diou', 'ciou', got %r" % (self.loss_reg_type,))
         else:
             self.detectheader, self.loss_detect = None, None
         if self.train_seg:
@@ -873,7 +883,8 @@ class HydraNet(nn.Module):
             ld["loss_seg"] = loss_seg
         if self.train_detect:
             d = pred_dict["detection"]
-            cl, rl = self.loss_detect(d["classification"], d["regression"], d["anchors"], gt_dict["gt_det"])
+            cl, rl, *iou = self.loss_detect(d["classification"], d["regression"], d["anchors"], gt_dict["gt_det"])
+            self.det_pos_iou = iou[0].detach().reshape(()) if iou else None      # (IoU types only: the positives' mean IoU, a device scalar)
             # the reference takes .mean() of the [1]-shaped batch means (model.py:226-227): a reshape for one element
             cl, rl = (cl.reshape(()) if cl.numel() == 1 else cl.mean()), (rl.reshape(()) if rl.numel() == 1 else rl.mean())
             self._guard(cl, "cal det cls loss diverge!", allow_zero=True)

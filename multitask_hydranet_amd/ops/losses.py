@@ -208,6 +208,75 @@ def det_loss_hip(classification, regression, anchors, annotations):
     return DetLoss.apply(classification, regression, anchors, annotations)
 
 
+DET_IOU_KINDS = {"giou": 1, "diou": 2, "ciou": 3}
+
+
+class DetIoULoss(torch.autograd.Function):
+    """DetLoss with an IoU-family regression term (hn_det_iou.hip): (classification loss, regression loss, mean IoU of the positives),
+    all batch means; the third is a diagnostic and not differentiable."""
+
+    @staticmethod
+    def forward(ctx, cls, reg, anchors, ann, kind):
+        n, a, k = cls.shape
+        mx = ann.shape[1]
+        dev = cls.device
+        cls, reg, ann = cls.contiguous(), reg.contiguous(), ann.contiguous().float()
+        anc = anchors.reshape(-1, 4).contiguous()
+        blocks = lib().query("hn_det_loss_blocks", a)
+        assign = torch.empty((n, a), device=dev, dtype=torch.int16)
+        part = torch.empty((n, blocks, 4), device=dev, dtype=F32)
+        npos = torch.empty((n,), device=dev, dtype=F32)
+        out = torch.empty((3,), device=dev, dtype=F32)
+        lib().call("hn_det_loss_iou_fwd", ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, kind, ptr(assign), ptr(part), ptr(npos), ptr(out))
+        ctx.kind = kind
+        ctx.save_for_backward(cls, reg, anc, ann, assign, npos)
+        pos_iou = out[2:3]
+        ctx.mark_non_differentiable(pos_iou)
+        ctx.set_materialize_grads(False)        # (no zero-filled "gradient" of the diagnostic: a fill launch per step)
+        return out[0:1], out[1:2], pos_iou
+
+    @staticmethod
+    def backward(ctx, gcls, greg, _giou):
+        cls, reg, anc, ann, assign, npos = ctx.saved_tensors
+        n, a, k = cls.shape
+        dcls, dreg = torch.empty_like(cls), torch.empty_like(reg)
+        if (gcls is not None and greg is not None and gcls.dtype == F32 and greg.dtype == F32
+                and greg.data_ptr() == gcls.data_ptr() + 4):       # neighbours in WeightedLossSum.backward's gradient vector: used in place
+            g = gcls
+        else:
+            z = zeros((1,), cls.device)
+            g = torch.cat([(gcls if gcls is not None else z).reshape(1).to(F32), (greg if greg is not None else z).reshape(1).to(F32)])
+        lib().call("hn_det_loss_iou_bwd", ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, ann.shape[1], ctx.kind, ptr(assign), ptr(npos), ptr(g),
+                   ptr(dcls), ptr(dreg))
+        return dcls, dreg, None, None, None
+
+
+def det_iou_loss_hip(classification, regression, anchors, annotations, kind):
+    """The detection loss with its regression term replaced by an IoU-family loss; kind = "giou" | "diou" | "ciou".  Returns
+    (classification loss [1], regression loss [1], pos_iou [1]).  Anchor assignment (IoU >= 0.5 positive, < 0.4 background, between
+    ignored, first maximum wins, an image without boxes all background) and the focal classification loss are det_loss_hip's, bit for
+    bit.  For a positive anchor (ay1, ax1, ay2, ax2) with regression (dy, dx, dh, dw) and matched annotation (x1, y1, x2, y2):
+
+      predicted box   the deploy decode (BBoxTransform, head_detect/detection_loss.py:19-33): ha = ay2 - ay1, wa = ax2 - ax1,
+                      cya = (ay1 + ay2) / 2, cxa = (ax1 + ax2) / 2; cy = dy ha + cya, cx = dx wa + cxa; h = exp(min(dh, C)) ha,
+                      w = exp(min(dw, C)) wa with C = log(1000 / 16).  The clip keeps one large dh of a bf16 forward from overflowing
+                      exp and making the loss non-finite; the gradient w.r.t. dh / dw is zero where it is active.
+      target box      the annotation's centre (gcx, gcy) with gw = max(x2 - x1, 1), gh = max(y2 - y1, 1): the smooth-L1 targets' clamp
+      iou             eps = 1e-7; iw, ih = the overlap of the two boxes along x, y; inter = max(0, iw) max(0, ih);
+                      union = w h + gw gh - inter + eps; iou = inter / union
+      enclosing box   the smallest box around both, sides cw, ch
+      giou            ac = cw ch + eps; loss = 1 - iou + (ac - union) / ac
+      diou            rho2 = (cx - gcx)^2 + (cy - gcy)^2; c2 = cw^2 + ch^2 + eps; loss = 1 - iou + rho2 / c2
+      ciou            diou + alpha v; v = (4 / pi^2) (atan(gw / gh) - atan(w / h))^2; alpha = v / (1 - iou + v + eps), a constant in
+                      the backward (the published form)
+
+    Per image the regression loss is sum_pos loss / npos (0 when npos = 0) and the output the mean over the N images: the smooth-L1
+    term's reduction without its x4.  pos_iou is the positives' plain iou reduced the same way (non-differentiable)."""
+    if kind not in DET_IOU_KINDS:
+        raise ValueError(f"kind must be one of {sorted(DET_IOU_KINDS)}, got {kind!r}")
+    return DetIoULoss.apply(classification, regression, anchors, annotations, DET_IOU_KINDS[kind])
+
+
 
 # --------------------------------------------------------------------------------------------------------------
 # Lane losses on the device (head_lane/lanedetect_loss.py:18-78): one workgroup does the OHEM classification loss (log-softmax, counts,
