@@ -526,6 +526,21 @@ int hn_det_loss_iou_fwd(const float* cls, const float* reg, const float* anchors
                         void* assign, float* part, float* npos, float* out, hipStream_t stream);
 int hn_det_loss_iou_bwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx, int kind,
                         const void* assign, const float* npos, const float* gout, float* dcls, float* dreg, hipStream_t stream);
+/* ATSS anchor assignment (detection.assigner = atss; hn_det_atss.hip, the rule is stated there and in ops.det_atss_assign): per box the
+ * topk * anchors_per_location nearest anchors (centre distance, ties to the lower index) on every level are its candidates, the threshold
+ * is mean + std of their IoUs, a candidate at or above it whose centre lies inside the box is positive, conflicts go to the larger IoU.
+ * level_sizes: HOST int [n_levels] (<= 8 levels, read during the call), the contiguous anchor ranges, summing to A; topk *
+ * anchors_per_location <= 1024.  ws: hn_det_atss_ws_bytes(...) bytes (-1 for arguments the call would reject).  Writes assign int16 [N][A]
+ * (>= 0 annotation index, -1 background; never -2) and thr fp32 [N][Mx] (rows of padding annotations are left unwritten).  Three launches. */
+long hn_det_atss_ws_bytes(int N, int A, int Mx, const int* level_sizes, int n_levels, int topk, int anchors_per_location);
+int hn_det_atss_assign(const float* anchors, const float* ann, int N, int A, int Mx, const int* level_sizes, int n_levels, int topk,
+                       int anchors_per_location, void* ws, void* assign, float* thr, hipStream_t stream);
+/* hn_det_loss_fwd / hn_det_loss_iou_fwd with assign [N][A] as an INPUT (e.g. hn_det_atss_assign's) instead of computing the max-IoU
+ * assignment; values outside -2 .. Mx - 1 count as ignored.  The backward entry points above read the same assign. */
+int hn_det_loss_fwd_assigned(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                             const void* assign, float* part, float* npos, float* out, hipStream_t stream);
+int hn_det_loss_iou_fwd_assigned(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                                 int kind, const void* assign, float* part, float* npos, float* out, hipStream_t stream);
 /* torch.argmax(seg, dim=1) of deploy mode (model/model.py:197): fp32 NHWC logits -> int64 class ids, first maximum wins. */
 /* Lane losses (head_lane/lanedetect_loss.py:18-78).  cls: logits / one-hot target fp32 [M][2]; out[0] = positive term, out[1] = OHEM
  * negative term (NEGATIVE_RATIO 15, ALPHA 10: the k-th smallest background log-prob is found by a radix select, not a sort);

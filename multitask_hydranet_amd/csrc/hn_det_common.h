@@ -34,6 +34,10 @@ __device__ __forceinline__ int det_assign(const float* anc, const float* ann, in
     return -2;
 }
 
+// an assignment handed to the loss forward (ATSS, hn_det_atss.hip): anything that is not an annotation index, -1 or -2 counts as ignored,
+// so a stray value never indexes the annotations
+__device__ __forceinline__ int det_given_assign(short v, int Mx) { return v >= -2 && v < Mx ? (int)v : -2; }
+
 // focal BCE (alpha 0.25, gamma 2) of one counted anchor's K probabilities, clamped to [1e-4, 1-1e-4]; cid = its class, -1 for background
 __device__ __forceinline__ float det_focal_sum(const float* c, int K, int cid) {
     float s = 0.f;

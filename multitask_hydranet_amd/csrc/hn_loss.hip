@@ -388,6 +388,8 @@ __global__ __launch_bounds__(256) void seg_count_ties_kernel(const float* loss, 
 // (dy, dx, dh, dw) averaged over positives x 4; batch mean.  One thread per (image, anchor); the per-image Python loop and the
 // A x M IoU matrix of the reference never exist.  assign[n][a]: >= 0 matched annotation, -1 background, -2 ignored.
 // ---------------------------------------------------------------------------------------------------------
+// GIVEN: assign is an input (hn_det_loss_fwd_assigned: ATSS, hn_det_atss.hip) instead of det_assign's output
+template <bool GIVEN>
 __global__ __launch_bounds__(256) void det_loss_fwd_kernel(const float* cls, const float* reg, const float* anchors, const float* ann, int A,
                                                            int K, int Mx, short* assign, float* part /* [N][blocks][3] */) {
     __shared__ float red[4][3];
@@ -397,9 +399,14 @@ __global__ __launch_bounds__(256) void det_loss_fwd_kernel(const float* cls, con
     if (a < A) {
         const float* anc = anchors + (long)a * 4;
         const float* an = ann + (long)n * Mx * 5;
-        float biou;
-        const int as = det_assign(anc, an, Mx, biou);
-        assign[(long)n * A + a] = (short)as;
+        int as;
+        if (GIVEN) {
+            as = det_given_assign(assign[(long)n * A + a], Mx);
+        } else {
+            float biou;
+            as = det_assign(anc, an, Mx, biou);
+            assign[(long)n * A + a] = (short)as;
+        }
         if (as != -2) s_cls = det_focal_sum(cls + ((long)n * A + a) * K, K, as >= 0 ? (int)an[as * 5 + 4] : -1);
         if (as >= 0) {
             s_pos = 1.f;
@@ -683,7 +690,17 @@ extern "C" int hn_det_loss_fwd(const float* cls, const float* reg, const float* 
                                void* assign, float* part, float* npos, float* out, hipStream_t st) {
     HN_CHECK_ARG(cls && reg && anchors && ann && assign && part && npos && out && N > 0 && A > 0 && K > 0 && K <= HN_DET_MAXK && Mx > 0);
     const int blocks = hn_det_loss_blocks(A);
-    hipLaunchKernelGGL(det_loss_fwd_kernel, dim3(blocks, N), dim3(256), 0, st, cls, reg, anchors, ann, A, K, Mx, (short*)assign, part);
+    hipLaunchKernelGGL(det_loss_fwd_kernel<false>, dim3(blocks, N), dim3(256), 0, st, cls, reg, anchors, ann, A, K, Mx, (short*)assign, part);
+    hipLaunchKernelGGL((det_loss_finalize_kernel<3, 4>), dim3(1), dim3(1024), 0, st, part, blocks, N, npos, out);
+    HN_LAUNCH_CHECK();
+}
+
+// hn_det_loss_fwd with assign [N][A] as an INPUT (values outside -2 .. Mx - 1 count as ignored); everything else as above
+extern "C" int hn_det_loss_fwd_assigned(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                                        const void* assign, float* part, float* npos, float* out, hipStream_t st) {
+    HN_CHECK_ARG(cls && reg && anchors && ann && assign && part && npos && out && N > 0 && A > 0 && K > 0 && K <= HN_DET_MAXK && Mx > 0);
+    const int blocks = hn_det_loss_blocks(A);
+    hipLaunchKernelGGL(det_loss_fwd_kernel<true>, dim3(blocks, N), dim3(256), 0, st, cls, reg, anchors, ann, A, K, Mx, (short*)assign, part);
     hipLaunchKernelGGL((det_loss_finalize_kernel<3, 4>), dim3(1), dim3(1024), 0, st, part, blocks, N, npos, out);
     HN_LAUNCH_CHECK();
 }

@@ -144,6 +144,15 @@ class HydraNet(nn.Module):
                 self.loss_detect = functools.partial(K.det_iou_loss_hip, kind=self.loss_reg_type)
             else:
                 raise ValueError("detection.loss_reg_type must be one of 'smooth_l1', 'giou', 'diou', 'ciou', got %r" % (self.loss_reg_type,))
+            # detection.assigner: which anchors are positive.  max_iou (or no key) is the reference's fixed rule (IoU >= 0.5 positive, < 0.4
+            # background, between ignored), computed inside the loss forward; atss picks per box the atss_topk nearest locations of every
+            # level and thresholds their IoUs at mean + std (ops/losses.py det_atss_assign).  Works with every loss_reg_type.  HIP only.
+            self.det_assigner = cfgs["detection"].get("assigner", "max_iou")
+            if self.det_assigner not in ("max_iou", "atss"):
+                raise ValueError("detection.assigner must be one of 'max_iou', 'atss', got %r" % (self.det_assigner,))
+            self.atss_topk = cfgs["detection"].get("atss_topk", 9)
+            if isinstance(self.atss_topk, bool) or not isinstance(self.atss_topk, int) or self.atss_topk < 1:
+                raise ValueError("detection.atss_topk must be an integer >= 1, got %r" % (self.atss_topk,))
         else:
             self.detectheader, self.loss_detect = None, None
         if self.train_seg:
@@ -666,6 +675,22 @@ class HydraNet(nn.Module):
             self._anchor_cache[key] = a
         return self._anchor_cache[key]
 
+    def anchor_level_sizes(self, h, w):
+        """anchors_for's companion: the number of anchors of every pyramid level for the same (h, w), in the order anchors_for stacks them"""
+        d = self.cfgs["detection"]
+        return [(h // 2 ** (lv + 3)) * (w // 2 ** (lv + 3)) * self.anchors_per_location for lv in range(d["pyramid_levels"])]
+
+    def _anchor_hw(self, anchors):
+        """(h, w) of the input an anchors tensor handed out by anchors_for was made for"""
+        for (h, w, _), a in self._anchor_cache.items():
+            if a is anchors or (a.data_ptr() == anchors.data_ptr() and a.shape == anchors.shape):
+                return h, w
+        raise ValueError("detection.assigner = atss needs the anchors tensor of this module's own forward (anchors_for)")
+
+    @property
+    def anchors_per_location(self):
+        return len(self.cfgs["detection"]["scales_factor"]) * 3        # scales x the three aspect ratios of anchors_for
+
     def _streams(self, device, count):
         pool = self._side_streams.setdefault(device, [])
         while len(pool) < count:
@@ -883,7 +908,13 @@ class HydraNet(nn.Module):
             ld["loss_seg"] = loss_seg
         if self.train_detect:
             d = pred_dict["detection"]
-            cl, rl, *iou = self.loss_detect(d["classification"], d["regression"], d["anchors"], gt_dict["gt_det"])
+            if self.det_assigner == "atss":
+                h, w = self._anchor_hw(d["anchors"])
+                assign, _ = K.det_atss_assign(d["anchors"], self.anchor_level_sizes(h, w), gt_dict["gt_det"], self.atss_topk,
+                                              self.anchors_per_location)
+                cl, rl, *iou = self.loss_detect(d["classification"], d["regression"], d["anchors"], gt_dict["gt_det"], assign=assign)
+            else:
+                cl, rl, *iou = self.loss_detect(d["classification"], d["regression"], d["anchors"], gt_dict["gt_det"])
             self.det_pos_iou = iou[0].detach().reshape(()) if iou else None      # (IoU types only: the positives' mean IoU, a device scalar)
             # the reference takes .mean() of the [1]-shaped batch means (model.py:226-227): a reshape for one element
             cl, rl = (cl.reshape(()) if cl.numel() == 1 else cl.mean()), (rl.reshape(()) if rl.numel() == 1 else rl.mean())

@@ -171,18 +171,23 @@ class DetLoss(torch.autograd.Function):
     """returns a 2-vector (classification loss, regression loss), both batch means like FocalLoss.forward."""
 
     @staticmethod
-    def forward(ctx, cls, reg, anchors, ann):
+    def forward(ctx, cls, reg, anchors, ann, given=None):
         n, a, k = cls.shape
         mx = ann.shape[1]
         dev = cls.device
         cls, reg, ann = cls.contiguous(), reg.contiguous(), ann.contiguous().float()
         anc = anchors.reshape(-1, 4).contiguous()
         blocks = lib().query("hn_det_loss_blocks", a)
-        assign = torch.empty((n, a), device=dev, dtype=torch.int16)
         part = torch.empty((n, blocks, 3), device=dev, dtype=F32)
         npos = torch.empty((n,), device=dev, dtype=F32)
         out = torch.empty((2,), device=dev, dtype=F32)
-        lib().call("hn_det_loss_fwd", ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, ptr(assign), ptr(part), ptr(npos), ptr(out))
+        if given is None:
+            assign = torch.empty((n, a), device=dev, dtype=torch.int16)
+            lib().call("hn_det_loss_fwd", ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, ptr(assign), ptr(part), ptr(npos), ptr(out))
+        else:
+            assign = _given_assign(given, n, a, dev)
+            lib().call("hn_det_loss_fwd_assigned", ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, ptr(assign), ptr(part), ptr(npos),
+                       ptr(out))
         ctx.save_for_backward(cls, reg, anc, ann, assign, npos)
         # the two losses leave as two outputs (slicing a 2-vector OUTSIDE the node cost two SliceBackward nodes -- fill + copy each -- and
         # an add per step: seven 5 us launches)
@@ -201,11 +206,61 @@ class DetLoss(torch.autograd.Function):
             g = torch.cat([(gcls if gcls is not None else z).reshape(1).to(F32), (greg if greg is not None else z).reshape(1).to(F32)])
         lib().call("hn_det_loss_bwd", ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, ann.shape[1], ptr(assign), ptr(npos), ptr(g), ptr(dcls),
                    ptr(dreg))
-        return dcls, dreg, None, None
+        return dcls, dreg, None, None, None
 
 
-def det_loss_hip(classification, regression, anchors, annotations):
-    return DetLoss.apply(classification, regression, anchors, annotations)
+def _given_assign(assign, n, a, dev):
+    """an assignment handed to a detection loss: int16 [N, A] on the loss's device"""
+    if assign.dtype != torch.int16 or tuple(assign.shape) != (n, a) or assign.device != dev:
+        raise ValueError(f"assign must be an int16 [{n}, {a}] tensor on {dev}, got {assign.dtype} {tuple(assign.shape)} on {assign.device}")
+    return assign.contiguous()
+
+
+def det_loss_hip(classification, regression, anchors, annotations, assign=None):
+    """assign: None = the reference's max-IoU assignment, computed inside the forward launch; an int16 [N, A] tensor (det_atss_assign's)
+    is read instead (hn_det_loss_fwd_assigned)."""
+    if assign is None:
+        return DetLoss.apply(classification, regression, anchors, annotations)
+    return DetLoss.apply(classification, regression, anchors, annotations, assign)
+
+
+def det_atss_assign(anchors, level_sizes, annotations, topk=9, anchors_per_location=9):
+    """ATSS (adaptive training sample selection) anchor assignment on HIP kernels (hn_det_atss.hip, three launches, no host
+    synchronisation, capturable).  anchors [A, 4] or [1, A, 4] fp32 (y1, x1, y2, x2); level_sizes: the sizes of the contiguous anchor
+    ranges of the pyramid levels (HydraNet.anchor_level_sizes), summing to A; annotations [N, Mx, 5] (x1, y1, x2, y2, class), class -1
+    marks padding.  Returns (assign int16 [N, A]: the matched annotation's index or -1, thr fp32 [N, Mx]: undefined for padding rows).
+
+    The rule, per image:
+      1. An image without valid annotations has every anchor -1 (background).
+      2. Centres: acy = (y1 + y2) * 0.5f, acx = (x1 + x2) * 0.5f of an anchor; gcx = (x1 + x2) * 0.5f, gcy = (y1 + y2) * 0.5f of a box.
+      3. Distance d2 = dx*dx + dy*dy with dx = acx - gcx, dy = acy - gcy; every operation is an individually rounded fp32 operation
+         (no fused multiply-add), so a numpy float32 restatement reproduces it bit for bit.
+      4. Levels are the contiguous anchor ranges given by level_sizes.
+      5. On level l with A_l anchors the candidates of a box are the k_l = min(topk * anchors_per_location, A_l) anchors with the
+         smallest (d2, anchor index): ties in d2 go to the lower index.  The anchors of one location share a centre, so topk counts
+         locations, as in the ATSS authors' code.
+      6. IoU is the max-IoU assignment's formula (inter / max(area_a + area_b - inter, 1e-8)) in fp32.
+      7. Over all of a box's candidates (n = sum of k_l) thr = mean + std of their IoUs; std is unbiased (n - 1), taken in two passes,
+         and 0 when n < 2.
+      8. A candidate is positive for the box when iou >= thr and min(acx - x1, acy - y1, x2 - acx, y2 - acy) > 0.01.
+      9. An anchor positive for several boxes goes to the one with the largest IoU; ties go to the lowest annotation index.
+     10. Every other anchor is -1.  There is no ignore zone: -2 never appears."""
+    anc = anchors.reshape(-1, 4).contiguous()
+    ann = annotations.contiguous().float()
+    if anc.dtype != F32 or ann.dim() != 3 or ann.shape[2] != 5:
+        raise ValueError("anchors must be fp32 [A, 4] and annotations [N, Mx, 5]")
+    n, mx, a, dev = ann.shape[0], ann.shape[1], anc.shape[0], anc.device
+    sizes = (ctypes.c_int * len(level_sizes))(*[int(v) for v in level_sizes])
+    args = (ctypes.addressof(sizes), len(level_sizes), int(topk), int(anchors_per_location))
+    nbytes = lib().query("hn_det_atss_ws_bytes", n, a, mx, *args)
+    if nbytes < 0:
+        raise ValueError(f"det_atss_assign: level_sizes {list(level_sizes)} must be 1..8 positive sizes summing to A = {a}, topk >= 1 and "
+                         f"topk * anchors_per_location <= 1024 (got {topk} * {anchors_per_location})")
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    assign = torch.empty((n, a), device=dev, dtype=torch.int16)
+    thr = torch.empty((n, mx), device=dev, dtype=F32)
+    lib().call("hn_det_atss_assign", ptr(anc), ptr(ann), n, a, mx, *args, ptr(ws), ptr(assign), ptr(thr))
+    return assign, thr
 
 
 DET_IOU_KINDS = {"giou": 1, "diou": 2, "ciou": 3}
@@ -216,18 +271,24 @@ class DetIoULoss(torch.autograd.Function):
     all batch means; the third is a diagnostic and not differentiable."""
 
     @staticmethod
-    def forward(ctx, cls, reg, anchors, ann, kind):
+    def forward(ctx, cls, reg, anchors, ann, kind, given=None):
         n, a, k = cls.shape
         mx = ann.shape[1]
         dev = cls.device
         cls, reg, ann = cls.contiguous(), reg.contiguous(), ann.contiguous().float()
         anc = anchors.reshape(-1, 4).contiguous()
         blocks = lib().query("hn_det_loss_blocks", a)
-        assign = torch.empty((n, a), device=dev, dtype=torch.int16)
         part = torch.empty((n, blocks, 4), device=dev, dtype=F32)
         npos = torch.empty((n,), device=dev, dtype=F32)
         out = torch.empty((3,), device=dev, dtype=F32)
-        lib().call("hn_det_loss_iou_fwd", ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, kind, ptr(assign), ptr(part), ptr(npos), ptr(out))
+        if given is None:
+            assign = torch.empty((n, a), device=dev, dtype=torch.int16)
+            lib().call("hn_det_loss_iou_fwd", ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, kind, ptr(assign), ptr(part), ptr(npos),
+                       ptr(out))
+        else:
+            assign = _given_assign(given, n, a, dev)
+            lib().call("hn_det_loss_iou_fwd_assigned", ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, kind, ptr(assign), ptr(part),
+                       ptr(npos), ptr(out))
         ctx.kind = kind
         ctx.save_for_backward(cls, reg, anc, ann, assign, npos)
         pos_iou = out[2:3]
@@ -248,10 +309,10 @@ class DetIoULoss(torch.autograd.Function):
             g = torch.cat([(gcls if gcls is not None else z).reshape(1).to(F32), (greg if greg is not None else z).reshape(1).to(F32)])
         lib().call("hn_det_loss_iou_bwd", ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, ann.shape[1], ctx.kind, ptr(assign), ptr(npos), ptr(g),
                    ptr(dcls), ptr(dreg))
-        return dcls, dreg, None, None, None
+        return dcls, dreg, None, None, None, None
 
 
-def det_iou_loss_hip(classification, regression, anchors, annotations, kind):
+def det_iou_loss_hip(classification, regression, anchors, annotations, kind, assign=None):
     """The detection loss with its regression term replaced by an IoU-family loss; kind = "giou" | "diou" | "ciou".  Returns
     (classification loss [1], regression loss [1], pos_iou [1]).  Anchor assignment (IoU >= 0.5 positive, < 0.4 background, between
     ignored, first maximum wins, an image without boxes all background) and the focal classification loss are det_loss_hip's, bit for
@@ -271,10 +332,14 @@ def det_iou_loss_hip(classification, regression, anchors, annotations, kind):
                       the backward (the published form)
 
     Per image the regression loss is sum_pos loss / npos (0 when npos = 0) and the output the mean over the N images: the smooth-L1
-    term's reduction without its x4.  pos_iou is the positives' plain iou reduced the same way (non-differentiable)."""
+    term's reduction without its x4.  pos_iou is the positives' plain iou reduced the same way (non-differentiable).
+
+    assign: None = the assignment above; an int16 [N, A] tensor (det_atss_assign's) is read instead (hn_det_loss_iou_fwd_assigned)."""
     if kind not in DET_IOU_KINDS:
         raise ValueError(f"kind must be one of {sorted(DET_IOU_KINDS)}, got {kind!r}")
-    return DetIoULoss.apply(classification, regression, anchors, annotations, DET_IOU_KINDS[kind])
+    if assign is None:
+        return DetIoULoss.apply(classification, regression, anchors, annotations, DET_IOU_KINDS[kind])
+    return DetIoULoss.apply(classification, regression, anchors, annotations, DET_IOU_KINDS[kind], assign)
 
 
 
