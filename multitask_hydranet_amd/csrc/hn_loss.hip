@@ -1083,22 +1083,32 @@ struct WSum {
     const float* x[HN_MAX_LOSS_TERMS]; float w[HN_MAX_LOSS_TERMS]; float gw[HN_MAX_LOSS_TERMS]; int grp[HN_MAX_LOSS_TERMS];
     int n; const float* gout; float* out; float* grads;
 };
+// (plain operators under the pragma, as ema_lerp_rn in hn_common.h: written with __fadd_rn(s, __fmul_rn(x, w)) every product was
+// contracted into the sum that takes it, one rounding instead of two, and the total differed from the reference's in the last bit)
 __global__ void weighted_sum_kernel(const WSum p) {
+#pragma clang fp contract(off)
     if (threadIdx.x != 0) return;
     if (p.out) {
         float tot = 0.f;
         int i = 0;
         while (i < p.n) {
             const int g = p.grp[i];
-            float s = __fmul_rn(p.x[i][0], p.w[i]);
-            for (++i; i < p.n && p.grp[i] == g; ++i) s = __fadd_rn(s, __fmul_rn(p.x[i][0], p.w[i]));
-            tot = __fadd_rn(tot, __fmul_rn(s, p.gw[g]));
+            float s = p.x[i][0] * p.w[i];
+            for (++i; i < p.n && p.grp[i] == g; ++i) {
+                const float t = p.x[i][0] * p.w[i];
+                s = s + t;
+            }
+            const float sg = s * p.gw[g];
+            tot = tot + sg;
         }
         p.out[0] = tot;
     }
     if (p.grads) {
         const float go = p.gout[0];
-        for (int i = 0; i < p.n; ++i) p.grads[i] = __fmul_rn(__fmul_rn(go, p.gw[p.grp[i]]), p.w[i]);
+        for (int i = 0; i < p.n; ++i) {
+            const float gg = go * p.gw[p.grp[i]];
+            p.grads[i] = gg * p.w[i];
+        }
     }
 }
 /* xs: HOST array of n device pointers (one fp32 scalar each); w, gw, grp: HOST arrays (term weight, group weight indexed by group id, group
