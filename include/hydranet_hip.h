@@ -554,6 +554,60 @@ int hn_lane_loc_loss_fwd(const float* pred, const float* target, const void* pma
                          float* rowloss, float* rownorm, float* out, hipStream_t stream);
 int hn_lane_loc_loss_bwd(const float* pred, const float* target, const void* pmask, const float* rownorm, const float* aux,
                          const float* gout, long M, int L, int wcol, float alpha, float* dpred, hipStream_t stream);
+/* Per-image task masks (gt_dict["task_valid"], DESIGN 4u): every loss entry point above has a `_masked` twin that also takes `valid`, one
+ * contiguous uint8 row of N bytes on the device (1 = image n is labelled for the task; NULL returns 1 before any launch).  The rule: the
+ * losses equal the unmasked losses of the sub-batch of labelled images, taken in batch order; without a labelled image every loss is 0;
+ * the gradient with respect to an unlabelled image's predictions is written as exactly 0.  The same kernels and the same number of
+ * launches as the unmasked call; the mask is read on the device (no synchronisation, capturable); an all-ones mask gives the unmasked
+ * call's bits.
+ *   seg CE / top-k: sum over labelled images of their top-k sums / (N_valid k); focal: the mean over N_valid HW pixels; Lovasz: an
+ *     unlabelled image's pixels are dropped like ignored pixels.  The workspaces are the unmasked calls' and go to the matching bwd.
+ *   det: an unlabelled image's anchors are all ignored (its row of a computed assign is -2 throughout, npos = 0; a given assign is read
+ *     only for labelled images and never written); the batch means, out[2] included, are taken over N_valid.  bwd takes the same mask.
+ *   lane cls: M = N x rows; the rows of an unlabelled image are neither positive nor negative: they stay out of #pos, #neg, the rank, the
+ *     select and both sums (lsm is still written, pmask is 0).  M % rows != 0 returns 1.  The location loss follows through pmask and aux
+ *     and needs no twin. */
+int hn_seg_loss_fwd_masked(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* class_weights,
+                           int ignore_index, int N, long HW, int use_topk, long k, const unsigned char* valid, void* ws, float* out,
+                           hipStream_t stream);
+int hn_seg_loss_bwd_masked(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* class_weights,
+                           int ignore_index, int N, long HW, int use_topk, long k, const unsigned char* valid, const void* ws,
+                           const float* gout, float* dlogits, int ldd, hipStream_t stream);
+int hn_seg_loss_bwd_s2d_masked(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* class_weights,
+                               int ignore_index, int N, int H, int W, int use_topk, long k, const unsigned char* valid, const void* ws,
+                               const float* gout, void* dz, int ldz, hipStream_t stream);
+int hn_seg_focal_fwd_masked(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* class_weights,
+                            float gamma, float alpha, int N, long HW, const unsigned char* valid, void* ws, float* out, hipStream_t stream);
+int hn_seg_focal_bwd_masked(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* class_weights,
+                            float gamma, float alpha, int N, long HW, const unsigned char* valid, const float* gout, float* dlogits, int ldd,
+                            hipStream_t stream);
+int hn_seg_lovasz_fwd_masked(const float* logits, int ldl, int C, const void* target, int target_is_float, int ignore_index, int N, long HW,
+                             const unsigned char* valid, void* ws, float* out, hipStream_t stream);
+int hn_seg_lovasz_bwd_masked(const float* logits, int ldl, int C, const void* target, int target_is_float, int ignore_index, int N, long HW,
+                             const unsigned char* valid, const void* ws, const float* gout, float* dlogits, int ldd, hipStream_t stream);
+int hn_seg_lovasz_bwd_s2d_masked(const float* logits, int ldl, int C, const void* target, int target_is_float, int ignore_index, int N,
+                                 int H, int W, const unsigned char* valid, const void* ws, const float* gout, void* dz, int ldz,
+                                 hipStream_t stream);
+int hn_det_loss_fwd_masked(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                           const unsigned char* valid, void* assign, float* part, float* npos, float* out, hipStream_t stream);
+int hn_det_loss_fwd_assigned_masked(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                                    const unsigned char* valid, const void* assign, float* part, float* npos, float* out,
+                                    hipStream_t stream);
+int hn_det_loss_bwd_masked(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                           const unsigned char* valid, const void* assign, const float* npos, const float* gout, float* dcls, float* dreg,
+                           hipStream_t stream);
+int hn_det_loss_iou_fwd_masked(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                               int kind, const unsigned char* valid, void* assign, float* part, float* npos, float* out, hipStream_t stream);
+int hn_det_loss_iou_fwd_assigned_masked(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K,
+                                        int Mx, int kind, const unsigned char* valid, const void* assign, float* part, float* npos,
+                                        float* out, hipStream_t stream);
+int hn_det_loss_iou_bwd_masked(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                               int kind, const unsigned char* valid, const void* assign, const float* npos, const float* gout, float* dcls,
+                               float* dreg, hipStream_t stream);
+int hn_lane_cls_loss_fwd_masked(const float* logits, const float* target, long M, int rows, const unsigned char* valid, float neg_ratio,
+                                float alpha, float* lsm, void* pmask, float* out, float* aux, hipStream_t stream);
+int hn_lane_cls_loss_bwd_masked(const float* lsm, const void* pmask, const float* aux, const float* gpos, const float* gneg, float alpha,
+                                long M, int rows, const unsigned char* valid, float* dlogits, hipStream_t stream);
 /* Greedy NMS on the device for the detection post-process (head_detect/detection_loss.py:70-108; torchvision batched_nms semantics):
  * boxes fp32 [K][4] (x1,y1,x2,y2) sorted by descending score with their class offsets added; suppress j > i when IoU > threshold, IoU in
  * separately rounded fp32 ops (bit-identical decisions to the host path).  mask: hn_nms_mask_words(K) uint64 scratch; keep: K bytes. */

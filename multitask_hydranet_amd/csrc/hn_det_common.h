@@ -6,6 +6,17 @@
 
 #define HN_DET_MAXK 32
 
+// Per-image task masks (gt_dict["task_valid"], one uint8 row per task: 1 = image n carries a label for the task).  Every masked entry
+// point (hn_*_masked) runs its unmasked twin's kernels with the row handed in; valid == nullptr is the unmasked call.  The number of
+// labelled images is counted where it is needed, by the thread that needs it, in image order: N bytes, no extra launch, no atomics.
+__device__ __forceinline__ int hn_count_valid(const unsigned char* valid, int N) {
+    if (!valid) return N;
+    int c = 0;
+    for (int n = 0; n < N; ++n) c += valid[n] != 0 ? 1 : 0;
+    return c;
+}
+__device__ __forceinline__ bool hn_image_valid(const unsigned char* valid, int n) { return !valid || valid[n] != 0; }
+
 // assign: >= 0 matched annotation, -1 background, -2 ignored (IoU: neg < 0.4, pos >= 0.5)
 __device__ __forceinline__ int det_assign(const float* anc, const float* ann, int Mx, float& best_iou) {
     const float ay1 = anc[0], ax1 = anc[1], ay2 = anc[2], ax2 = anc[3];
@@ -66,11 +77,13 @@ __device__ __forceinline__ void det_focal_grad_row(float* c, int K, int as, int 
 
 // One block of 1024 threads folds the forward's partial rows part[N][blocks][COLS] = {cls, reg, #pos[, extra]}.  Per image:
 // cls = sum_cls / max(npos, 1), reg = sum_reg / (REG_PER_POS npos) and extra = sum_extra / npos (both 0 without positives);
-// out[0], out[1][, out[2]] = their batch means; npos kept for the backward.
+// out[0], out[1][, out[2]] = their batch means; npos kept for the backward.  With a mask an unlabelled image's partial rows are zeros
+// (its anchors are all ignored), so its terms add +0 to the sums, and the means are taken over the labelled images (0 without any).
 // One wave per image (16 images walked one after the other by a single wave took 30 us of dependent load rounds), images beyond 16 in
 // further passes; the batch means are summed in image order by one thread.
 template <int COLS, int REG_PER_POS>
-__global__ __launch_bounds__(1024) void det_loss_finalize_kernel(const float* part, int blocks, int N, float* npos, float* out /* [COLS - 1] */) {
+__global__ __launch_bounds__(1024) void det_loss_finalize_kernel(const float* part, int blocks, int N, float* npos, float* out /* [COLS - 1] */,
+                                                                 const unsigned char* valid) {
     static_assert(COLS == 3 || COLS == 4, "partial rows are {cls, reg, #pos} or {cls, reg, #pos, extra}");
     __shared__ float pc[64], pr[64], px[64];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -101,7 +114,10 @@ __global__ __launch_bounds__(1024) void det_loss_finalize_kernel(const float* pa
             }
     }
     if (threadIdx.x == 0) {
-        out[0] = tc / N; out[1] = tr / N;
-        if (COLS == 4) out[2] = tx / N;
+        const int nv = hn_count_valid(valid, N);
+        if (nv == 0) { tc = 0.f; tr = 0.f; tx = 0.f; }
+        const int dn = nv > 0 ? nv : 1;
+        out[0] = tc / dn; out[1] = tr / dn;
+        if (COLS == 4) out[2] = tx / dn;
     }
 }

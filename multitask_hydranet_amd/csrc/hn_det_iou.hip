@@ -99,7 +99,8 @@ __device__ __forceinline__ void det_iou_box(const float* r, const float* anc, co
 // GIVEN: assign is an input (hn_det_loss_iou_fwd_assigned: ATSS, hn_det_atss.hip) instead of det_assign's output
 template <bool GIVEN>
 __global__ __launch_bounds__(256) void det_loss_iou_fwd_kernel(const float* cls, const float* reg, const float* anchors, const float* ann, int A,
-                                                               int K, int Mx, int kind, short* assign, float* part /* [N][blocks][4] */) {
+                                                               int K, int Mx, int kind, short* assign, float* part /* [N][blocks][4] */,
+                                                               const unsigned char* valid) {
     __shared__ float red[4][4];
     const int n = blockIdx.y;
     const int a = blockIdx.x * 256 + threadIdx.x;
@@ -107,12 +108,12 @@ __global__ __launch_bounds__(256) void det_loss_iou_fwd_kernel(const float* cls,
     if (a < A) {
         const float* anc = anchors + (long)a * 4;
         const float* an = ann + (long)n * Mx * 5;
-        int as;
+        int as = -2;                                                   // an unlabelled image: every anchor ignored
         if (GIVEN) {
-            as = det_given_assign(assign[(long)n * A + a], Mx);
+            if (hn_image_valid(valid, n)) as = det_given_assign(assign[(long)n * A + a], Mx);
         } else {
             float biou;
-            as = det_assign(anc, an, Mx, biou);
+            if (hn_image_valid(valid, n)) as = det_assign(anc, an, Mx, biou);
             assign[(long)n * A + a] = (short)as;
         }
         if (as != -2) s_cls = det_focal_sum(cls + ((long)n * A + a) * K, K, as >= 0 ? (int)an[as * 5 + 4] : -1);
@@ -132,7 +133,8 @@ __global__ __launch_bounds__(256) void det_loss_iou_fwd_kernel(const float* cls,
 
 __global__ __launch_bounds__(256) void det_loss_iou_bwd_kernel(const float* cls, const float* reg, const float* anchors, const float* ann, int N,
                                                                int A, int K, int Mx, int kind, const short* assign, const float* npos,
-                                                               const float* gout /* [2] */, float* dcls, float* dreg) {
+                                                               const float* gout /* [2] */, float* dcls, float* dreg,
+                                                               const unsigned char* valid) {
     // the classification tile moves through LDS as in det_loss_bwd_kernel (hn_loss.hip)
     extern __shared__ float tile[];                                    // [256][K]
     const int n = blockIdx.y;
@@ -143,9 +145,11 @@ __global__ __launch_bounds__(256) void det_loss_iou_bwd_kernel(const float* cls,
     for (int i = threadIdx.x; i < nv * K; i += 256) tile[i] = cblk[i];
     __syncthreads();
     const float p_n = npos[n];
-    const float fc = gout[0] / (N * fmaxf(p_n, 1.f));
-    const float fr = p_n > 0.f ? gout[1] / (N * p_n) : 0.f;
-    const int as = a < A ? assign[(long)n * A + a] : -2;
+    const bool lab = hn_image_valid(valid, n);
+    const int nlab = hn_count_valid(valid, N);                         // (lab implies nlab >= 1)
+    const float fc = lab ? gout[0] / (nlab * fmaxf(p_n, 1.f)) : 0.f;
+    const float fr = lab && p_n > 0.f ? gout[1] / (nlab * p_n) : 0.f;
+    const int as = a < A && lab ? assign[(long)n * A + a] : -2;       // a given assignment keeps its values for an unlabelled image
     const float* an = ann + (long)n * Mx * 5;
     if (a < A)
         det_focal_grad_row(tile + threadIdx.x * K, K, as, as >= 0 ? (int)an[as * 5 + 4] : -1, fc);
@@ -162,35 +166,69 @@ __global__ __launch_bounds__(256) void det_loss_iou_bwd_kernel(const float* cls,
 }
 
 // fwd: out[0] = classification loss, out[1] = regression loss, out[2] = mean IoU of the positives (batch means of per-image means);
-// assign int16 [N][A], part fp32 [N][blocks][4], npos fp32 [N]
-extern "C" int hn_det_loss_iou_fwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
-                                   int kind, void* assign, float* part, float* npos, float* out, hipStream_t st) {
+// assign int16 [N][A], part fp32 [N][blocks][4], npos fp32 [N]  (valid: the det row of the task masks; nullptr = every image labelled)
+static int det_loss_iou_fwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                            int kind, void* assign, float* part, float* npos, float* out, const unsigned char* valid, hipStream_t st) {
     HN_CHECK_ARG(cls && reg && anchors && ann && assign && part && npos && out && N > 0 && A > 0 && K > 0 && K <= HN_DET_MAXK && Mx > 0);
     HN_CHECK_ARG(kind >= 1 && kind <= 3);
     const int blocks = hn_det_loss_blocks(A);
-    hipLaunchKernelGGL(det_loss_iou_fwd_kernel<false>, dim3(blocks, N), dim3(256), 0, st, cls, reg, anchors, ann, A, K, Mx, kind, (short*)assign, part);
-    hipLaunchKernelGGL((det_loss_finalize_kernel<4, 1>), dim3(1), dim3(1024), 0, st, part, blocks, N, npos, out);
+    hipLaunchKernelGGL(det_loss_iou_fwd_kernel<false>, dim3(blocks, N), dim3(256), 0, st, cls, reg, anchors, ann, A, K, Mx, kind, (short*)assign, part, valid);
+    hipLaunchKernelGGL((det_loss_finalize_kernel<4, 1>), dim3(1), dim3(1024), 0, st, part, blocks, N, npos, out, valid);
     HN_LAUNCH_CHECK();
+}
+
+extern "C" int hn_det_loss_iou_fwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                                   int kind, void* assign, float* part, float* npos, float* out, hipStream_t st) {
+    return det_loss_iou_fwd(cls, reg, anchors, ann, N, A, K, Mx, kind, assign, part, npos, out, nullptr, st);
+}
+extern "C" int hn_det_loss_iou_fwd_masked(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K,
+                                          int Mx, int kind, const unsigned char* valid, void* assign, float* part, float* npos, float* out,
+                                          hipStream_t st) {
+    HN_CHECK_ARG(valid);
+    return det_loss_iou_fwd(cls, reg, anchors, ann, N, A, K, Mx, kind, assign, part, npos, out, valid, st);
 }
 
 // hn_det_loss_iou_fwd with assign [N][A] as an INPUT (values outside -2 .. Mx - 1 count as ignored); everything else as above
-extern "C" int hn_det_loss_iou_fwd_assigned(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K,
-                                            int Mx, int kind, const void* assign, float* part, float* npos, float* out, hipStream_t st) {
+static int det_loss_iou_fwd_assigned(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K,
+                                     int Mx, int kind, const void* assign, float* part, float* npos, float* out, const unsigned char* valid,
+                                     hipStream_t st) {
     HN_CHECK_ARG(cls && reg && anchors && ann && assign && part && npos && out && N > 0 && A > 0 && K > 0 && K <= HN_DET_MAXK && Mx > 0);
     HN_CHECK_ARG(kind >= 1 && kind <= 3);
     const int blocks = hn_det_loss_blocks(A);
-    hipLaunchKernelGGL(det_loss_iou_fwd_kernel<true>, dim3(blocks, N), dim3(256), 0, st, cls, reg, anchors, ann, A, K, Mx, kind, (short*)assign, part);
-    hipLaunchKernelGGL((det_loss_finalize_kernel<4, 1>), dim3(1), dim3(1024), 0, st, part, blocks, N, npos, out);
+    hipLaunchKernelGGL(det_loss_iou_fwd_kernel<true>, dim3(blocks, N), dim3(256), 0, st, cls, reg, anchors, ann, A, K, Mx, kind, (short*)assign, part, valid);
+    hipLaunchKernelGGL((det_loss_finalize_kernel<4, 1>), dim3(1), dim3(1024), 0, st, part, blocks, N, npos, out, valid);
     HN_LAUNCH_CHECK();
 }
 
-extern "C" int hn_det_loss_iou_bwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
-                                   int kind, const void* assign, const float* npos, const float* gout, float* dcls, float* dreg,
-                                   hipStream_t st) {
+extern "C" int hn_det_loss_iou_fwd_assigned(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K,
+                                            int Mx, int kind, const void* assign, float* part, float* npos, float* out, hipStream_t st) {
+    return det_loss_iou_fwd_assigned(cls, reg, anchors, ann, N, A, K, Mx, kind, assign, part, npos, out, nullptr, st);
+}
+extern "C" int hn_det_loss_iou_fwd_assigned_masked(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A,
+                                                   int K, int Mx, int kind, const unsigned char* valid, const void* assign, float* part,
+                                                   float* npos, float* out, hipStream_t st) {
+    HN_CHECK_ARG(valid);
+    return det_loss_iou_fwd_assigned(cls, reg, anchors, ann, N, A, K, Mx, kind, assign, part, npos, out, valid, st);
+}
+
+static int det_loss_iou_bwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                            int kind, const void* assign, const float* npos, const float* gout, float* dcls, float* dreg,
+                            const unsigned char* valid, hipStream_t st) {
     HN_CHECK_ARG(cls && reg && anchors && ann && assign && npos && gout && dcls && dreg && N > 0 && A > 0 && K > 0 && Mx > 0);
     HN_CHECK_ARG(K <= HN_DET_MAXK);                                     // 256 x K floats of LDS
     HN_CHECK_ARG(kind >= 1 && kind <= 3);
     hipLaunchKernelGGL(det_loss_iou_bwd_kernel, dim3(hn_det_loss_blocks(A), N), dim3(256), 256 * (size_t)K * sizeof(float), st, cls, reg, anchors,
-                       ann, N, A, K, Mx, kind, (const short*)assign, npos, gout, dcls, dreg);
+                       ann, N, A, K, Mx, kind, (const short*)assign, npos, gout, dcls, dreg, valid);
     HN_LAUNCH_CHECK();
+}
+extern "C" int hn_det_loss_iou_bwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                                   int kind, const void* assign, const float* npos, const float* gout, float* dcls, float* dreg,
+                                   hipStream_t st) {
+    return det_loss_iou_bwd(cls, reg, anchors, ann, N, A, K, Mx, kind, assign, npos, gout, dcls, dreg, nullptr, st);
+}
+extern "C" int hn_det_loss_iou_bwd_masked(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K,
+                                          int Mx, int kind, const unsigned char* valid, const void* assign, const float* npos,
+                                          const float* gout, float* dcls, float* dreg, hipStream_t st) {
+    HN_CHECK_ARG(valid);
+    return det_loss_iou_bwd(cls, reg, anchors, ann, N, A, K, Mx, kind, assign, npos, gout, dcls, dreg, valid, st);
 }

@@ -11,7 +11,7 @@
 // per pixel: loss = w[y] * (logsumexp(l) - l[y]) (0 for ignored pixels); also the level-0 histogram (top 11 bits) per image
 __global__ __launch_bounds__(256) void seg_ce_fwd_kernel(const float* logits, int ldl, int C, const void* target, int target_is_float,
                                                          const float* cw, int ignore_index, long HW, long M, float* loss,
-                                                         unsigned int* hist /* [N][2048] or null */) {
+                                                         unsigned int* hist /* [N][2048] or null */, const unsigned char* valid) {
     __shared__ unsigned int sh[2048];
     const bool do_hist = hist != nullptr;
     if (do_hist) {
@@ -25,10 +25,14 @@ __global__ __launch_bounds__(256) void seg_ce_fwd_kernel(const float* logits, in
     const long p0 = (long)n * HW + b * per;
     long p1 = p0 + per;
     if (p1 > (long)(n + 1) * HW) p1 = (long)(n + 1) * HW;
+    // an unlabelled image: every pixel as if ignored.  Its histograms stay empty at every level (its HW zero losses would all land in bin
+    // 0, one LDS address): no bin stops the select's walk, which then ends at bin 0 with the whole rank left over, as it does for HW
+    // zeros -- prefix 0, remaining k either way
+    const bool lab = hn_image_valid(valid, n);
     for (long m = p0 + threadIdx.x; m < p1; m += 256) {
         const int y = target_is_float ? (int)reinterpret_cast<const float*>(target)[m] : (int)reinterpret_cast<const long*>(target)[m];
         float l = 0.f;
-        if (y != ignore_index && y >= 0 && y < C) {
+        if (lab && y != ignore_index && y >= 0 && y < C) {
             const float* row = logits + m * ldl;
             float mx = row[0];
             for (int c = 1; c < C; ++c) mx = fmaxf(mx, row[c]);
@@ -38,7 +42,7 @@ __global__ __launch_bounds__(256) void seg_ce_fwd_kernel(const float* logits, in
             if (l < 0.f) l = 0.f;                     // guards the unsigned-bit-pattern ordering (rounding can give -0)
         }
         loss[m] = l;
-        if (do_hist) atomicAdd(&sh[__float_as_uint(l) >> 21], 1u);
+        if (do_hist && lab) atomicAdd(&sh[__float_as_uint(l) >> 21], 1u);
     }
     if (do_hist) {
         __syncthreads();
@@ -50,7 +54,7 @@ __global__ __launch_bounds__(256) void seg_ce_fwd_kernel(const float* logits, in
 // compile-time class count, four consecutive pixels per thread: 4*CT contiguous floats = CT float4 loads, float4 targets, float4 loss store
 template <int CT>
 __global__ __launch_bounds__(256) void seg_ce_fwd_vec_kernel(const float* logits, const float* target, const float* cw, int ignore_index,
-                                                             long HW, long M, float* loss, unsigned int* hist) {
+                                                             long HW, long M, float* loss, unsigned int* hist, const unsigned char* valid) {
     __shared__ unsigned int sh[2048];
     const bool do_hist = hist != nullptr;
     if (do_hist) {
@@ -63,7 +67,12 @@ __global__ __launch_bounds__(256) void seg_ce_fwd_vec_kernel(const float* logits
     const long p0 = (long)n * HW + b * per;
     long p1 = p0 + per;
     if (p1 > (long)(n + 1) * HW) p1 = (long)(n + 1) * HW;
+    const bool lab = hn_image_valid(valid, n);
     for (long m = p0 + 4 * threadIdx.x; m < p1; m += 1024) {
+        if (!lab) {                                                    // an unlabelled image: four zero losses, nothing read, no histogram
+            *reinterpret_cast<f32x4*>(loss + m) = f32x4{0.f, 0.f, 0.f, 0.f};
+            continue;
+        }
         float lg[4 * CT];
         const f32x4* row = reinterpret_cast<const f32x4*>(logits + m * CT);
 #pragma unroll
@@ -74,7 +83,7 @@ __global__ __launch_bounds__(256) void seg_ce_fwd_vec_kernel(const float* logits
         for (int u = 0; u < 4; ++u) {
             const int y = (int)tg[u];
             float l = 0.f;
-            if (y != ignore_index && y >= 0 && y < CT) {
+            if (lab && y != ignore_index && y >= 0 && y < CT) {
                 const float* r = &lg[u * CT];
                 float mx = r[0];
 #pragma unroll
@@ -101,12 +110,14 @@ __global__ __launch_bounds__(256) void seg_ce_fwd_vec_kernel(const float* logits
 struct SelState { unsigned int prefix; unsigned int remaining; };
 
 // level L histogram of the elements whose higher bits equal the prefix.  level 1: bits 20..10 (11 bits), level 2: bits 9..0 (10 bits)
-__global__ __launch_bounds__(256) void seg_hist_kernel(const float* loss, long HW, long M, const SelState* st, int level, unsigned int* hist) {
+__global__ __launch_bounds__(256) void seg_hist_kernel(const float* loss, long HW, long M, const SelState* st, int level, unsigned int* hist,
+                                                       const unsigned char* valid) {
     __shared__ unsigned int sh[2048];
-    for (int i = threadIdx.x; i < 2048; i += 256) sh[i] = 0;
-    __syncthreads();
     const int bpi = gridDim.x / (int)(M / HW);
     const int n = blockIdx.x / bpi, b = blockIdx.x - n * bpi;
+    if (!hn_image_valid(valid, n)) return;                            // (the whole workgroup: see seg_ce_fwd_kernel)
+    for (int i = threadIdx.x; i < 2048; i += 256) sh[i] = 0;
+    __syncthreads();
     const long per = (HW + bpi - 1) / bpi;
     const long p0 = (long)n * HW + b * per;
     long p1 = p0 + per;
@@ -201,9 +212,16 @@ __global__ __launch_bounds__(256) void seg_topk_sum_kernel(const float* loss, lo
     if (threadIdx.x == 0) psum[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
-// out = ( sum_blocks psum + sum_n remaining_n * thr_n ) / denom
+// 1 / (labelled images x per_image), rounded to fp32 once like the host's (float)(1.0 / denom) of the unmasked call; 0 without any
+__device__ __forceinline__ float seg_masked_inv_denom(const unsigned char* valid, int N, double per_image) {
+    const int nv = hn_count_valid(valid, N);
+    return nv > 0 ? (float)(1.0 / ((double)nv * per_image)) : 0.f;
+}
+
+// out = ( sum_blocks psum + sum_n remaining_n * thr_n ) / denom;  with a mask denom = labelled images x per_image (out = 0 without any):
+// an unlabelled image's losses are all zero, so its partial sums and its threshold term add +0
 __global__ __launch_bounds__(256) void seg_loss_finalize_kernel(const float* psum, int nblocks, const SelState* st, int N, int use_topk,
-                                                                double denom, float* out) {
+                                                                double denom, float* out, const unsigned char* valid, double per_image) {
     __shared__ double red[4];
     double s = 0.0;
     for (int i = threadIdx.x; i < nblocks; i += 256) s += psum[i];
@@ -213,20 +231,28 @@ __global__ __launch_bounds__(256) void seg_loss_finalize_kernel(const float* psu
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) out[0] = (float)((red[0] + red[1] + red[2] + red[3]) / denom);
+    if (threadIdx.x == 0) {
+        if (valid) {
+            const int nv = hn_count_valid(valid, N);
+            out[0] = nv > 0 ? (float)((red[0] + red[1] + red[2] + red[3]) / ((double)nv * per_image)) : 0.f;
+        } else {
+            out[0] = (float)((red[0] + red[1] + red[2] + red[3]) / denom);
+        }
+    }
 }
 
 // backward: dlogits[m][c] = gout/denom * sel(m) * w[y] * (softmax_c - [c == y]);  sel = 1 above the threshold, remaining/ties at it, 0 below
 __global__ __launch_bounds__(256) void seg_ce_bwd_kernel(const float* logits, int ldl, int C, const void* target, int target_is_float,
                                                          const float* cw, int ignore_index, long HW, long M, const float* loss,
                                                          const SelState* st, const unsigned int* ties, int use_topk, const float* gout,
-                                                         float inv_denom, float* dlogits, int ldd) {
-    const float gs = gout[0] * inv_denom;
+                                                         float inv_denom, float* dlogits, int ldd, const unsigned char* valid,
+                                                         double per_image) {
+    const float gs = gout[0] * (valid ? seg_masked_inv_denom(valid, (int)(M / HW), per_image) : inv_denom);
     for (long m = (long)blockIdx.x * 256 + threadIdx.x; m < M; m += (long)gridDim.x * 256) {
         const int n = (int)(m / HW);
         const int y = target_is_float ? (int)reinterpret_cast<const float*>(target)[m] : (int)reinterpret_cast<const long*>(target)[m];
         float sel = 0.f;
-        if (y != ignore_index && y >= 0 && y < C) {
+        if (hn_image_valid(valid, n) && y != ignore_index && y >= 0 && y < C) {
             sel = 1.f;
             if (use_topk) {
                 const unsigned int u = __float_as_uint(loss[m]), thr = st[n].prefix;
@@ -256,8 +282,8 @@ __global__ __launch_bounds__(256) void seg_ce_bwd_kernel(const float* logits, in
 __global__ __launch_bounds__(256) void seg_ce_bwd_s2d_kernel(const float* logits, int ldl, int C, const void* target, int target_is_float,
                                                              const float* cw, int ignore_index, int H, int W, long M4, const float* loss,
                                                              const SelState* st, const unsigned int* ties, int use_topk, const float* gout,
-                                                             float inv_denom, bf16* dz, int ldz) {
-    const float gs = gout[0] * inv_denom;
+                                                             float inv_denom, bf16* dz, int ldz, const unsigned char* valid, double per_image) {
+    const float gs = gout[0] * (valid ? seg_masked_inv_denom(valid, (int)(M4 / ((long)(H >> 1) * (W >> 1))), per_image) : inv_denom);
     const int h = H >> 1, w = W >> 1;
     const long HW = (long)H * W;
     for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < M4; q += (long)gridDim.x * 256) {
@@ -271,7 +297,7 @@ __global__ __launch_bounds__(256) void seg_ce_bwd_s2d_kernel(const float* logits
             const long m = (long)n * HW + (long)(2 * y + (ph >> 1)) * W + 2 * x + (ph & 1);
             const int yy = target_is_float ? (int)reinterpret_cast<const float*>(target)[m] : (int)reinterpret_cast<const long*>(target)[m];
             float sel = 0.f;
-            if (yy != ignore_index && yy >= 0 && yy < C) {
+            if (hn_image_valid(valid, n) && yy != ignore_index && yy >= 0 && yy < C) {
                 sel = 1.f;
                 if (use_topk) {
                     const unsigned int u = __float_as_uint(loss[m]), thr = st[n].prefix;
@@ -302,9 +328,9 @@ template <int CT, int LDZ>
 __global__ __launch_bounds__(256) void seg_ce_bwd_s2d_vec_kernel(const float* logits, const float* target, const float* cw, int ignore_index,
                                                                  int H, int W, long M4, const float* loss, const SelState* st,
                                                                  const unsigned int* ties, int use_topk, const float* gout, float inv_denom,
-                                                                 bf16* dz) {
+                                                                 bf16* dz, const unsigned char* valid, double per_image) {
     typedef float f32x2 __attribute__((ext_vector_type(2)));
-    const float gs = gout[0] * inv_denom;
+    const float gs = gout[0] * (valid ? seg_masked_inv_denom(valid, (int)(M4 / ((long)(H >> 1) * (W >> 1))), per_image) : inv_denom);
     const int h = H >> 1, w = W >> 1;
     const long HW = (long)H * W;
     for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < M4; q += (long)gridDim.x * 256) {
@@ -333,7 +359,7 @@ __global__ __launch_bounds__(256) void seg_ce_bwd_s2d_vec_kernel(const float* lo
             const int py = ph >> 1, px = ph & 1;
             const int yy = (int)tg[py][px];
             float sel = 0.f;
-            if (yy != ignore_index && yy >= 0 && yy < CT) {
+            if (hn_image_valid(valid, n) && yy != ignore_index && yy >= 0 && yy < CT) {
                 sel = 1.f;
                 if (use_topk) {
                     const unsigned int u = __float_as_uint(ls[py][px]);
@@ -391,7 +417,8 @@ __global__ __launch_bounds__(256) void seg_count_ties_kernel(const float* loss, 
 // GIVEN: assign is an input (hn_det_loss_fwd_assigned: ATSS, hn_det_atss.hip) instead of det_assign's output
 template <bool GIVEN>
 __global__ __launch_bounds__(256) void det_loss_fwd_kernel(const float* cls, const float* reg, const float* anchors, const float* ann, int A,
-                                                           int K, int Mx, short* assign, float* part /* [N][blocks][3] */) {
+                                                           int K, int Mx, short* assign, float* part /* [N][blocks][3] */,
+                                                           const unsigned char* valid) {
     __shared__ float red[4][3];
     const int n = blockIdx.y;
     const int a = blockIdx.x * 256 + threadIdx.x;
@@ -399,12 +426,12 @@ __global__ __launch_bounds__(256) void det_loss_fwd_kernel(const float* cls, con
     if (a < A) {
         const float* anc = anchors + (long)a * 4;
         const float* an = ann + (long)n * Mx * 5;
-        int as;
+        int as = -2;                                                   // an unlabelled image: every anchor ignored
         if (GIVEN) {
-            as = det_given_assign(assign[(long)n * A + a], Mx);
+            if (hn_image_valid(valid, n)) as = det_given_assign(assign[(long)n * A + a], Mx);
         } else {
             float biou;
-            as = det_assign(anc, an, Mx, biou);
+            if (hn_image_valid(valid, n)) as = det_assign(anc, an, Mx, biou);
             assign[(long)n * A + a] = (short)as;
         }
         if (as != -2) s_cls = det_focal_sum(cls + ((long)n * A + a) * K, K, as >= 0 ? (int)an[as * 5 + 4] : -1);
@@ -434,7 +461,7 @@ __global__ __launch_bounds__(256) void det_loss_fwd_kernel(const float* cls, con
 
 __global__ __launch_bounds__(256) void det_loss_bwd_kernel(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A,
                                                            int K, int Mx, const short* assign, const float* npos, const float* gout /* [2] */,
-                                                           float* dcls, float* dreg) {
+                                                           float* dcls, float* dreg, const unsigned char* valid) {
     // the block's 256 x K probabilities / gradients are one contiguous run in memory: they move through LDS with coalesced 4-byte
     // accesses (a thread walking its own K floats 36 bytes from its neighbour's wrote partial lines: 0.9 TB/s, 91 us per step)
     extern __shared__ float tile[];                                    // [256][K]
@@ -446,9 +473,11 @@ __global__ __launch_bounds__(256) void det_loss_bwd_kernel(const float* cls, con
     for (int i = threadIdx.x; i < nv * K; i += 256) tile[i] = cblk[i];
     __syncthreads();
     const float p_n = npos[n];
-    const float fc = gout[0] / (N * fmaxf(p_n, 1.f));
-    const float fr = p_n > 0.f ? gout[1] / (N * 4.f * p_n) : 0.f;
-    const int as = a < A ? assign[(long)n * A + a] : -2;
+    const bool lab = hn_image_valid(valid, n);
+    const int nlab = hn_count_valid(valid, N);                         // (lab implies nlab >= 1)
+    const float fc = lab ? gout[0] / (nlab * fmaxf(p_n, 1.f)) : 0.f;
+    const float fr = lab && p_n > 0.f ? gout[1] / (nlab * 4.f * p_n) : 0.f;
+    const int as = a < A && lab ? assign[(long)n * A + a] : -2;       // a given assignment keeps its values for an unlabelled image
     const float* an = ann + (long)n * Mx * 5;
     if (a < A)                                                         // (K odd or not: stride-K rows, each thread only touches its own)
         det_focal_grad_row(tile + threadIdx.x * K, K, as, as >= 0 ? (int)an[as * 5 + 4] : -1, fc);
@@ -512,8 +541,10 @@ __global__ void zero_u32_kernel(unsigned int* p, long n) {
 }
 
 // forward: returns the scalar loss in out[0]; ws is kept for the backward pass.  k = int(top_k_ratio * HW) when use_topk.
-extern "C" int hn_seg_loss_fwd(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* cw,
-                               int ignore_index, int N, long HW, int use_topk, long k, void* ws, float* out, hipStream_t st) {
+// (valid: the seg row of the task masks, hn_det_common.h; nullptr = every image labelled.  Same launches either way.)
+static int seg_loss_fwd(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* cw,
+                        int ignore_index, int N, long HW, int use_topk, long k, void* ws, float* out, const unsigned char* valid,
+                        hipStream_t st) {
     HN_CHECK_ARG(logits && target && cw && ws && out && C >= 1 && C <= HN_SEG_MAXC && N > 0 && HW > 0 && (!use_topk || (k >= 1 && k <= HW)));
     const long M = (long)N * HW;
     char* w = (char*)ws;
@@ -532,27 +563,38 @@ extern "C" int hn_seg_loss_fwd(const float* logits, int ldl, int C, const void* 
     if (C == 5 && ldl == 5 && target_is_float && (HW & 3) == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0 &&
         (reinterpret_cast<uintptr_t>(target) & 15) == 0)
         hipLaunchKernelGGL(seg_ce_fwd_vec_kernel<5>, dim3(blocks), dim3(256), 0, st, logits, (const float*)target, cw, ignore_index, HW, M, loss,
-                           use_topk ? hist : (unsigned int*)nullptr);
+                           use_topk ? hist : (unsigned int*)nullptr, valid);
     else
         hipLaunchKernelGGL(seg_ce_fwd_kernel, dim3(blocks), dim3(256), 0, st, logits, ldl, C, target, target_is_float, cw, ignore_index, HW, M,
-                           loss, use_topk ? hist : (unsigned int*)nullptr);
+                           loss, use_topk ? hist : (unsigned int*)nullptr, valid);
     if (use_topk) {
         hipLaunchKernelGGL(seg_select_kernel, dim3(N), dim3(64), 0, st, hist, state, 0, (unsigned int)k);
-        hipLaunchKernelGGL(seg_hist_kernel, dim3(blocks), dim3(256), 0, st, loss, HW, M, state, 1, hist);
+        hipLaunchKernelGGL(seg_hist_kernel, dim3(blocks), dim3(256), 0, st, loss, HW, M, state, 1, hist, valid);
         hipLaunchKernelGGL(seg_select_kernel, dim3(N), dim3(64), 0, st, hist, state, 1, (unsigned int)k);
-        hipLaunchKernelGGL(seg_hist_kernel, dim3(blocks), dim3(256), 0, st, loss, HW, M, state, 2, hist);
+        hipLaunchKernelGGL(seg_hist_kernel, dim3(blocks), dim3(256), 0, st, loss, HW, M, state, 2, hist, valid);
         hipLaunchKernelGGL(seg_select_kernel, dim3(N), dim3(64), 0, st, hist, state, 2, (unsigned int)k);
         hipLaunchKernelGGL(seg_count_ties_kernel, dim3(blocks), dim3(256), 0, st, loss, HW, M, state, ties);
     }
     hipLaunchKernelGGL(seg_topk_sum_kernel, dim3(blocks), dim3(256), 0, st, loss, HW, M, state, use_topk, psum);
     const double denom = use_topk ? (double)N * (double)k : (double)M;
-    hipLaunchKernelGGL(seg_loss_finalize_kernel, dim3(1), dim3(256), 0, st, psum, blocks, state, N, use_topk, denom, out);
+    hipLaunchKernelGGL(seg_loss_finalize_kernel, dim3(1), dim3(256), 0, st, psum, blocks, state, N, use_topk, denom, out, valid,
+                       use_topk ? (double)k : (double)HW);
     HN_LAUNCH_CHECK();
 }
+extern "C" int hn_seg_loss_fwd(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* cw,
+                               int ignore_index, int N, long HW, int use_topk, long k, void* ws, float* out, hipStream_t st) {
+    return seg_loss_fwd(logits, ldl, C, target, target_is_float, cw, ignore_index, N, HW, use_topk, k, ws, out, nullptr, st);
+}
+extern "C" int hn_seg_loss_fwd_masked(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* cw,
+                                      int ignore_index, int N, long HW, int use_topk, long k, const unsigned char* valid, void* ws, float* out,
+                                      hipStream_t st) {
+    HN_CHECK_ARG(valid);
+    return seg_loss_fwd(logits, ldl, C, target, target_is_float, cw, ignore_index, N, HW, use_topk, k, ws, out, valid, st);
+}
 
-extern "C" int hn_seg_loss_bwd(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* cw,
-                               int ignore_index, int N, long HW, int use_topk, long k, const void* ws, const float* gout, float* dlogits,
-                               int ldd, hipStream_t st) {
+static int seg_loss_bwd(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* cw,
+                        int ignore_index, int N, long HW, int use_topk, long k, const void* ws, const float* gout, float* dlogits,
+                        int ldd, const unsigned char* valid, hipStream_t st) {
     HN_CHECK_ARG(logits && target && cw && ws && gout && dlogits && C >= 1 && C <= HN_SEG_MAXC && N > 0 && HW > 0);
     const long M = (long)N * HW;
     const char* w = (const char*)ws;
@@ -563,15 +605,26 @@ extern "C" int hn_seg_loss_bwd(const float* logits, int ldl, int C, const void* 
     long blocks = (M + 255) / 256;
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(seg_ce_bwd_kernel, dim3(blocks), dim3(256), 0, st, logits, ldl, C, target, target_is_float, cw, ignore_index, HW, M, loss,
-                       state, ties, use_topk, gout, (float)(1.0 / denom), dlogits, ldd);
+                       state, ties, use_topk, gout, (float)(1.0 / denom), dlogits, ldd, valid, use_topk ? (double)k : (double)HW);
     HN_LAUNCH_CHECK();
+}
+extern "C" int hn_seg_loss_bwd(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* cw,
+                               int ignore_index, int N, long HW, int use_topk, long k, const void* ws, const float* gout, float* dlogits,
+                               int ldd, hipStream_t st) {
+    return seg_loss_bwd(logits, ldl, C, target, target_is_float, cw, ignore_index, N, HW, use_topk, k, ws, gout, dlogits, ldd, nullptr, st);
+}
+extern "C" int hn_seg_loss_bwd_masked(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* cw,
+                                      int ignore_index, int N, long HW, int use_topk, long k, const unsigned char* valid, const void* ws,
+                                      const float* gout, float* dlogits, int ldd, hipStream_t st) {
+    HN_CHECK_ARG(valid);
+    return seg_loss_bwd(logits, ldl, C, target, target_is_float, cw, ignore_index, N, HW, use_topk, k, ws, gout, dlogits, ldd, valid, st);
 }
 
 /* hn_seg_loss_bwd writing the space-to-depth bf16 operand of the phase-form output conv's backward instead of fp32 dlogits:
  * dz [N][H/2][W/2][ldz], ldz >= 4*C (see seg_ce_bwd_s2d_kernel); H, W even */
-extern "C" int hn_seg_loss_bwd_s2d(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* cw,
-                                   int ignore_index, int N, int H, int W, int use_topk, long k, const void* ws, const float* gout, void* dz,
-                                   int ldz, hipStream_t st) {
+static int seg_loss_bwd_s2d(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* cw,
+                            int ignore_index, int N, int H, int W, int use_topk, long k, const void* ws, const float* gout, void* dz,
+                            int ldz, const unsigned char* valid, hipStream_t st) {
     HN_CHECK_ARG(logits && target && cw && ws && gout && dz && C >= 1 && C <= HN_SEG_MAXC && N > 0 && H > 0 && W > 0 && !(H & 1) && !(W & 1) &&
                  ldz >= 4 * C);
     const long HW = (long)H * W, M = (long)N * HW;
@@ -580,18 +633,30 @@ extern "C" int hn_seg_loss_bwd_s2d(const float* logits, int ldl, int C, const vo
     const SelState* state = (const SelState*)(w + M * 4 + (long)N * 2048 * 4);
     const unsigned int* ties = (const unsigned int*)(w + M * 4 + (long)N * 2048 * 4 + (long)N * 8);
     const double denom = use_topk ? (double)N * (double)k : (double)M;
+    const double per_image = use_topk ? (double)k : (double)HW;
     long blocks = (M / 4 + 255) / 256;
     if (blocks > 8192) blocks = 8192;
     if (C == 5 && ldl == 5 && ldz == 24 && target_is_float && (reinterpret_cast<uintptr_t>(logits) & 7) == 0 &&
         (reinterpret_cast<uintptr_t>(target) & 7) == 0 && (reinterpret_cast<uintptr_t>(dz) & 15) == 0) {
         // the shipped 5-class cfgs (cityscapes-style class list): vector loads / stores
         hipLaunchKernelGGL((seg_ce_bwd_s2d_vec_kernel<5, 24>), dim3(blocks), dim3(256), 0, st, logits, (const float*)target, cw, ignore_index, H, W,
-                           M / 4, loss, state, ties, use_topk, gout, (float)(1.0 / denom), (bf16*)dz);
+                           M / 4, loss, state, ties, use_topk, gout, (float)(1.0 / denom), (bf16*)dz, valid, per_image);
         HN_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(seg_ce_bwd_s2d_kernel, dim3(blocks), dim3(256), 0, st, logits, ldl, C, target, target_is_float, cw, ignore_index, H, W,
-                       M / 4, loss, state, ties, use_topk, gout, (float)(1.0 / denom), (bf16*)dz, ldz);
+                       M / 4, loss, state, ties, use_topk, gout, (float)(1.0 / denom), (bf16*)dz, ldz, valid, per_image);
     HN_LAUNCH_CHECK();
+}
+extern "C" int hn_seg_loss_bwd_s2d(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* cw,
+                                   int ignore_index, int N, int H, int W, int use_topk, long k, const void* ws, const float* gout, void* dz,
+                                   int ldz, hipStream_t st) {
+    return seg_loss_bwd_s2d(logits, ldl, C, target, target_is_float, cw, ignore_index, N, H, W, use_topk, k, ws, gout, dz, ldz, nullptr, st);
+}
+extern "C" int hn_seg_loss_bwd_s2d_masked(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* cw,
+                                          int ignore_index, int N, int H, int W, int use_topk, long k, const unsigned char* valid,
+                                          const void* ws, const float* gout, void* dz, int ldz, hipStream_t st) {
+    HN_CHECK_ARG(valid);
+    return seg_loss_bwd_s2d(logits, ldl, C, target, target_is_float, cw, ignore_index, N, H, W, use_topk, k, ws, gout, dz, ldz, valid, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -602,10 +667,12 @@ extern "C" int hn_seg_loss_bwd_s2d(const float* logits, int ldl, int C, const vo
 __device__ __forceinline__ float focal_pow(float q, float gamma) { return gamma == 2.0f ? q * q : powf(q, gamma); }
 
 __global__ __launch_bounds__(256) void seg_focal_fwd_kernel(const float* logits, int ldl, int C, const void* target, int target_is_float,
-                                                            const float* cw, float gamma, float alpha, long M, float* psum) {
+                                                            const float* cw, float gamma, float alpha, long M, float* psum,
+                                                            const unsigned char* valid, long HW) {
     __shared__ float red[4];
     float s = 0.f;
     for (long m = (long)blockIdx.x * 256 + threadIdx.x; m < M; m += (long)gridDim.x * 256) {
+        if (valid && !valid[m / HW]) continue;                        // a pixel of an unlabelled image: not in the sum
         const int y = target_is_float ? (int)reinterpret_cast<const float*>(target)[m] : (int)reinterpret_cast<const long*>(target)[m];
         const float* row = logits + m * ldl;
         float mx = row[0];
@@ -629,9 +696,13 @@ __global__ __launch_bounds__(256) void seg_focal_fwd_kernel(const float* logits,
 // dlogits_j = gout/M * s_j * (g_j - sum_c g_c s_c),  g_c = dloss/dp_c = t_c w_c alpha (gamma (1-p_c)^(gamma-1) log p_c - (1-p_c)^gamma / p_c)
 __global__ __launch_bounds__(256) void seg_focal_bwd_kernel(const float* logits, int ldl, int C, const void* target, int target_is_float,
                                                             const float* cw, float gamma, float alpha, long M, const float* gout,
-                                                            float inv_denom, float* dlogits, int ldd) {
-    const float gs = gout[0] * inv_denom;
+                                                            float inv_denom, float* dlogits, int ldd, const unsigned char* valid, long HW) {
+    const float gs = gout[0] * (valid ? seg_masked_inv_denom(valid, (int)(M / HW), (double)HW) : inv_denom);
     for (long m = (long)blockIdx.x * 256 + threadIdx.x; m < M; m += (long)gridDim.x * 256) {
+        if (valid && !valid[m / HW]) {
+            for (int c = 0; c < C; ++c) dlogits[m * ldd + c] = 0.f;
+            continue;
+        }
         const int y = target_is_float ? (int)reinterpret_cast<const float*>(target)[m] : (int)reinterpret_cast<const long*>(target)[m];
         const float* row = logits + m * ldl;
         float mx = row[0];
@@ -653,26 +724,47 @@ __global__ __launch_bounds__(256) void seg_focal_bwd_kernel(const float* logits,
 
 /* focal seg loss: logits fp32 [N*HW][ldl] (C classes), target float32 or int64 class ids [N*HW] (no ignore_index on this path, as in the
  * reference), ws = fp32 [hn_seg_loss_blocks(N, HW)] partial sums, out[0] = mean over all N*HW pixels */
-extern "C" int hn_seg_focal_fwd(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* cw, float gamma,
-                                float alpha, int N, long HW, void* ws, float* out, hipStream_t st) {
+static int seg_focal_fwd(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* cw, float gamma,
+                         float alpha, int N, long HW, void* ws, float* out, const unsigned char* valid, hipStream_t st) {
     HN_CHECK_ARG(logits && target && cw && ws && out && C >= 1 && C <= HN_SEG_MAXC && N > 0 && HW > 0);
     const long M = (long)N * HW;
     const int blocks = hn_seg_loss_blocks(N, HW);
     hipLaunchKernelGGL(seg_focal_fwd_kernel, dim3(blocks), dim3(256), 0, st, logits, ldl, C, target, target_is_float, cw, gamma, alpha, M,
-                       (float*)ws);
-    hipLaunchKernelGGL(seg_loss_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, blocks, (const SelState*)nullptr, N, 0, (double)M, out);
+                       (float*)ws, valid, HW);
+    hipLaunchKernelGGL(seg_loss_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, blocks, (const SelState*)nullptr, N, 0, (double)M, out,
+                       valid, (double)HW);
     HN_LAUNCH_CHECK();
 }
+extern "C" int hn_seg_focal_fwd(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* cw, float gamma,
+                                float alpha, int N, long HW, void* ws, float* out, hipStream_t st) {
+    return seg_focal_fwd(logits, ldl, C, target, target_is_float, cw, gamma, alpha, N, HW, ws, out, nullptr, st);
+}
+extern "C" int hn_seg_focal_fwd_masked(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* cw,
+                                       float gamma, float alpha, int N, long HW, const unsigned char* valid, void* ws, float* out,
+                                       hipStream_t st) {
+    HN_CHECK_ARG(valid);
+    return seg_focal_fwd(logits, ldl, C, target, target_is_float, cw, gamma, alpha, N, HW, ws, out, valid, st);
+}
 
-extern "C" int hn_seg_focal_bwd(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* cw, float gamma,
-                                float alpha, int N, long HW, const float* gout, float* dlogits, int ldd, hipStream_t st) {
+static int seg_focal_bwd(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* cw, float gamma,
+                         float alpha, int N, long HW, const float* gout, float* dlogits, int ldd, const unsigned char* valid, hipStream_t st) {
     HN_CHECK_ARG(logits && target && cw && gout && dlogits && C >= 1 && C <= HN_SEG_MAXC && N > 0 && HW > 0);
     const long M = (long)N * HW;
     long blocks = (M + 255) / 256;
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(seg_focal_bwd_kernel, dim3(blocks), dim3(256), 0, st, logits, ldl, C, target, target_is_float, cw, gamma, alpha, M, gout,
-                       (float)(1.0 / (double)M), dlogits, ldd);
+                       (float)(1.0 / (double)M), dlogits, ldd, valid, HW);
     HN_LAUNCH_CHECK();
+}
+extern "C" int hn_seg_focal_bwd(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* cw, float gamma,
+                                float alpha, int N, long HW, const float* gout, float* dlogits, int ldd, hipStream_t st) {
+    return seg_focal_bwd(logits, ldl, C, target, target_is_float, cw, gamma, alpha, N, HW, gout, dlogits, ldd, nullptr, st);
+}
+extern "C" int hn_seg_focal_bwd_masked(const float* logits, int ldl, int C, const void* target, int target_is_float, const float* cw,
+                                       float gamma, float alpha, int N, long HW, const unsigned char* valid, const float* gout,
+                                       float* dlogits, int ldd, hipStream_t st) {
+    HN_CHECK_ARG(valid);
+    return seg_focal_bwd(logits, ldl, C, target, target_is_float, cw, gamma, alpha, N, HW, gout, dlogits, ldd, valid, st);
 }
 
 extern "C" int hn_argmax_channels(const float* logits, int ldl, int C, long M, long* out, hipStream_t st) {
@@ -686,32 +778,65 @@ extern "C" int hn_argmax_channels(const float* logits, int ldl, int C, long M, l
 extern "C" int hn_det_loss_blocks(int A) { return (A + 255) / 256; }
 
 // fwd: out[0] = classification loss, out[1] = regression loss (batch means); assign int16 [N][A], part fp32 [N][blocks][3], npos fp32 [N]
-extern "C" int hn_det_loss_fwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
-                               void* assign, float* part, float* npos, float* out, hipStream_t st) {
+// (valid: the det row of the task masks, hn_det_common.h; nullptr = every image labelled)
+static int det_loss_fwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                        void* assign, float* part, float* npos, float* out, const unsigned char* valid, hipStream_t st) {
     HN_CHECK_ARG(cls && reg && anchors && ann && assign && part && npos && out && N > 0 && A > 0 && K > 0 && K <= HN_DET_MAXK && Mx > 0);
     const int blocks = hn_det_loss_blocks(A);
-    hipLaunchKernelGGL(det_loss_fwd_kernel<false>, dim3(blocks, N), dim3(256), 0, st, cls, reg, anchors, ann, A, K, Mx, (short*)assign, part);
-    hipLaunchKernelGGL((det_loss_finalize_kernel<3, 4>), dim3(1), dim3(1024), 0, st, part, blocks, N, npos, out);
+    hipLaunchKernelGGL(det_loss_fwd_kernel<false>, dim3(blocks, N), dim3(256), 0, st, cls, reg, anchors, ann, A, K, Mx, (short*)assign, part, valid);
+    hipLaunchKernelGGL((det_loss_finalize_kernel<3, 4>), dim3(1), dim3(1024), 0, st, part, blocks, N, npos, out, valid);
     HN_LAUNCH_CHECK();
+}
+
+extern "C" int hn_det_loss_fwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                               void* assign, float* part, float* npos, float* out, hipStream_t st) {
+    return det_loss_fwd(cls, reg, anchors, ann, N, A, K, Mx, assign, part, npos, out, nullptr, st);
+}
+extern "C" int hn_det_loss_fwd_masked(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                                      const unsigned char* valid, void* assign, float* part, float* npos, float* out, hipStream_t st) {
+    HN_CHECK_ARG(valid);
+    return det_loss_fwd(cls, reg, anchors, ann, N, A, K, Mx, assign, part, npos, out, valid, st);
 }
 
 // hn_det_loss_fwd with assign [N][A] as an INPUT (values outside -2 .. Mx - 1 count as ignored); everything else as above
-extern "C" int hn_det_loss_fwd_assigned(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
-                                        const void* assign, float* part, float* npos, float* out, hipStream_t st) {
+static int det_loss_fwd_assigned(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                                 const void* assign, float* part, float* npos, float* out, const unsigned char* valid, hipStream_t st) {
     HN_CHECK_ARG(cls && reg && anchors && ann && assign && part && npos && out && N > 0 && A > 0 && K > 0 && K <= HN_DET_MAXK && Mx > 0);
     const int blocks = hn_det_loss_blocks(A);
-    hipLaunchKernelGGL(det_loss_fwd_kernel<true>, dim3(blocks, N), dim3(256), 0, st, cls, reg, anchors, ann, A, K, Mx, (short*)assign, part);
-    hipLaunchKernelGGL((det_loss_finalize_kernel<3, 4>), dim3(1), dim3(1024), 0, st, part, blocks, N, npos, out);
+    hipLaunchKernelGGL(det_loss_fwd_kernel<true>, dim3(blocks, N), dim3(256), 0, st, cls, reg, anchors, ann, A, K, Mx, (short*)assign, part, valid);
+    hipLaunchKernelGGL((det_loss_finalize_kernel<3, 4>), dim3(1), dim3(1024), 0, st, part, blocks, N, npos, out, valid);
     HN_LAUNCH_CHECK();
 }
 
-extern "C" int hn_det_loss_bwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
-                               const void* assign, const float* npos, const float* gout, float* dcls, float* dreg, hipStream_t st) {
+extern "C" int hn_det_loss_fwd_assigned(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                                        const void* assign, float* part, float* npos, float* out, hipStream_t st) {
+    return det_loss_fwd_assigned(cls, reg, anchors, ann, N, A, K, Mx, assign, part, npos, out, nullptr, st);
+}
+extern "C" int hn_det_loss_fwd_assigned_masked(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K,
+                                               int Mx, const unsigned char* valid, const void* assign, float* part, float* npos, float* out,
+                                               hipStream_t st) {
+    HN_CHECK_ARG(valid);
+    return det_loss_fwd_assigned(cls, reg, anchors, ann, N, A, K, Mx, assign, part, npos, out, valid, st);
+}
+
+static int det_loss_bwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                        const void* assign, const float* npos, const float* gout, float* dcls, float* dreg, const unsigned char* valid,
+                        hipStream_t st) {
     HN_CHECK_ARG(cls && reg && anchors && ann && assign && npos && gout && dcls && dreg && N > 0 && A > 0 && K > 0 && Mx > 0);
     HN_CHECK_ARG(K <= 48);                                             // 256 x K floats of LDS
     hipLaunchKernelGGL(det_loss_bwd_kernel, dim3(hn_det_loss_blocks(A), N), dim3(256), 256 * (size_t)K * sizeof(float), st, cls, reg, anchors, ann, N, A, K, Mx,
-                       (const short*)assign, npos, gout, dcls, dreg);
+                       (const short*)assign, npos, gout, dcls, dreg, valid);
     HN_LAUNCH_CHECK();
+}
+extern "C" int hn_det_loss_bwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                               const void* assign, const float* npos, const float* gout, float* dcls, float* dreg, hipStream_t st) {
+    return det_loss_bwd(cls, reg, anchors, ann, N, A, K, Mx, assign, npos, gout, dcls, dreg, nullptr, st);
+}
+extern "C" int hn_det_loss_bwd_masked(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                                      const unsigned char* valid, const void* assign, const float* npos, const float* gout, float* dcls,
+                                      float* dreg, hipStream_t st) {
+    HN_CHECK_ARG(valid);
+    return det_loss_bwd(cls, reg, anchors, ann, N, A, K, Mx, assign, npos, gout, dcls, dreg, valid, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -762,8 +887,13 @@ __device__ __forceinline__ void hist_select_256(const unsigned int* hist, unsign
     }
     __syncthreads();
 }
+// With a mask (valid: the lane row of the task masks, R rows per image) the rows of an unlabelled image are neither positive nor negative:
+// their log-probabilities are still written, but they stay out of the counts, the rank, the select and both sums.
+__device__ __forceinline__ bool lane_row_valid(const unsigned char* valid, int R, long i) { return !valid || valid[(int)i / R] != 0; }
+
 __global__ __launch_bounds__(1024) void lane_cls_fwd_kernel(const float* logits, const float* target, long M, float neg_ratio, float alpha,
-                                                            float* lsm, unsigned char* pmask, float* out, float* aux) {
+                                                            float* lsm, unsigned char* pmask, float* out, float* aux,
+                                                            const unsigned char* valid, int R) {
     __shared__ unsigned int hist[256];
     __shared__ float red[16];
     __shared__ unsigned int s_bin, s_k, s_wsum[4];
@@ -775,10 +905,11 @@ __global__ __launch_bounds__(1024) void lane_cls_fwd_kernel(const float* logits,
         const float lse = mx + logf(expf(z0 - mx) + expf(z1 - mx));
         lsm[2 * i] = z0 - lse;
         lsm[2 * i + 1] = z1 - lse;
-        const bool p = target[2 * i + 1] > 0.f;
+        const bool ok = lane_row_valid(valid, R, i);
+        const bool p = ok && target[2 * i + 1] > 0.f;
         pmask[i] = p ? 1 : 0;
         npos += p ? 1.f : 0.f;
-        nneg += p ? 0.f : 1.f;
+        nneg += p || !ok ? 0.f : 1.f;
     }
     npos = block_sum_1024(npos, red);
     nneg = block_sum_1024(nneg, red);
@@ -794,7 +925,7 @@ __global__ __launch_bounds__(1024) void lane_cls_fwd_kernel(const float* logits,
             __syncthreads();
             const unsigned int himask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
             for (long i = tid; i < M; i += 1024) {
-                if (pmask[i]) continue;
+                if (pmask[i] || !lane_row_valid(valid, R, i)) continue;
                 const unsigned int key = f2ord(lsm[2 * i]);
                 if ((key & himask) == prefix) atomicAdd(&hist[(key >> shift) & 255], 1u);
             }
@@ -809,7 +940,7 @@ __global__ __launch_bounds__(1024) void lane_cls_fwd_kernel(const float* logits,
     for (long i = tid; i < M; i += 1024) {
         const float bg = lsm[2 * i], fg = lsm[2 * i + 1];
         if (pmask[i]) sp += fg;
-        else if (bg <= thr) sn += bg;
+        else if (bg <= thr && lane_row_valid(valid, R, i)) sn += bg;
     }
     sp = block_sum_1024(sp, red);
     sn = block_sum_1024(sn, red);
@@ -823,13 +954,14 @@ __global__ __launch_bounds__(1024) void lane_cls_fwd_kernel(const float* logits,
 // round trip over the rows with one workgroup (58 us for 32 768 rows); here the rows are read once, the radix passes run on registers.
 template <int RPT>
 __global__ __launch_bounds__(1024) void lane_cls_fwd_reg_kernel(const float* logits, const float* target, long M, float neg_ratio, float alpha,
-                                                                float* lsm, unsigned char* pmask, float* out, float* aux) {
+                                                                float* lsm, unsigned char* pmask, float* out, float* aux,
+                                                                const unsigned char* vmask, int R) {
     __shared__ unsigned int hist[256];
     __shared__ float red[16];
     __shared__ unsigned int s_bin, s_k, s_wsum[4];
     const int tid = threadIdx.x;
     float bg[RPT], fg[RPT];
-    unsigned int pos = 0, valid = 0;                                  // bit j: row tid + 1024 j is a positive / exists
+    unsigned int pos = 0, valid = 0;                                  // bit j: row tid + 1024 j is a positive / exists (and is labelled)
     float npos = 0.f, nneg = 0.f;
 #pragma unroll
     for (int j0 = 0; j0 < RPT; j0 += 8) {                              // eight rows' loads in flight at a time
@@ -853,13 +985,14 @@ __global__ __launch_bounds__(1024) void lane_cls_fwd_reg_kernel(const float* log
             bg[j] = z0 - lse;
             fg[j] = z1 - lse;
             if (i < M) {
-                const bool p = tt[jj].y > 0.f;
-                valid |= 1u << j;
+                const bool ok = lane_row_valid(vmask, R, i);
+                const bool p = ok && tt[jj].y > 0.f;
+                valid |= ok ? (1u << j) : 0u;
                 pos |= p ? (1u << j) : 0u;
                 *reinterpret_cast<float2*>(lsm + 2 * i) = make_float2(bg[j], fg[j]);
                 pmask[i] = p ? 1 : 0;
                 npos += p ? 1.f : 0.f;
-                nneg += p ? 0.f : 1.f;
+                nneg += p || !ok ? 0.f : 1.f;
             }
         }
     }
@@ -905,7 +1038,7 @@ __global__ __launch_bounds__(1024) void lane_cls_fwd_reg_kernel(const float* log
 }
 // dlogits = gpos * d(pos)/dz + gneg * d(neg)/dz
 __global__ void lane_cls_bwd_kernel(const float* lsm, const unsigned char* pmask, const float* aux, const float* gpos, const float* gneg,
-                                    float alpha, long M, float* dlogits) {
+                                    float alpha, long M, float* dlogits, const unsigned char* valid, int R) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M) return;
     const float thr = aux[0], posn = aux[1];
@@ -916,7 +1049,7 @@ __global__ void lane_cls_bwd_kernel(const float* lsm, const unsigned char* pmask
         const float c = -alpha / posn * gpos[0];
         d0 = -p0 * c;
         d1 = (1.f - p1) * c;
-    } else if (bg <= thr) {                            // -alpha/P * log p_bg
+    } else if (bg <= thr && lane_row_valid(valid, R, i)) {   // -alpha/P * log p_bg
         const float c = -alpha / posn * gneg[0];
         d0 = (1.f - p0) * c;
         d1 = -p1 * c;
@@ -976,24 +1109,43 @@ __global__ void lane_loc_bwd_kernel(const float* pred, const float* tgt, const u
     dpred[idx] = g;
 }
 
-extern "C" int hn_lane_cls_loss_fwd(const float* logits, const float* target, long M, float neg_ratio, float alpha, float* lsm,
-                                    void* pmask, float* out, float* aux, hipStream_t st) {
+static int lane_cls_loss_fwd(const float* logits, const float* target, long M, float neg_ratio, float alpha, float* lsm,
+                             void* pmask, float* out, float* aux, const unsigned char* valid, int R, hipStream_t st) {
     HN_CHECK_ARG(logits && target && lsm && pmask && out && aux && M > 0 && M <= (1L << 22));
     const bool al8 = ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(lsm)) & 7) == 0;
     if (al8 && M <= 1024L * 8)
-        hipLaunchKernelGGL(lane_cls_fwd_reg_kernel<8>, dim3(1), dim3(1024), 0, st, logits, target, M, neg_ratio, alpha, lsm, (unsigned char*)pmask, out, aux);
+        hipLaunchKernelGGL(lane_cls_fwd_reg_kernel<8>, dim3(1), dim3(1024), 0, st, logits, target, M, neg_ratio, alpha, lsm, (unsigned char*)pmask, out, aux, valid, R);
     else if (al8 && M <= 1024L * 32)
-        hipLaunchKernelGGL(lane_cls_fwd_reg_kernel<32>, dim3(1), dim3(1024), 0, st, logits, target, M, neg_ratio, alpha, lsm, (unsigned char*)pmask, out, aux);
+        hipLaunchKernelGGL(lane_cls_fwd_reg_kernel<32>, dim3(1), dim3(1024), 0, st, logits, target, M, neg_ratio, alpha, lsm, (unsigned char*)pmask, out, aux, valid, R);
     else
-        hipLaunchKernelGGL(lane_cls_fwd_kernel, dim3(1), dim3(1024), 0, st, logits, target, M, neg_ratio, alpha, lsm, (unsigned char*)pmask, out, aux);
+        hipLaunchKernelGGL(lane_cls_fwd_kernel, dim3(1), dim3(1024), 0, st, logits, target, M, neg_ratio, alpha, lsm, (unsigned char*)pmask, out, aux, valid, R);
+    HN_LAUNCH_CHECK();
+}
+extern "C" int hn_lane_cls_loss_fwd(const float* logits, const float* target, long M, float neg_ratio, float alpha, float* lsm,
+                                    void* pmask, float* out, float* aux, hipStream_t st) {
+    return lane_cls_loss_fwd(logits, target, M, neg_ratio, alpha, lsm, pmask, out, aux, nullptr, 1, st);
+}
+/* rows: rows per image (M = N x rows); valid: uint8 [N] */
+extern "C" int hn_lane_cls_loss_fwd_masked(const float* logits, const float* target, long M, int rows, const unsigned char* valid,
+                                           float neg_ratio, float alpha, float* lsm, void* pmask, float* out, float* aux, hipStream_t st) {
+    HN_CHECK_ARG(valid && rows > 0 && M > 0 && M % rows == 0);
+    return lane_cls_loss_fwd(logits, target, M, neg_ratio, alpha, lsm, pmask, out, aux, valid, rows, st);
+}
+static int lane_cls_loss_bwd(const float* lsm, const void* pmask, const float* aux, const float* gpos, const float* gneg, float alpha,
+                             long M, float* dlogits, const unsigned char* valid, int R, hipStream_t st) {
+    HN_CHECK_ARG(lsm && pmask && aux && gpos && gneg && dlogits && M > 0);
+    hipLaunchKernelGGL(lane_cls_bwd_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, lsm, (const unsigned char*)pmask, aux, gpos, gneg,
+                       alpha, M, dlogits, valid, R);
     HN_LAUNCH_CHECK();
 }
 extern "C" int hn_lane_cls_loss_bwd(const float* lsm, const void* pmask, const float* aux, const float* gpos, const float* gneg, float alpha,
                                     long M, float* dlogits, hipStream_t st) {
-    HN_CHECK_ARG(lsm && pmask && aux && gpos && gneg && dlogits && M > 0);
-    hipLaunchKernelGGL(lane_cls_bwd_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, lsm, (const unsigned char*)pmask, aux, gpos, gneg,
-                       alpha, M, dlogits);
-    HN_LAUNCH_CHECK();
+    return lane_cls_loss_bwd(lsm, pmask, aux, gpos, gneg, alpha, M, dlogits, nullptr, 1, st);
+}
+extern "C" int hn_lane_cls_loss_bwd_masked(const float* lsm, const void* pmask, const float* aux, const float* gpos, const float* gneg,
+                                           float alpha, long M, int rows, const unsigned char* valid, float* dlogits, hipStream_t st) {
+    HN_CHECK_ARG(valid && rows > 0 && M > 0 && M % rows == 0 && M <= (1L << 22));
+    return lane_cls_loss_bwd(lsm, pmask, aux, gpos, gneg, alpha, M, dlogits, valid, rows, st);
 }
 extern "C" int hn_lane_loc_loss_fwd(const float* pred, const float* target, const void* pmask, const float* aux, long M, int L, int wcol,
                                     float alpha, float* rowloss, float* rownorm, float* out, hipStream_t st) {

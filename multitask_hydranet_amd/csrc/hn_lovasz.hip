@@ -88,7 +88,8 @@ template <int CT>
 __global__ __launch_bounds__(LV_THREADS) void lv_key_kernel(const float* __restrict__ logits, int ldl, int Cr, const void* __restrict__ target,
                                                             int tf, int ignore_index, long P, long nblk, unsigned* __restrict__ keys,
                                                             unsigned* __restrict__ vals, unsigned* __restrict__ hist,
-                                                            unsigned* __restrict__ counts) {
+                                                            unsigned* __restrict__ counts, const unsigned char* __restrict__ vmask,
+                                                            long HW) {
     extern __shared__ unsigned lv_sh[];
     const int C = CT > 0 ? CT : Cr;
     unsigned* sh = lv_sh;
@@ -106,6 +107,7 @@ __global__ __launch_bounds__(LV_THREADS) void lv_key_kernel(const float* __restr
         const float* row = logits + (act ? i : 0) * (long)ldl;
         if (act) {
             y = lv_label(target, tf, i);
+            if (vmask && !vmask[i / HW]) y = ignore_index;             // a pixel of an unlabelled image (task mask): dropped like an ignored one
             mx = row[0];
             for (int c = 1; c < C; ++c) mx = fmaxf(mx, row[c]);
             float se = 0.f;
@@ -349,9 +351,10 @@ __global__ __launch_bounds__(LV_THREADS) void lv_finalize_kernel(const float* __
 // gradient of one pixel: st(c, value) for every class (zeros for an ignored pixel).  pmask: present classes; scale = gout / n_present.
 template <int CT, typename Store>
 __device__ __forceinline__ void lv_pixel_grad(const float* __restrict__ logits, int ldl, int C, const void* __restrict__ target, int tf,
-                                              int ignore_index, long m, const float* __restrict__ g, unsigned pmask, float scale, Store st) {
+                                              int ignore_index, long m, const float* __restrict__ g, unsigned pmask, float scale, Store st,
+                                              const unsigned char* __restrict__ vmask, long HW) {
     const long y = lv_label(target, tf, m);
-    if (y == ignore_index || scale == 0.f) {
+    if (y == ignore_index || scale == 0.f || (vmask && !vmask[m / HW])) {
         for (int c = 0; c < C; ++c) st(c, 0.f);
         return;
     }
@@ -385,14 +388,15 @@ __device__ __forceinline__ void lv_present(const unsigned* counts, int C, const 
 template <int CT>
 __global__ __launch_bounds__(256) void lv_bwd_kernel(const float* __restrict__ logits, int ldl, int Cr, const void* __restrict__ target, int tf,
                                                      int ignore_index, long P, const float* __restrict__ g, const unsigned* __restrict__ counts,
-                                                     const float* __restrict__ gout, float* __restrict__ dl, int ldd) {
+                                                     const float* __restrict__ gout, float* __restrict__ dl, int ldd,
+                                                     const unsigned char* __restrict__ vmask, long HW) {
     const int C = CT > 0 ? CT : Cr;
     unsigned pmask;
     float scale;
     lv_present(counts, C, gout, pmask, scale);
     for (long m = (long)blockIdx.x * 256 + threadIdx.x; m < P; m += (long)gridDim.x * 256) {
         float* d = dl + m * ldd;
-        lv_pixel_grad<CT>(logits, ldl, C, target, tf, ignore_index, m, g, pmask, scale, [=](int c, float v) { d[c] = v; });
+        lv_pixel_grad<CT>(logits, ldl, C, target, tf, ignore_index, m, g, pmask, scale, [=](int c, float v) { d[c] = v; }, vmask, HW);
     }
 }
 
@@ -402,7 +406,7 @@ template <int CT>
 __global__ __launch_bounds__(256) void lv_bwd_s2d_kernel(const float* __restrict__ logits, int ldl, int Cr, const void* __restrict__ target,
                                                          int tf, int ignore_index, int H, int W, long M4, const float* __restrict__ g,
                                                          const unsigned* __restrict__ counts, const float* __restrict__ gout,
-                                                         bf16* __restrict__ dz, int ldz) {
+                                                         bf16* __restrict__ dz, int ldz, const unsigned char* __restrict__ vmask) {
     const int C = CT > 0 ? CT : Cr;
     unsigned pmask;
     float scale;
@@ -419,7 +423,7 @@ __global__ __launch_bounds__(256) void lv_bwd_s2d_kernel(const float* __restrict
         for (int ph = 0; ph < 4; ++ph) {
             const long m = (long)n * HW + (long)(2 * y + (ph >> 1)) * W + 2 * x + (ph & 1);
             bf16* dp = d + ph * C;
-            lv_pixel_grad<CT>(logits, ldl, C, target, tf, ignore_index, m, g, pmask, scale, [=](int c, float v) { dp[c] = f2bf(v); });
+            lv_pixel_grad<CT>(logits, ldl, C, target, tf, ignore_index, m, g, pmask, scale, [=](int c, float v) { dp[c] = f2bf(v); }, vmask, HW);
         }
         for (int c = 4 * C; c < ldz; ++c) d[c] = f2bf(0.f);
     }
@@ -473,8 +477,9 @@ extern "C" long hn_seg_lovasz_ws_bytes(int N, long HW, int C) {
 
 static std::atomic<unsigned long long> g_lv_key_lds{0};
 
-extern "C" int hn_seg_lovasz_fwd(const float* logits, int ldl, int C, const void* target, int target_is_float, int ignore_index, int N,
-                                 long HW, void* ws, float* out, hipStream_t st) {
+// (valid: the seg row of the task masks, uint8 [N]; nullptr = every image labelled.  Same launches either way.)
+static int seg_lovasz_fwd(const float* logits, int ldl, int C, const void* target, int target_is_float, int ignore_index, int N,
+                          long HW, void* ws, float* out, const unsigned char* valid, hipStream_t st) {
     HN_CHECK_ARG(logits && target && ws && out && C >= 2 && C <= HN_SEG_MAXC && ldl >= C && N > 0 && HW > 0);
     const long P = (long)N * HW;
     HN_CHECK_ARG(P <= 0x7FFFFFFFL);                  // pixel index + fg bit in one 32-bit payload
@@ -488,10 +493,10 @@ extern "C" int hn_seg_lovasz_fwd(const float* logits, int ldl, int C, const void
     hipLaunchKernelGGL(lv_zero_kernel, dim3(1), dim3(64), 0, st, L.counts, 32);
     if (C == 5)
         hipLaunchKernelGGL(lv_key_kernel<5>, dim3((unsigned)nblk), dim3(LV_THREADS), key_lds, st, logits, ldl, C, target, target_is_float,
-                           ignore_index, P, nblk, L.keysA, L.valsA, L.hist, L.counts);
+                           ignore_index, P, nblk, L.keysA, L.valsA, L.hist, L.counts, valid, HW);
     else
         hipLaunchKernelGGL(lv_key_kernel<0>, dim3((unsigned)nblk), dim3(LV_THREADS), key_lds, st, logits, ldl, C, target, target_is_float,
-                           ignore_index, P, nblk, L.keysA, L.valsA, L.hist, L.counts);
+                           ignore_index, P, nblk, L.keysA, L.valsA, L.hist, L.counts, valid, HW);
     const dim3 tiles((unsigned)(C * nblk)), rows((unsigned)(C * LV_BINS));
     unsigned *kin = L.keysA, *vin = L.valsA, *kout = L.keysB, *vout = L.valsB;
     for (int pass = 0; pass < 3; ++pass) {
@@ -508,9 +513,18 @@ extern "C" int hn_seg_lovasz_fwd(const float* logits, int ldl, int C, const void
     hipLaunchKernelGGL(lv_finalize_kernel, dim3(1), dim3(LV_THREADS), 0, st, L.part, nblk, C, L.counts, out);
     HN_LAUNCH_CHECK();
 }
+extern "C" int hn_seg_lovasz_fwd(const float* logits, int ldl, int C, const void* target, int target_is_float, int ignore_index, int N,
+                                 long HW, void* ws, float* out, hipStream_t st) {
+    return seg_lovasz_fwd(logits, ldl, C, target, target_is_float, ignore_index, N, HW, ws, out, nullptr, st);
+}
+extern "C" int hn_seg_lovasz_fwd_masked(const float* logits, int ldl, int C, const void* target, int target_is_float, int ignore_index, int N,
+                                        long HW, const unsigned char* valid, void* ws, float* out, hipStream_t st) {
+    HN_CHECK_ARG(valid);
+    return seg_lovasz_fwd(logits, ldl, C, target, target_is_float, ignore_index, N, HW, ws, out, valid, st);
+}
 
-extern "C" int hn_seg_lovasz_bwd(const float* logits, int ldl, int C, const void* target, int target_is_float, int ignore_index, int N,
-                                 long HW, const void* ws, const float* gout, float* dlogits, int ldd, hipStream_t st) {
+static int seg_lovasz_bwd(const float* logits, int ldl, int C, const void* target, int target_is_float, int ignore_index, int N,
+                          long HW, const void* ws, const float* gout, float* dlogits, int ldd, const unsigned char* valid, hipStream_t st) {
     HN_CHECK_ARG(logits && target && ws && gout && dlogits && C >= 2 && C <= HN_SEG_MAXC && ldl >= C && ldd >= C && N > 0 && HW > 0);
     const long P = (long)N * HW;
     HN_CHECK_ARG(P <= 0x7FFFFFFFL);
@@ -520,15 +534,26 @@ extern "C" int hn_seg_lovasz_bwd(const float* logits, int ldl, int C, const void
     if (blocks > 8192) blocks = 8192;
     if (C == 5)
         hipLaunchKernelGGL(lv_bwd_kernel<5>, dim3((unsigned)blocks), dim3(256), 0, st, logits, ldl, C, target, target_is_float, ignore_index, P,
-                           (const float*)L.keysA, L.counts, gout, dlogits, ldd);
+                           (const float*)L.keysA, L.counts, gout, dlogits, ldd, valid, HW);
     else
         hipLaunchKernelGGL(lv_bwd_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, st, logits, ldl, C, target, target_is_float, ignore_index, P,
-                           (const float*)L.keysA, L.counts, gout, dlogits, ldd);
+                           (const float*)L.keysA, L.counts, gout, dlogits, ldd, valid, HW);
     HN_LAUNCH_CHECK();
 }
 
-extern "C" int hn_seg_lovasz_bwd_s2d(const float* logits, int ldl, int C, const void* target, int target_is_float, int ignore_index, int N,
-                                     int H, int W, const void* ws, const float* gout, void* dz, int ldz, hipStream_t st) {
+extern "C" int hn_seg_lovasz_bwd(const float* logits, int ldl, int C, const void* target, int target_is_float, int ignore_index, int N,
+                                 long HW, const void* ws, const float* gout, float* dlogits, int ldd, hipStream_t st) {
+    return seg_lovasz_bwd(logits, ldl, C, target, target_is_float, ignore_index, N, HW, ws, gout, dlogits, ldd, nullptr, st);
+}
+extern "C" int hn_seg_lovasz_bwd_masked(const float* logits, int ldl, int C, const void* target, int target_is_float, int ignore_index, int N,
+                                        long HW, const unsigned char* valid, const void* ws, const float* gout, float* dlogits, int ldd,
+                                        hipStream_t st) {
+    HN_CHECK_ARG(valid);
+    return seg_lovasz_bwd(logits, ldl, C, target, target_is_float, ignore_index, N, HW, ws, gout, dlogits, ldd, valid, st);
+}
+
+static int seg_lovasz_bwd_s2d(const float* logits, int ldl, int C, const void* target, int target_is_float, int ignore_index, int N,
+                              int H, int W, const void* ws, const float* gout, void* dz, int ldz, const unsigned char* valid, hipStream_t st) {
     HN_CHECK_ARG(logits && target && ws && gout && dz && C >= 2 && C <= HN_SEG_MAXC && ldl >= C && N > 0 && H > 0 && W > 0 && !(H & 1) &&
                  !(W & 1) && ldz >= 4 * C);
     const long HW = (long)H * W, P = (long)N * HW;
@@ -539,9 +564,19 @@ extern "C" int hn_seg_lovasz_bwd_s2d(const float* logits, int ldl, int C, const 
     if (blocks > 8192) blocks = 8192;
     if (C == 5)
         hipLaunchKernelGGL(lv_bwd_s2d_kernel<5>, dim3((unsigned)blocks), dim3(256), 0, st, logits, ldl, C, target, target_is_float, ignore_index,
-                           H, W, P / 4, (const float*)L.keysA, L.counts, gout, (bf16*)dz, ldz);
+                           H, W, P / 4, (const float*)L.keysA, L.counts, gout, (bf16*)dz, ldz, valid);
     else
         hipLaunchKernelGGL(lv_bwd_s2d_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, st, logits, ldl, C, target, target_is_float, ignore_index,
-                           H, W, P / 4, (const float*)L.keysA, L.counts, gout, (bf16*)dz, ldz);
+                           H, W, P / 4, (const float*)L.keysA, L.counts, gout, (bf16*)dz, ldz, valid);
     HN_LAUNCH_CHECK();
+}
+extern "C" int hn_seg_lovasz_bwd_s2d(const float* logits, int ldl, int C, const void* target, int target_is_float, int ignore_index, int N,
+                                     int H, int W, const void* ws, const float* gout, void* dz, int ldz, hipStream_t st) {
+    return seg_lovasz_bwd_s2d(logits, ldl, C, target, target_is_float, ignore_index, N, H, W, ws, gout, dz, ldz, nullptr, st);
+}
+extern "C" int hn_seg_lovasz_bwd_s2d_masked(const float* logits, int ldl, int C, const void* target, int target_is_float, int ignore_index,
+                                            int N, int H, int W, const unsigned char* valid, const void* ws, const float* gout, void* dz, int ldz,
+                                            hipStream_t st) {
+    HN_CHECK_ARG(valid);
+    return seg_lovasz_bwd_s2d(logits, ldl, C, target, target_is_float, ignore_index, N, H, W, ws, gout, dz, ldz, valid, st);
 }

@@ -12,6 +12,12 @@ the batch carries the zlib streams (`src_seg_streams`), which to_gpu inflates an
     ds = MultitaskData(cfgs, "train")                 # with dataloader.do_split: MultitaskData(cfgs, "train", split_rule=augment.cal_split)
     loader = DataLoader(ds, batch_size=16, shuffle=True, num_workers=8, collate_fn=ds.collate_fn, pin_memory=True)
     for epoch in ...: ds.set_epoch(epoch); trainer.train_one_epoch(epoch)
+
+With dataloader.allow_missing_labels (default False: a missing label file raises FileNotFoundError, as ever) an image may lack the label
+file of some trained tasks: every item carries `task_valid`, (seg, det, lane) as 0 / 1, the batch a uint8 [3, N] array of them, and the
+losses are masked with it (HydraNet.cal_loss).  A missing label is replaced by a stand-in of the right shape -- an all-255
+label map, no boxes, no lines -- so that packing, augmentation and the lane encoder run unchanged; the stand-ins only fill shapes, the
+masks decide what is trained.  Images without a label for any trained task are dropped at construction (`unlabelled` counts them).
 """
 from __future__ import annotations
 
@@ -129,6 +135,19 @@ class MultitaskData:
             raise NotImplementedError("mode should be one of ('train', 'val')")
         lst = os.path.join(dl["data_list"], "train.txt" if mode == "train" else "valid.txt")
         self.image_annot_path_pairs = create_subset(lst, with_lane=self.train_lane, with_seg=self.train_seg, with_detect=self.train_detect)
+        # dataloader.allow_missing_labels: every derived label path is checked once, here; an item then knows which labels it has
+        self.allow_missing_labels = bool(dl.get("allow_missing_labels", False))
+        self.unlabelled = 0
+        if self.allow_missing_labels:
+            kept = []
+            for pair in self.image_annot_path_pairs:
+                pair["task_valid"] = tuple(int(key in pair and os.path.isfile(pair[key]))
+                                           for key in ("annot_path_seg", "annot_path_detect", "annot_path_lane"))
+                if any(pair["task_valid"]):
+                    kept.append(pair)
+                else:
+                    self.unlabelled += 1
+            self.image_annot_path_pairs = kept
 
     def set_epoch(self, epoch: int):
         """plans are seeded from (base_seed, epoch, index): call before every epoch's iteration"""
@@ -170,20 +189,28 @@ class MultitaskData:
             item = dict(src_coefs=img, jpeg_head=head, src_image_shape=dict(width=w, height=h, channel=3), src_image_path=pair["image_path"])
         else:
             item = dict(src_frame=img, src_image_shape=dict(width=w, height=h, channel=3), src_image_path=pair["image_path"])
+        has_seg, has_det, has_lane = pair.get("task_valid", (1, 1, 1))       # (without allow_missing_labels: every file is opened)
+        if self.allow_missing_labels:
+            item["task_valid"] = np.array(pair["task_valid"], dtype=np.uint8)
         if self.train_lane:
-            with open(pair["annot_path_lane"]) as f:
-                item["lane_raw"] = parse_own_label(json.load(f))
+            if has_lane:
+                with open(pair["annot_path_lane"]) as f:
+                    item["lane_raw"] = parse_own_label(json.load(f))
+            else:
+                item["lane_raw"] = {"Lines": [], "Labels": []}             # stand-in: no lines
             item["annot_lane_path"] = pair["annot_path_lane"]
         if not self.with_aug:
             item["aug_plan"] = identity_plan()
         elif self.do_split:                                   # dataloader.py:300-304: the ratio from the source lanes at source size
-            ok, ratio = self.split_rule(item["lane_raw"], w, h)
+            ok, ratio = self.split_rule(item["lane_raw"], w, h) if has_lane else (False, None)     # no lane label: not split
             item["aug_plan"] = sample_plan(self.base_seed, self.epoch, idx, do_flip=self.do_flip, do_split=True, split_ratio=ratio if ok else None)
         else:
             item["aug_plan"] = sample_plan(self.base_seed, self.epoch, idx, do_flip=self.do_flip)
         if self.train_seg:
             phead = None
-            if self.decode_labels == "device":
+            if not has_seg:
+                seg = np.full((h, w), 255, dtype=np.uint8)              # stand-in: every pixel ignored (the already-decoded slot of either path)
+            elif self.decode_labels == "device":
                 from . import png
                 phead, seg = png.stream_stage(png.read_bytes(pair["annot_path_seg"]))   # (head, zlib stream) or (None, PIL's map)
             else:
@@ -196,7 +223,7 @@ class MultitaskData:
             else:
                 item["src_seg"] = seg
         if self.train_detect:
-            item["det_raw"] = load_detect_annot(pair["annot_path_detect"])
+            item["det_raw"] = load_detect_annot(pair["annot_path_detect"]) if has_det else np.zeros((0, 5), dtype=np.float64)
         return item
 
     def collate_fn(self, batch):
@@ -208,7 +235,8 @@ def collate(batch, net_h, net_w):
     entropy-decoded items (decode="device") carries `src_coefs` instead of `src_frames`: jpeg.pack_coefs' buffers, the PIL-decoded frames of
     its unsupported files among them; one with items of decode="device-entropy" carries `src_streams`, jpeg.pack_streams' buffers, likewise.
     A batch with items of decode_labels="device" carries `src_seg_streams` (png.pack_streams' buffers, the PIL-decoded maps of its
-    unsupported files among them) in place of `src_segs`."""
+    unsupported files among them) in place of `src_segs`.  Items of dataloader.allow_missing_labels carry `task_valid`: the batch's is the
+    uint8 [3, N] array of them (rows seg, det, lane), which HydraTrainer.to_gpu copies to the device."""
     if any("src_stream" in b for b in batch):
         from .jpeg import pack_streams
         src = dict(src_streams=pack_streams([(b["jpeg_head"], b["jpeg_scan"], b["src_stream"]) if "src_stream" in b else (None, b["src_frame"])
@@ -231,4 +259,6 @@ def collate(batch, net_h, net_w):
         out["src_segs"] = pack([b["src_seg"] for b in batch])
     if "det_raw" in batch[0]:
         out["det_raw"] = [b["det_raw"] for b in batch]
+    if "task_valid" in batch[0]:
+        out["task_valid"] = np.ascontiguousarray(np.stack([b["task_valid"] for b in batch], axis=1).astype(np.uint8))
     return out

@@ -875,36 +875,60 @@ class HydraNet(nn.Module):
                                             *(self.deploy_postprocess[2:3] or (4096,))),)
         return dep
 
-    def _seg_loss(self, logits, target):
+    def _seg_loss(self, logits, target, valid=None):
         """CrossEntropyLoss.forward (head_seg/segmentation_loss.py:27-65) on HIP kernels: the weighted-CE / top-k path of the big cfgs
         (hn_seg_loss_*) and the focal variant of the small cfg (hn_seg_focal_*); with use_lovasz the Lovasz-softmax loss instead
-        (lovasz_softmax(F.softmax(seg, 1), gt, ignore=255), model.py:207-210; hn_seg_lovasz_*).  No CPU fallback: raises off-device."""
+        (lovasz_softmax(F.softmax(seg, 1), gt, ignore=255), model.py:207-210; hn_seg_lovasz_*).  No CPU fallback: raises off-device.
+        valid: the seg row of gt_dict["task_valid"] (cal_loss), None without it."""
+        kw = {} if valid is None else {"valid": valid}
         use_top_k, ratio, use_focal = self._seg_cfg
         key = getattr(self, "_seg_grad_slot", None)
         self._seg_grad_slot = None                                    # consumed (or dropped) by the first loss call after the forward
         if self.use_lovasz:
             slot = key[0] if (key is not None and key[1]() is logits) else None
-            return K.seg_lovasz_loss_hip(logits, target, ignore_index=255, slot=slot)
+            return K.seg_lovasz_loss_hip(logits, target, ignore_index=255, slot=slot, **kw)
         if use_focal:
             # (the reference always hands gt_seg.long() to the loss, model.py:212; to_gpu delivers float32 class ids: both are accepted)
-            return K.seg_focal_loss_hip(logits, target, self._seg_class_weight)
+            return K.seg_focal_loss_hip(logits, target, self._seg_class_weight, **kw)
         slot = None
         if key is not None and key[1]() is logits:
             slot = key[0]                                             # this forward's own "seg" output
-        return K.seg_loss_hip(logits, target, self._seg_class_weight, use_top_k, ratio, slot=slot)
+        return K.seg_loss_hip(logits, target, self._seg_class_weight, use_top_k, ratio, slot=slot, **kw)
 
     def _guard(self, value, what, allow_zero=False):
         if self.check_finite and ((not allow_zero and value == 0) or not torch.isfinite(value)):
             print(what)
             sys.exit()
 
+    TASK_VALID_ROWS = {"seg": 0, "det": 1, "lane": 2}
+
+    def _task_valid(self, pred_dict, gt_dict):
+        """gt_dict["task_valid"]: uint8 [3, N] on the predictions' device, row 0 seg, 1 det, 2 lane, 1 = image n is labelled for the task.
+        Returns the rows as keyword arguments for the losses (contiguous views: no copies, no launches); {} without the key."""
+        tv = gt_dict.get("task_valid") if hasattr(gt_dict, "get") else None
+        if tv is None:
+            return {}
+        ref = next(v for v in (pred_dict.get("seg"), (pred_dict.get("detection") or {}).get("classification"),
+                               (pred_dict.get("lane") or {}).get("predict_cls")) if v is not None)
+        n = ref.shape[0]
+        if not isinstance(tv, torch.Tensor) or tv.dtype != torch.uint8 or tuple(tv.shape) != (3, n) or tv.device != ref.device:
+            what = f"{tv.dtype} {tuple(tv.shape)} on {tv.device}" if isinstance(tv, torch.Tensor) else repr(type(tv))
+            raise ValueError(f"gt_dict['task_valid'] must be a uint8 [3, {n}] tensor on {ref.device}, got {what}")
+        tv = tv.contiguous()
+        return {task: {"valid": tv[row]} for task, row in self.TASK_VALID_ROWS.items()}
+
     def cal_loss(self, pred_dict, gt_dict):
-        """HydraNet.cal_loss, model/model.py:201-264 (same keys, same divergence guard)."""
+        """HydraNet.cal_loss, model/model.py:201-264 (same keys, same divergence guard).  With gt_dict["task_valid"] (_task_valid) every
+        task's losses are those of the sub-batch of its labelled images (ops/losses.py); a task without a labelled image in the batch has
+        loss 0, which is then no divergence (non-finite still is)."""
         ld = {}
+        tv = self._task_valid(pred_dict, gt_dict)
+        masked = bool(tv)
         if self.train_seg:
             gt_seg = gt_dict["gt_seg"]
-            loss_seg = self.loss_seg(pred_dict["seg"], gt_seg if gt_seg.dtype == torch.float32 and gt_seg.is_cuda else gt_seg.long())
-            self._guard(loss_seg, "cal segment loss diverge!")
+            loss_seg = self.loss_seg(pred_dict["seg"], gt_seg if gt_seg.dtype == torch.float32 and gt_seg.is_cuda else gt_seg.long(),
+                                     **tv.get("seg", {}))
+            self._guard(loss_seg, "cal segment loss diverge!", allow_zero=masked)
             ld["loss_seg"] = loss_seg
         if self.train_detect:
             d = pred_dict["detection"]
@@ -912,9 +936,10 @@ class HydraNet(nn.Module):
                 h, w = self._anchor_hw(d["anchors"])
                 assign, _ = K.det_atss_assign(d["anchors"], self.anchor_level_sizes(h, w), gt_dict["gt_det"], self.atss_topk,
                                               self.anchors_per_location)
-                cl, rl, *iou = self.loss_detect(d["classification"], d["regression"], d["anchors"], gt_dict["gt_det"], assign=assign)
+                cl, rl, *iou = self.loss_detect(d["classification"], d["regression"], d["anchors"], gt_dict["gt_det"], assign=assign,
+                                                **tv.get("det", {}))
             else:
-                cl, rl, *iou = self.loss_detect(d["classification"], d["regression"], d["anchors"], gt_dict["gt_det"])
+                cl, rl, *iou = self.loss_detect(d["classification"], d["regression"], d["anchors"], gt_dict["gt_det"], **tv.get("det", {}))
             self.det_pos_iou = iou[0].detach().reshape(()) if iou else None      # (IoU types only: the positives' mean IoU, a device scalar)
             # the reference takes .mean() of the [1]-shaped batch means (model.py:226-227): a reshape for one element
             cl, rl = (cl.reshape(()) if cl.numel() == 1 else cl.mean()), (rl.reshape(()) if rl.numel() == 1 else rl.mean())
@@ -922,12 +947,16 @@ class HydraNet(nn.Module):
             self._guard(rl, "cal det reg loss diverge!", allow_zero=True)
             ld["loss_det_cls"], ld["loss_det_reg"] = cl, rl
         if self.train_lane:
-            pos, neg, pmask, pnum = self.loss_cls(gt_dict["gt_cls"], pred_dict["lane"]["predict_cls"])
+            lkw = {}
+            if masked:
+                pc = pred_dict["lane"]["predict_cls"]
+                lkw = dict(tv["lane"], rows_per_image=pc.numel() // 2 // pc.shape[0])
+            pos, neg, pmask, pnum = self.loss_cls(gt_dict["gt_cls"], pred_dict["lane"]["predict_cls"], **lkw)
             loc = self.loss_reg(pmask, pnum, gt_dict["gt_loc"], pred_dict["lane"]["predict_loc"],
-                                points_per_line=self.lane_points_per_line)
-            self._guard(pos, "cal lane pos loss diverge!")
-            self._guard(neg, "cal lane neg loss diverge!")
-            self._guard(loc, "cal lane loc loss diverge!")
+                                points_per_line=self.lane_points_per_line, **lkw)
+            self._guard(pos, "cal lane pos loss diverge!", allow_zero=masked)
+            self._guard(neg, "cal lane neg loss diverge!", allow_zero=masked)
+            self._guard(loc, "cal lane loc loss diverge!", allow_zero=masked)
             ld["loss_lane_cls_pos"], ld["loss_lane_cls_neg"], ld["loss_lane_loc"] = pos, neg, loc
         return ld
 

@@ -17,16 +17,41 @@ from .heads import *        # noqa: F401,F403
 
 
 # --------------------------------------------------------------------------------------------------------------
+# Per-image task masks (gt_dict["task_valid"]).  Every loss below takes valid=None: None is the unmasked call; a task's row of
+# the mask tensor -- contiguous uint8 [N] on the loss's device, 1 = image n is labelled for the task -- goes to the `_masked` twin of every
+# entry point.  The rule: the losses equal the unmasked losses of the sub-batch of labelled images, taken in batch order; without a
+# labelled image every loss is 0; the gradient of an unlabelled image's predictions is written as exactly 0.  Same launches as the
+# unmasked call, the mask is read on the device, and one captured graph replayed with other mask contents gives those masks' results.
+# --------------------------------------------------------------------------------------------------------------
+def _task_valid_row(valid, n, dev):
+    if (not isinstance(valid, torch.Tensor) or valid.dtype != torch.uint8 or tuple(valid.shape) != (n,) or valid.device != dev
+            or not valid.is_contiguous()):
+        what = f"{valid.dtype} {tuple(valid.shape)} on {valid.device}" if isinstance(valid, torch.Tensor) else repr(type(valid))
+        raise ValueError(f"valid must be a contiguous uint8 [{n}] tensor on {dev}, got {what}")
+    return valid
+
+
+def _masked(name, valid):
+    return name if valid is None else name + "_masked"
+
+
+def _v(valid):
+    """the mask argument of a `_masked` entry point (placed before the workspace / outputs), nothing for the unmasked one"""
+    return () if valid is None else (ptr(valid),)
+
+
+# --------------------------------------------------------------------------------------------------------------
 # segmentation loss (weighted CE + ignore_index + top-k hardest pixels) and deploy-mode argmax
 # --------------------------------------------------------------------------------------------------------------
 class SegLoss(torch.autograd.Function):
     """logits: fp32 NHWC [N, H, W, C] (dense rows); target: [N, H, W] int64 or float32 class ids."""
 
     @staticmethod
-    def forward(ctx, logits, target, class_weights, use_top_k, top_k_ratio, ignore_index, slot=None):
+    def forward(ctx, logits, target, class_weights, use_top_k, top_k_ratio, ignore_index, slot=None, valid=None):
         """slot (GradSlot of the producing SegOutUp node): the gradient is handed over as that node's space-to-depth bf16 operand
         (hn_seg_loss_bwd_s2d) instead of an fp32 dlogits tensor"""
         n, h, w, c = logits.shape
+        ctx.valid = valid = None if valid is None else _task_valid_row(valid, n, logits.device)
         hw = h * w
         ctx.slot = slot if (slot is not None and h % 2 == 0 and w % 2 == 0) else None
         ctx.hw_dims = (h, w)
@@ -36,8 +61,8 @@ class SegLoss(torch.autograd.Function):
         out = torch.empty((1,), device=dev, dtype=F32)
         tf = 1 if target.dtype == torch.float32 else 0
         assert target.dtype in (torch.float32, torch.int64) and target.is_contiguous()
-        lib().call("hn_seg_loss_fwd", ptr(logits), logits.stride(2), c, ptr(target), tf, ptr(class_weights), ignore_index, n, hw,
-                   1 if use_top_k else 0, k, ptr(ws), ptr(out))
+        lib().call(_masked("hn_seg_loss_fwd", valid), ptr(logits), logits.stride(2), c, ptr(target), tf, ptr(class_weights), ignore_index, n, hw,
+                   1 if use_top_k else 0, k, *_v(valid), ptr(ws), ptr(out))
         ctx.meta = (n, hw, c, tf, 1 if use_top_k else 0, k, ignore_index)
         ctx.save_for_backward(logits, target, class_weights, ws)
         return out.view(())
@@ -46,27 +71,31 @@ class SegLoss(torch.autograd.Function):
     def backward(ctx, gout):
         logits, target, cw, ws = ctx.saved_tensors
         n, hw, c, tf, topk, k, ign = ctx.meta
+        valid = ctx.valid
         g = gout.contiguous().to(F32).view(1)
         if ctx.slot is not None and ctx.slot.buf is None:
             h, w = ctx.hw_dims
             dz = new_act(n, h // 2, w // 2, pad8(4 * c), logits.device)
-            lib().call("hn_seg_loss_bwd_s2d", ptr(logits), logits.stride(2), c, ptr(target), tf, ptr(cw), ign, n, h, w, topk, k, ptr(ws), ptr(g),
-                       ptr(dz), ld(dz))
+            lib().call(_masked("hn_seg_loss_bwd_s2d", valid), ptr(logits), logits.stride(2), c, ptr(target), tf, ptr(cw), ign, n, h, w, topk, k,
+                       *_v(valid), ptr(ws), ptr(g), ptr(dz), ld(dz))
             ctx.slot.buf = dz
-            return None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None
         dl = torch.empty_like(logits)
-        lib().call("hn_seg_loss_bwd", ptr(logits), logits.stride(2), c, ptr(target), tf, ptr(cw), ign, n, hw, topk, k, ptr(ws), ptr(g),
-                   ptr(dl), dl.stride(2))
-        return dl, None, None, None, None, None, None
+        lib().call(_masked("hn_seg_loss_bwd", valid), ptr(logits), logits.stride(2), c, ptr(target), tf, ptr(cw), ign, n, hw, topk, k,
+                   *_v(valid), ptr(ws), ptr(g), ptr(dl), dl.stride(2))
+        return dl, None, None, None, None, None, None, None
 
 
-def seg_loss_hip(seg_nchw, target, class_weights, use_top_k, top_k_ratio, ignore_index=255, slot=None):
+def seg_loss_hip(seg_nchw, target, class_weights, use_top_k, top_k_ratio, ignore_index=255, slot=None, valid=None):
     """seg_nchw: the module's "seg" output (fp32, NCHW-shaped view of NHWC memory).  slot: GradSlot of the SegOutUp node that produced
-    exactly this tensor (HydraNet passes it when its own cal_loss consumes its own "seg" output)."""
+    exactly this tensor (HydraNet passes it when its own cal_loss consumes its own "seg" output).  valid: the seg row of the task masks
+    (see _task_valid_row): sum over the labelled images of their top-k sums / (N_valid k), each image's selection as without a mask."""
     logits = seg_nchw.permute(0, 2, 3, 1)
     if not logits.is_contiguous():
         logits, slot = logits.contiguous(), None
-    return SegLoss.apply(logits, target.contiguous(), class_weights, use_top_k, top_k_ratio, ignore_index, slot)
+    if valid is None:
+        return SegLoss.apply(logits, target.contiguous(), class_weights, use_top_k, top_k_ratio, ignore_index, slot)
+    return SegLoss.apply(logits, target.contiguous(), class_weights, use_top_k, top_k_ratio, ignore_index, slot, valid)
 
 
 class SegFocalLoss(torch.autograd.Function):
@@ -74,16 +103,17 @@ class SegFocalLoss(torch.autograd.Function):
     int64 or float32 class ids; mean over all pixels"""
 
     @staticmethod
-    def forward(ctx, logits, target, class_weights, gamma, alpha):
+    def forward(ctx, logits, target, class_weights, gamma, alpha, valid=None):
         n, h, w, c = logits.shape
+        ctx.valid = valid = None if valid is None else _task_valid_row(valid, n, logits.device)
         hw = h * w
         dev = logits.device
         tf = 1 if target.dtype == torch.float32 else 0
         assert target.dtype in (torch.float32, torch.int64) and target.is_contiguous()
         ws = torch.empty((lib().query("hn_seg_loss_blocks", n, hw),), device=dev, dtype=F32)
         out = torch.empty((1,), device=dev, dtype=F32)
-        lib().call("hn_seg_focal_fwd", ptr(logits), logits.stride(2), c, ptr(target), tf, ptr(class_weights), float(gamma), float(alpha), n, hw,
-                   ptr(ws), ptr(out))
+        lib().call(_masked("hn_seg_focal_fwd", valid), ptr(logits), logits.stride(2), c, ptr(target), tf, ptr(class_weights), float(gamma),
+                   float(alpha), n, hw, *_v(valid), ptr(ws), ptr(out))
         ctx.meta = (n, hw, c, tf, float(gamma), float(alpha))
         ctx.save_for_backward(logits, target, class_weights)
         return out.view(())
@@ -94,17 +124,20 @@ class SegFocalLoss(torch.autograd.Function):
         n, hw, c, tf, gamma, alpha = ctx.meta
         g = gout.contiguous().to(F32).view(1)
         dl = torch.empty_like(logits)
-        lib().call("hn_seg_focal_bwd", ptr(logits), logits.stride(2), c, ptr(target), tf, ptr(cw), gamma, alpha, n, hw, ptr(g), ptr(dl),
-                   dl.stride(2))
-        return dl, None, None, None, None
+        lib().call(_masked("hn_seg_focal_bwd", ctx.valid), ptr(logits), logits.stride(2), c, ptr(target), tf, ptr(cw), gamma, alpha, n, hw,
+                   *_v(ctx.valid), ptr(g), ptr(dl), dl.stride(2))
+        return dl, None, None, None, None, None
 
 
-def seg_focal_loss_hip(seg_nchw, target, class_weights, gamma=2.0, alpha=1.0):
-    """CrossEntropyLoss.forward with use_focal=True (gamma 2, alpha 1: the defaults model.py:119-124 leaves untouched)"""
+def seg_focal_loss_hip(seg_nchw, target, class_weights, gamma=2.0, alpha=1.0, valid=None):
+    """CrossEntropyLoss.forward with use_focal=True (gamma 2, alpha 1: the defaults model.py:119-124 leaves untouched).  valid: the seg
+    row of the task masks: the mean over the labelled images' pixels."""
     logits = seg_nchw.permute(0, 2, 3, 1)
     if not logits.is_contiguous():
         logits = logits.contiguous()
-    return SegFocalLoss.apply(logits, target.contiguous(), class_weights, gamma, alpha)
+    if valid is None:
+        return SegFocalLoss.apply(logits, target.contiguous(), class_weights, gamma, alpha)
+    return SegFocalLoss.apply(logits, target.contiguous(), class_weights, gamma, alpha, valid)
 
 
 class SegLovaszLoss(torch.autograd.Function):
@@ -113,9 +146,10 @@ class SegLovaszLoss(torch.autograd.Function):
     gradient live in the workspace the backward reads (hn_lovasz.hip)."""
 
     @staticmethod
-    def forward(ctx, logits, target, ignore_index, slot=None):
+    def forward(ctx, logits, target, ignore_index, slot=None, valid=None):
         """slot: GradSlot of the producing SegOutUp node, as for SegLoss (hn_seg_lovasz_bwd_s2d hands the gradient over in its operand form)"""
         n, h, w, c = logits.shape
+        ctx.valid = valid = None if valid is None else _task_valid_row(valid, n, logits.device)
         hw = h * w
         ctx.slot = slot if (slot is not None and h % 2 == 0 and w % 2 == 0) else None
         ctx.hw_dims = (h, w)
@@ -124,7 +158,8 @@ class SegLovaszLoss(torch.autograd.Function):
         out = torch.empty((1,), device=dev, dtype=F32)
         tf = 1 if target.dtype == torch.float32 else 0
         assert target.dtype in (torch.float32, torch.int64) and target.is_contiguous()
-        lib().call("hn_seg_lovasz_fwd", ptr(logits), logits.stride(2), c, ptr(target), tf, ignore_index, n, hw, ptr(ws), ptr(out))
+        lib().call(_masked("hn_seg_lovasz_fwd", valid), ptr(logits), logits.stride(2), c, ptr(target), tf, ignore_index, n, hw, *_v(valid),
+                   ptr(ws), ptr(out))
         ctx.meta = (n, hw, c, tf, ignore_index)
         ctx.save_for_backward(logits, target, ws)
         return out.view(())
@@ -133,25 +168,31 @@ class SegLovaszLoss(torch.autograd.Function):
     def backward(ctx, gout):
         logits, target, ws = ctx.saved_tensors
         n, hw, c, tf, ign = ctx.meta
+        valid = ctx.valid
         g = gout.contiguous().to(F32).view(1)
         if ctx.slot is not None and ctx.slot.buf is None:
             h, w = ctx.hw_dims
             dz = new_act(n, h // 2, w // 2, pad8(4 * c), logits.device)
-            lib().call("hn_seg_lovasz_bwd_s2d", ptr(logits), logits.stride(2), c, ptr(target), tf, ign, n, h, w, ptr(ws), ptr(g), ptr(dz), ld(dz))
+            lib().call(_masked("hn_seg_lovasz_bwd_s2d", valid), ptr(logits), logits.stride(2), c, ptr(target), tf, ign, n, h, w, *_v(valid),
+                       ptr(ws), ptr(g), ptr(dz), ld(dz))
             ctx.slot.buf = dz
-            return None, None, None, None
+            return None, None, None, None, None
         dl = torch.empty_like(logits)
-        lib().call("hn_seg_lovasz_bwd", ptr(logits), logits.stride(2), c, ptr(target), tf, ign, n, hw, ptr(ws), ptr(g), ptr(dl), dl.stride(2))
-        return dl, None, None, None
+        lib().call(_masked("hn_seg_lovasz_bwd", valid), ptr(logits), logits.stride(2), c, ptr(target), tf, ign, n, hw, *_v(valid), ptr(ws),
+                   ptr(g), ptr(dl), dl.stride(2))
+        return dl, None, None, None, None
 
 
-def seg_lovasz_loss_hip(seg_nchw, target, ignore_index=255, slot=None):
+def seg_lovasz_loss_hip(seg_nchw, target, ignore_index=255, slot=None, valid=None):
     """model.py cal_loss with use_lovasz: lovasz_softmax(F.softmax(seg, 1), gt_seg.long(), ignore=255).  seg_nchw: the module's "seg"
-    output (fp32, NCHW-shaped view of NHWC memory); slot as for seg_loss_hip."""
+    output (fp32, NCHW-shaped view of NHWC memory); slot as for seg_loss_hip.  valid: the seg row of the task masks: an unlabelled
+    image's pixels are dropped like ignored pixels (class presence, ranks and the tie order come from the remaining ones)."""
     logits = seg_nchw.permute(0, 2, 3, 1)
     if not logits.is_contiguous():
         logits, slot = logits.contiguous(), None
-    return SegLovaszLoss.apply(logits, target.contiguous(), ignore_index, slot)
+    if valid is None:
+        return SegLovaszLoss.apply(logits, target.contiguous(), ignore_index, slot)
+    return SegLovaszLoss.apply(logits, target.contiguous(), ignore_index, slot, valid)
 
 
 def argmax_channels(seg_nchw):
@@ -171,10 +212,11 @@ class DetLoss(torch.autograd.Function):
     """returns a 2-vector (classification loss, regression loss), both batch means like FocalLoss.forward."""
 
     @staticmethod
-    def forward(ctx, cls, reg, anchors, ann, given=None):
+    def forward(ctx, cls, reg, anchors, ann, given=None, valid=None):
         n, a, k = cls.shape
         mx = ann.shape[1]
         dev = cls.device
+        ctx.valid = valid = None if valid is None else _task_valid_row(valid, n, dev)
         cls, reg, ann = cls.contiguous(), reg.contiguous(), ann.contiguous().float()
         anc = anchors.reshape(-1, 4).contiguous()
         blocks = lib().query("hn_det_loss_blocks", a)
@@ -183,11 +225,12 @@ class DetLoss(torch.autograd.Function):
         out = torch.empty((2,), device=dev, dtype=F32)
         if given is None:
             assign = torch.empty((n, a), device=dev, dtype=torch.int16)
-            lib().call("hn_det_loss_fwd", ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, ptr(assign), ptr(part), ptr(npos), ptr(out))
+            lib().call(_masked("hn_det_loss_fwd", valid), ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, *_v(valid), ptr(assign), ptr(part),
+                       ptr(npos), ptr(out))
         else:
             assign = _given_assign(given, n, a, dev)
-            lib().call("hn_det_loss_fwd_assigned", ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, ptr(assign), ptr(part), ptr(npos),
-                       ptr(out))
+            lib().call(_masked("hn_det_loss_fwd_assigned", valid), ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, *_v(valid), ptr(assign),
+                       ptr(part), ptr(npos), ptr(out))
         ctx.save_for_backward(cls, reg, anc, ann, assign, npos)
         # the two losses leave as two outputs (slicing a 2-vector OUTSIDE the node cost two SliceBackward nodes -- fill + copy each -- and
         # an add per step: seven 5 us launches)
@@ -204,9 +247,9 @@ class DetLoss(torch.autograd.Function):
         else:
             z = zeros((1,), cls.device)
             g = torch.cat([(gcls if gcls is not None else z).reshape(1).to(F32), (greg if greg is not None else z).reshape(1).to(F32)])
-        lib().call("hn_det_loss_bwd", ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, ann.shape[1], ptr(assign), ptr(npos), ptr(g), ptr(dcls),
-                   ptr(dreg))
-        return dcls, dreg, None, None, None
+        lib().call(_masked("hn_det_loss_bwd", ctx.valid), ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, ann.shape[1], *_v(ctx.valid),
+                   ptr(assign), ptr(npos), ptr(g), ptr(dcls), ptr(dreg))
+        return dcls, dreg, None, None, None, None
 
 
 def _given_assign(assign, n, a, dev):
@@ -216,12 +259,13 @@ def _given_assign(assign, n, a, dev):
     return assign.contiguous()
 
 
-def det_loss_hip(classification, regression, anchors, annotations, assign=None):
+def det_loss_hip(classification, regression, anchors, annotations, assign=None, valid=None):
     """assign: None = the reference's max-IoU assignment, computed inside the forward launch; an int16 [N, A] tensor (det_atss_assign's)
-    is read instead (hn_det_loss_fwd_assigned)."""
-    if assign is None:
+    is read instead (hn_det_loss_fwd_assigned).  valid: the det row of the task masks: an unlabelled image's anchors are all ignored
+    (npos 0; -2 throughout its row of a computed assignment) and the batch means are taken over the labelled images."""
+    if assign is None and valid is None:
         return DetLoss.apply(classification, regression, anchors, annotations)
-    return DetLoss.apply(classification, regression, anchors, annotations, assign)
+    return DetLoss.apply(classification, regression, anchors, annotations, assign, valid)
 
 
 def det_atss_assign(anchors, level_sizes, annotations, topk=9, anchors_per_location=9):
@@ -271,10 +315,11 @@ class DetIoULoss(torch.autograd.Function):
     all batch means; the third is a diagnostic and not differentiable."""
 
     @staticmethod
-    def forward(ctx, cls, reg, anchors, ann, kind, given=None):
+    def forward(ctx, cls, reg, anchors, ann, kind, given=None, valid=None):
         n, a, k = cls.shape
         mx = ann.shape[1]
         dev = cls.device
+        ctx.valid = valid = None if valid is None else _task_valid_row(valid, n, dev)
         cls, reg, ann = cls.contiguous(), reg.contiguous(), ann.contiguous().float()
         anc = anchors.reshape(-1, 4).contiguous()
         blocks = lib().query("hn_det_loss_blocks", a)
@@ -283,12 +328,12 @@ class DetIoULoss(torch.autograd.Function):
         out = torch.empty((3,), device=dev, dtype=F32)
         if given is None:
             assign = torch.empty((n, a), device=dev, dtype=torch.int16)
-            lib().call("hn_det_loss_iou_fwd", ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, kind, ptr(assign), ptr(part), ptr(npos),
-                       ptr(out))
+            lib().call(_masked("hn_det_loss_iou_fwd", valid), ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, kind, *_v(valid), ptr(assign),
+                       ptr(part), ptr(npos), ptr(out))
         else:
             assign = _given_assign(given, n, a, dev)
-            lib().call("hn_det_loss_iou_fwd_assigned", ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, kind, ptr(assign), ptr(part),
-                       ptr(npos), ptr(out))
+            lib().call(_masked("hn_det_loss_iou_fwd_assigned", valid), ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, kind, *_v(valid),
+                       ptr(assign), ptr(part), ptr(npos), ptr(out))
         ctx.kind = kind
         ctx.save_for_backward(cls, reg, anc, ann, assign, npos)
         pos_iou = out[2:3]
@@ -307,12 +352,12 @@ class DetIoULoss(torch.autograd.Function):
         else:
             z = zeros((1,), cls.device)
             g = torch.cat([(gcls if gcls is not None else z).reshape(1).to(F32), (greg if greg is not None else z).reshape(1).to(F32)])
-        lib().call("hn_det_loss_iou_bwd", ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, ann.shape[1], ctx.kind, ptr(assign), ptr(npos), ptr(g),
-                   ptr(dcls), ptr(dreg))
-        return dcls, dreg, None, None, None, None
+        lib().call(_masked("hn_det_loss_iou_bwd", ctx.valid), ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, ann.shape[1], ctx.kind,
+                   *_v(ctx.valid), ptr(assign), ptr(npos), ptr(g), ptr(dcls), ptr(dreg))
+        return dcls, dreg, None, None, None, None, None
 
 
-def det_iou_loss_hip(classification, regression, anchors, annotations, kind, assign=None):
+def det_iou_loss_hip(classification, regression, anchors, annotations, kind, assign=None, valid=None):
     """The detection loss with its regression term replaced by an IoU-family loss; kind = "giou" | "diou" | "ciou".  Returns
     (classification loss [1], regression loss [1], pos_iou [1]).  Anchor assignment (IoU >= 0.5 positive, < 0.4 background, between
     ignored, first maximum wins, an image without boxes all background) and the focal classification loss are det_loss_hip's, bit for
@@ -334,12 +379,13 @@ def det_iou_loss_hip(classification, regression, anchors, annotations, kind, ass
     Per image the regression loss is sum_pos loss / npos (0 when npos = 0) and the output the mean over the N images: the smooth-L1
     term's reduction without its x4.  pos_iou is the positives' plain iou reduced the same way (non-differentiable).
 
-    assign: None = the assignment above; an int16 [N, A] tensor (det_atss_assign's) is read instead (hn_det_loss_iou_fwd_assigned)."""
+    assign: None = the assignment above; an int16 [N, A] tensor (det_atss_assign's) is read instead (hn_det_loss_iou_fwd_assigned).
+    valid: the det row of the task masks, as for det_loss_hip; pos_iou is averaged over the labelled images as well."""
     if kind not in DET_IOU_KINDS:
         raise ValueError(f"kind must be one of {sorted(DET_IOU_KINDS)}, got {kind!r}")
-    if assign is None:
+    if assign is None and valid is None:
         return DetIoULoss.apply(classification, regression, anchors, annotations, DET_IOU_KINDS[kind])
-    return DetIoULoss.apply(classification, regression, anchors, annotations, DET_IOU_KINDS[kind], assign)
+    return DetIoULoss.apply(classification, regression, anchors, annotations, DET_IOU_KINDS[kind], assign, valid)
 
 
 
@@ -350,16 +396,26 @@ def det_iou_loss_hip(classification, regression, anchors, annotations, kind, ass
 # --------------------------------------------------------------------------------------------------------------
 class LaneClsLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, cls_targets, cls_preds, negative_ratio, alpha):
+    def forward(ctx, cls_targets, cls_preds, negative_ratio, alpha, valid=None, rows=None):
         tgt = cls_targets.reshape(-1, 2).float().contiguous()
         z = cls_preds.reshape(-1, 2).float().contiguous()
         m = z.shape[0]
         dev = z.device
+        ctx.valid = ctx.rows = None
+        if valid is not None:
+            rows = int(rows)
+            if rows < 1 or m % rows:
+                raise ValueError(f"rows_per_image = {rows} does not divide the {m} lane rows")
+            ctx.valid, ctx.rows = _task_valid_row(valid, m // rows, dev), rows
         lsm = torch.empty((m, 2), device=dev, dtype=F32)
         pmask = torch.empty((m,), device=dev, dtype=torch.uint8)
         out = torch.empty((2,), device=dev, dtype=F32)
         aux = torch.empty((4,), device=dev, dtype=F32)
-        lib().call("hn_lane_cls_loss_fwd", ptr(z), ptr(tgt), m, float(negative_ratio), float(alpha), ptr(lsm), ptr(pmask), ptr(out), ptr(aux))
+        if valid is None:
+            lib().call("hn_lane_cls_loss_fwd", ptr(z), ptr(tgt), m, float(negative_ratio), float(alpha), ptr(lsm), ptr(pmask), ptr(out), ptr(aux))
+        else:
+            lib().call("hn_lane_cls_loss_fwd_masked", ptr(z), ptr(tgt), m, rows, ptr(valid), float(negative_ratio), float(alpha), ptr(lsm),
+                       ptr(pmask), ptr(out), ptr(aux))
         ctx.alpha, ctx.shape = float(alpha), cls_preds.shape
         ctx.save_for_backward(lsm, pmask, aux)
         ctx.mark_non_differentiable(pmask, aux)
@@ -373,8 +429,12 @@ class LaneClsLoss(torch.autograd.Function):
         dz = torch.empty((m, 2), device=lsm.device, dtype=F32)
         gp = gpos.reshape(1).to(F32) if gpos is not None else zeros((1,), lsm.device)
         gn = gneg.reshape(1).to(F32) if gneg is not None else zeros((1,), lsm.device)
-        lib().call("hn_lane_cls_loss_bwd", ptr(lsm), ptr(pmask), ptr(aux), ptr(gp), ptr(gn), ctx.alpha, m, ptr(dz))
-        return None, dz.view(ctx.shape), None, None
+        if ctx.valid is None:
+            lib().call("hn_lane_cls_loss_bwd", ptr(lsm), ptr(pmask), ptr(aux), ptr(gp), ptr(gn), ctx.alpha, m, ptr(dz))
+        else:
+            lib().call("hn_lane_cls_loss_bwd_masked", ptr(lsm), ptr(pmask), ptr(aux), ptr(gp), ptr(gn), ctx.alpha, m, ctx.rows, ptr(ctx.valid),
+                       ptr(dz))
+        return None, dz.view(ctx.shape), None, None, None, None
 
 
 class LaneLocLoss(torch.autograd.Function):
@@ -407,15 +467,34 @@ class LaneLocLoss(torch.autograd.Function):
         return None, None, None, dp.view(shape), None, None
 
 
-def lane_cls_loss_hip(cls_targets, cls_preds, negative_ratio=15, alpha=10.0):
+def _lane_rows(valid, rows_per_image, m):
+    """rows per image of a masked lane loss: as given, else the row count over the mask's images"""
+    if rows_per_image is not None:
+        return int(rows_per_image)
+    n = valid.shape[0] if isinstance(valid, torch.Tensor) and valid.dim() == 1 and valid.shape[0] > 0 else 1
+    return m // n if m % n == 0 else 0
+
+
+def lane_cls_loss_hip(cls_targets, cls_preds, negative_ratio=15, alpha=10.0, valid=None, rows_per_image=None):
     """cal_loss_cls (lanedetect_loss.py:18-54): returns (pos, neg, pmask, positive_num) like the reference; pmask / positive_num are
-    device-side handles (byte mask, aux vector) consumed by lane_loc_loss_hip."""
-    pos, neg, pmask, aux = LaneClsLoss.apply(cls_targets, cls_preds, negative_ratio, alpha)
-    return pos, neg, pmask, aux
+    device-side handles (byte mask, aux vector) consumed by lane_loc_loss_hip.  valid: the lane row of the task masks, with
+    rows_per_image anchors rows per image (default: the row count over the mask's length): the rows of an unlabelled image are neither
+    positive nor negative -- out of #pos, #neg, the rank neg_num, the select and both sums."""
+    if valid is None:
+        return LaneClsLoss.apply(cls_targets, cls_preds, negative_ratio, alpha)
+    return LaneClsLoss.apply(cls_targets, cls_preds, negative_ratio, alpha, valid, _lane_rows(valid, rows_per_image, cls_preds.numel() // 2))
 
 
-def lane_loc_loss_hip(pmask, positive_num, loc_targets, loc_preds, alpha=10.0, points_per_line=160):
-    """cal_loss_regress (lanedetect_loss.py:57-78) incl. its hard-coded points_per_line = 160 default (x10 weights on columns 160/161)."""
+def lane_loc_loss_hip(pmask, positive_num, loc_targets, loc_preds, alpha=10.0, points_per_line=160, valid=None, rows_per_image=None):
+    """cal_loss_regress (lanedetect_loss.py:57-78) incl. its hard-coded points_per_line = 160 default (x10 weights on columns 160/161).
+    valid / rows_per_image: as handed to lane_cls_loss_hip; the masked pmask / positive_num already carry the mask (an unlabelled
+    image has no positive row, and only positive rows enter the loss and the gradient), so they are checked and the launches are the same."""
+    if valid is not None:
+        m = loc_preds.numel() // loc_preds.shape[-1]
+        rows = _lane_rows(valid, rows_per_image, m)
+        if rows < 1 or m % rows:
+            raise ValueError(f"rows_per_image = {rows} does not divide the {m} lane rows")
+        _task_valid_row(valid, m // rows, loc_preds.device)
     return LaneLocLoss.apply(pmask, positive_num, loc_targets, loc_preds, points_per_line, alpha)
 
 

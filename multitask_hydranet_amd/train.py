@@ -19,6 +19,7 @@ import os
 import sys
 from typing import Dict, Iterable, Optional
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -363,6 +364,15 @@ class HydraTrainer:
             batch_data["gt_seg"] = batch_data["gt_seg"].to(self.device).float()
         if self.train_detect:
             batch_data["gt_det"] = batch_data["gt_det"].to(self.device).float()
+        tv = batch_data.get("task_valid")
+        if tv is not None and "task_valid_host" not in batch_data and not (isinstance(tv, torch.Tensor) and tv.is_cuda):
+            # per-image task masks (dataloader.allow_missing_labels): the device copy feeds the losses (and rides into a captured
+            # step's static set like every device tensor of the batch); the host copy indexes valid()'s metrics without a synchronisation.
+            # (A mask that arrives on the device already is used as it is: copying it back would synchronise, so valid() then scores
+            # every image.)
+            host = torch.as_tensor(tv).to(torch.uint8).contiguous()
+            batch_data["task_valid_host"] = host
+            batch_data["task_valid"] = host.to(self.device, non_blocking=True)
         return batch_data
 
     def _augment(self, batch_data: dict) -> dict:
@@ -451,8 +461,9 @@ class HydraTrainer:
         if self.reducer is not None and not in_graph:
             self.reducer.reduce_now()
         if self.hydranet.check_finite:
+            masked = "task_valid" in static             # (a task without a labelled image in the batch has loss 0: no divergence)
             for name, v in loss_dict.items():
-                self.hydranet._guard(v, "cal %s diverge!" % name, allow_zero=name.startswith("loss_det"))
+                self.hydranet._guard(v, "cal %s diverge!" % name, allow_zero=masked or name.startswith("loss_det"))
         if not clone:
             return loss_dict
         return {k: v.detach().clone() for k, v in loss_dict.items()}      # the static tensors are rewritten by the next replay
@@ -594,15 +605,26 @@ class HydraTrainer:
                 if self.rank == 0 and iter_idx % self.print_interval == 0:
                     self.print_loss_info(loss_dict, epoch, iter_idx, mode="valid")
             shapes = batch_data.get("src_image_shape") or [{"width": net_w, "height": net_h}] * n
+            # per-image task masks: every task is scored on its labelled images only, picked with the HOST copy of the mask (no sync)
+            tvh = batch_data.get("task_valid_host")
+            labelled = (lambda row: [True] * n) if tvh is None else (lambda row: [bool(v) for v in tvh[row].tolist()])
             if self.train_seg and "gt_seg" in batch_data:
                 from . import ops as K
-                self.metric_evaluator_iou.update(K.argmax_channels(outputs["seg"]), batch_data["gt_seg"])
+                pred_seg, gt_seg = K.argmax_channels(outputs["seg"]), batch_data["gt_seg"]
+                if tvh is not None:
+                    keep = torch.tensor([i for i, on in enumerate(labelled(0)) if on], dtype=torch.int64).to(self.device)
+                    pred_seg, gt_seg = pred_seg.index_select(0, keep), gt_seg.index_select(0, keep)
+                if pred_seg.shape[0]:
+                    self.metric_evaluator_iou.update(pred_seg, gt_seg)
             if self.train_detect:
                 d = outputs["detection"]
                 preds = net.detectheader.decode(inputs, d["regression"], d["classification"], d["anchors"], conf_thres=det_conf_thres,
                                                 iou_thres=det_iou_thres)
                 metas = [[net_w, net_h, sh["width"], sh["height"], 0, 0] for sh in shapes]
                 preds = net.detectheader.invert_affine(metas, preds)                                       # train.py:334-336
+                if tvh is not None:                  # an image without a box label leaves no record; the others keep their image ids
+                    none = dict(rois=np.zeros((0, 4), np.float32), class_ids=np.zeros((0,), np.int64), scores=np.zeros((0,), np.float32))
+                    preds = [pr if on else none for pr, on in zip(preds, labelled(1))]
                 first_id = iter_idx * self.cfgs["train"].get("batch_size_valid", n) + 1
                 detect_result += detections_to_coco(preds, first_id)
                 if det_eval is not None:
@@ -616,7 +638,7 @@ class HydraTrainer:
                 for i, (ln, sh) in enumerate(zip(lanes, shapes)):
                     pj = net.laneheader.scale_to_org(ln, net_w, net_h, sh["width"], sh["height"])
                     lane_result.append(dict(pr_result={**pj, **dict(Shape=sh)}))
-                    if gts is not None:
+                    if gts is not None and labelled(2)[i]:
                         pairs.append(dict(pr_result=lane_result[-1]["pr_result"], gt_result={**gts[i], **dict(Shape=sh)}))
                 if pairs:
                     lane_metric(output=pairs)                                                                      # train.py:397
