@@ -541,6 +541,20 @@ int hn_det_loss_fwd_assigned(const float* cls, const float* reg, const float* an
                              const void* assign, float* part, float* npos, float* out, hipStream_t stream);
 int hn_det_loss_iou_fwd_assigned(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
                                  int kind, const void* assign, float* part, float* npos, float* out, hipStream_t stream);
+/* Detection loss with a quality classification term (detection.loss_cls_type = qfl | vfl; hn_det_quality.hip) and an IoU-family
+ * regression term (kind 1 giou, 2 diou, 3 ciou).  The target of a positive anchor's class is the IoU q of its decoded prediction with its
+ * annotation (the iou of hn_det_loss_iou_fwd, a constant in the backward), every other target is 0; with p^ = clamp(p, 1e-4, 1 - 1e-4),
+ * BCE = -(y ln p^ + (1 - y) ln(1 - p^)): cls_kind 1 (qfl) l = (y - p^)^2 BCE; cls_kind 2 (vfl) l = y BCE for y > 0 and
+ * 0.75 p^2 (-ln(1 - p^)) for y = 0; reduced like the focal term.  One pair for every variant: valid = the det row of the task masks or
+ * NULL (every image labelled); assign_given = 0: the max-IoU assignment is computed and written to assign, 1: assign is read (values
+ * outside -2 .. Mx - 1 count as ignored) and not written.  Regression loss, out[2], npos, dreg and part[..][1..3] are
+ * hn_det_loss_iou_fwd / _bwd's, bit for bit.  Buffers as there; K <= 32.  Two launches forward, one backward. */
+int hn_det_loss_quality_fwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx, int kind,
+                            int cls_kind, const unsigned char* valid, int assign_given, void* assign, float* part, float* npos, float* out,
+                            hipStream_t stream);
+int hn_det_loss_quality_bwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx, int kind,
+                            int cls_kind, const unsigned char* valid, const void* assign, const float* npos, const float* gout, float* dcls,
+                            float* dreg, hipStream_t stream);
 /* torch.argmax(seg, dim=1) of deploy mode (model/model.py:197): fp32 NHWC logits -> int64 class ids, first maximum wins. */
 /* Lane losses (head_lane/lanedetect_loss.py:18-78).  cls: logits / one-hot target fp32 [M][2]; out[0] = positive term, out[1] = OHEM
  * negative term (NEGATIVE_RATIO 15, ALPHA 10: the k-th smallest background log-prob is found by a radix select, not a sort);

@@ -477,7 +477,9 @@ __global__ __launch_bounds__(256) void det_loss_bwd_kernel(const float* cls, con
     const int nlab = hn_count_valid(valid, N);                         // (lab implies nlab >= 1)
     const float fc = lab ? gout[0] / (nlab * fmaxf(p_n, 1.f)) : 0.f;
     const float fr = lab && p_n > 0.f ? gout[1] / (nlab * 4.f * p_n) : 0.f;
-    const int as = a < A && lab ? assign[(long)n * A + a] : -2;       // a given assignment keeps its values for an unlabelled image
+    // (a given assignment keeps its values for an unlabelled image; a stray value counts as ignored here as in the forward, so it never
+    // indexes the annotations)
+    const int as = a < A && lab ? det_given_assign(assign[(long)n * A + a], Mx) : -2;
     const float* an = ann + (long)n * Mx * 5;
     if (a < A)                                                         // (K odd or not: stride-K rows, each thread only touches its own)
         det_focal_grad_row(tile + threadIdx.x * K, K, as, as >= 0 ? (int)an[as * 5 + 4] : -1, fc);

@@ -144,6 +144,18 @@ class HydraNet(nn.Module):
                 self.loss_detect = functools.partial(K.det_iou_loss_hip, kind=self.loss_reg_type)
             else:
                 raise ValueError("detection.loss_reg_type must be one of 'smooth_l1', 'giou', 'diou', 'ciou', got %r" % (self.loss_reg_type,))
+            # detection.loss_cls_type: the classification term.  focal (or no key) is the reference's hard 0 / 1 target; qfl / vfl make
+            # the positive class's target the IoU of the decoded box with its annotation, so the score NMS and mAP rank by says how
+            # well the box is placed (ops/losses.py det_iou_loss_hip, cls_kind).  They take that IoU from the IoU regression kernel, so
+            # they need an IoU loss_reg_type.  Nothing changes at inference.  HIP only.
+            self.loss_cls_type = cfgs["detection"].get("loss_cls_type", "focal")
+            if self.loss_cls_type not in K.DET_CLS_KINDS:
+                raise ValueError("detection.loss_cls_type must be one of 'focal', 'qfl', 'vfl', got %r" % (self.loss_cls_type,))
+            if self.loss_cls_type != "focal":
+                if self.loss_reg_type not in K.DET_IOU_KINDS:
+                    raise ValueError("detection.loss_cls_type %r needs detection.loss_reg_type to be one of 'giou', 'diou', 'ciou' (the IoU "
+                                     "kernel decodes the box whose quality is the target), got %r" % (self.loss_cls_type, self.loss_reg_type))
+                self.loss_detect = functools.partial(K.det_iou_loss_hip, kind=self.loss_reg_type, cls_kind=self.loss_cls_type)
             # detection.assigner: which anchors are positive.  max_iou (or no key) is the reference's fixed rule (IoU >= 0.5 positive, < 0.4
             # background, between ignored), computed inside the loss forward; atss picks per box the atss_topk nearest locations of every
             # level and thresholds their IoUs at mean + std (ops/losses.py det_atss_assign).  Works with every loss_reg_type.  HIP only.

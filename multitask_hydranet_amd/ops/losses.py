@@ -357,7 +357,52 @@ class DetIoULoss(torch.autograd.Function):
         return dcls, dreg, None, None, None, None, None
 
 
-def det_iou_loss_hip(classification, regression, anchors, annotations, kind, assign=None, valid=None):
+DET_CLS_KINDS = {"focal": 0, "qfl": 1, "vfl": 2}
+
+
+class DetQualityLoss(torch.autograd.Function):
+    """DetIoULoss with a quality classification term (hn_det_quality.hip; cls_kind 1 = qfl, 2 = vfl): the same three outputs, the same
+    launch count.  One pair of entry points takes the mask and the given assignment as (nullable) arguments."""
+
+    @staticmethod
+    def forward(ctx, cls, reg, anchors, ann, kind, cls_kind, given=None, valid=None):
+        n, a, k = cls.shape
+        mx = ann.shape[1]
+        dev = cls.device
+        ctx.valid = valid = None if valid is None else _task_valid_row(valid, n, dev)
+        cls, reg, ann = cls.contiguous(), reg.contiguous(), ann.contiguous().float()
+        anc = anchors.reshape(-1, 4).contiguous()
+        blocks = lib().query("hn_det_loss_blocks", a)
+        part = torch.empty((n, blocks, 4), device=dev, dtype=F32)
+        npos = torch.empty((n,), device=dev, dtype=F32)
+        out = torch.empty((3,), device=dev, dtype=F32)
+        assign = torch.empty((n, a), device=dev, dtype=torch.int16) if given is None else _given_assign(given, n, a, dev)
+        lib().call("hn_det_loss_quality_fwd", ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, kind, cls_kind,
+                   ptr(valid), 0 if given is None else 1, ptr(assign), ptr(part), ptr(npos), ptr(out))
+        ctx.kind, ctx.cls_kind = kind, cls_kind
+        ctx.save_for_backward(cls, reg, anc, ann, assign, npos)
+        pos_iou = out[2:3]
+        ctx.mark_non_differentiable(pos_iou)
+        ctx.set_materialize_grads(False)        # (no zero-filled "gradient" of the diagnostic: a fill launch per step)
+        return out[0:1], out[1:2], pos_iou
+
+    @staticmethod
+    def backward(ctx, gcls, greg, _giou):
+        cls, reg, anc, ann, assign, npos = ctx.saved_tensors
+        n, a, k = cls.shape
+        dcls, dreg = torch.empty_like(cls), torch.empty_like(reg)
+        if (gcls is not None and greg is not None and gcls.dtype == F32 and greg.dtype == F32
+                and greg.data_ptr() == gcls.data_ptr() + 4):       # neighbours in WeightedLossSum.backward's gradient vector: used in place
+            g = gcls
+        else:
+            z = zeros((1,), cls.device)
+            g = torch.cat([(gcls if gcls is not None else z).reshape(1).to(F32), (greg if greg is not None else z).reshape(1).to(F32)])
+        lib().call("hn_det_loss_quality_bwd", ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, ann.shape[1], ctx.kind, ctx.cls_kind,
+                   ptr(ctx.valid), ptr(assign), ptr(npos), ptr(g), ptr(dcls), ptr(dreg))
+        return dcls, dreg, None, None, None, None, None, None
+
+
+def det_iou_loss_hip(classification, regression, anchors, annotations, kind, assign=None, valid=None, cls_kind="focal"):
     """The detection loss with its regression term replaced by an IoU-family loss; kind = "giou" | "diou" | "ciou".  Returns
     (classification loss [1], regression loss [1], pos_iou [1]).  Anchor assignment (IoU >= 0.5 positive, < 0.4 background, between
     ignored, first maximum wins, an image without boxes all background) and the focal classification loss are det_loss_hip's, bit for
@@ -380,9 +425,32 @@ def det_iou_loss_hip(classification, regression, anchors, annotations, kind, ass
     term's reduction without its x4.  pos_iou is the positives' plain iou reduced the same way (non-differentiable).
 
     assign: None = the assignment above; an int16 [N, A] tensor (det_atss_assign's) is read instead (hn_det_loss_iou_fwd_assigned).
-    valid: the det row of the task masks, as for det_loss_hip; pos_iou is averaged over the labelled images as well."""
+    valid: the det row of the task masks, as for det_loss_hip; pos_iou is averaged over the labelled images as well.
+
+    cls_kind: "focal" (the default) makes exactly the calls above.  "qfl" (quality focal loss, Li et al. 2020) and "vfl" (varifocal
+    loss, Zhang et al. 2021) replace the classification term by one whose target is the quality of the box (hn_det_quality.hip); the
+    assignment, the regression loss, pos_iou and the regression gradient stay the focal call's, bit for bit.  For a counted anchor
+    (assignment not -2: ignored anchors and every anchor of an unlabelled image contribute nothing and get gradient 0) and class k:
+
+      quality         q = the `iou` above of a positive anchor: the deploy decode with the exp clip, the target sides clamped to at least
+                      1, eps = 1e-7.  q is a constant in the backward: the classification term sends no gradient to the regression.
+      target          y = q when the anchor is positive and k is its annotation's class, else y = 0; a class id outside 0 .. K - 1
+                      matches no k
+      probability     p^ = clamp(p, 1e-4, 1 - 1e-4) as in the focal loss; the gradient w.r.t. p is 0 unless 1e-4 < p < 1 - 1e-4
+      BCE(p^, y)      -(y ln p^ + (1 - y) ln(1 - p^))
+      qfl (beta 2)    l = (y - p^)^2 BCE(p^, y);  dl/dp = 2 (p - y) BCE + (p - y)^2 ((1 - y) / (1 - p) - y / p)
+      vfl, y > 0      l = y BCE(p^, y);  dl/dp = y ((1 - y) / (1 - p) - y / p)
+      vfl, y = 0      (alpha 0.75, gamma 2; includes a positive whose q is exactly 0)  l = 0.75 p^^2 (-ln(1 - p^));
+                      dl/dp = 0.75 (-2 p ln(1 - p) + p^2 / (1 - p))
+
+    Per image the sum of l over counted anchors and classes is divided by max(npos, 1); the output is the mean over the images (over
+    the labelled images under a mask, 0 without any): the focal term's reduction.  beta, alpha and gamma are fixed."""
     if kind not in DET_IOU_KINDS:
         raise ValueError(f"kind must be one of {sorted(DET_IOU_KINDS)}, got {kind!r}")
+    if cls_kind not in DET_CLS_KINDS:
+        raise ValueError(f"cls_kind must be one of {sorted(DET_CLS_KINDS)}, got {cls_kind!r}")
+    if cls_kind != "focal":
+        return DetQualityLoss.apply(classification, regression, anchors, annotations, DET_IOU_KINDS[kind], DET_CLS_KINDS[cls_kind], assign, valid)
     if assign is None and valid is None:
         return DetIoULoss.apply(classification, regression, anchors, annotations, DET_IOU_KINDS[kind])
     return DetIoULoss.apply(classification, regression, anchors, annotations, DET_IOU_KINDS[kind], assign, valid)
