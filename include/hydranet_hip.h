@@ -471,7 +471,7 @@ int hn_eltwise(int op, const void* a, int lda, const void* b, int ldb, void* out
 int hn_add_strided2(void* dx, int ldx, const void* dxs, int lds, int N, int Ho, int Wo, int C, hipStream_t stream);
 int hn_cast_f32_to_bf16_pad(const float* src, int lds, void* dst, int ldo, long M, int C, hipStream_t stream);
 
-/* ---- losses (hn_loss.hip) --------------------------------------------------------------------------------------------------- */
+/* ---- losses (hn_loss.hip; the detection losses: hn_det_loss.hip) ------------------------------------------------------------- */
 
 /* Weighted cross entropy with ignore_index and optional top-k hardest pixels per image (CrossEntropyLoss.forward, use_focal=False,
  * head_seg/segmentation_loss.py:48-65).  logits: fp32 NHWC [N*HW][C] (row stride ldl); target: int64 or float32 class ids [N*HW];
@@ -517,7 +517,7 @@ int hn_det_loss_fwd(const float* cls, const float* reg, const float* anchors, co
                     float* part, float* npos, float* out, hipStream_t stream);
 int hn_det_loss_bwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
                     const void* assign, const float* npos, const float* gout, float* dcls, float* dreg, hipStream_t stream);
-/* The same loss with an IoU-family regression term (detection.loss_reg_type; hn_det_iou.hip): kind 1 GIoU, 2 DIoU, 3 CIoU between the
+/* The same loss with an IoU-family regression term (detection.loss_reg_type; hn_det_loss.hip): kind 1 GIoU, 2 DIoU, 3 CIoU between the
  * deploy-mode decode of a positive anchor's (dy, dx, dh, dw) (exp clipped at log(1000/16)) and its annotation (sides clamped to >= 1),
  * per image the mean over its positives, then the batch mean.  Assignment and the classification loss are hn_det_loss_fwd's, bit for bit.
  * out[0] / out[1] = classification / regression loss, out[2] = mean IoU of the positives (reduced like the loss).  assign: int16 [N][A];
@@ -541,7 +541,7 @@ int hn_det_loss_fwd_assigned(const float* cls, const float* reg, const float* an
                              const void* assign, float* part, float* npos, float* out, hipStream_t stream);
 int hn_det_loss_iou_fwd_assigned(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
                                  int kind, const void* assign, float* part, float* npos, float* out, hipStream_t stream);
-/* Detection loss with a quality classification term (detection.loss_cls_type = qfl | vfl; hn_det_quality.hip) and an IoU-family
+/* Detection loss with a quality classification term (detection.loss_cls_type = qfl | vfl; hn_det_loss.hip) and an IoU-family
  * regression term (kind 1 giou, 2 diou, 3 ciou).  The target of a positive anchor's class is the IoU q of its decoded prediction with its
  * annotation (the iou of hn_det_loss_iou_fwd, a constant in the backward), every other target is 0; with p^ = clamp(p, 1e-4, 1 - 1e-4),
  * BCE = -(y ln p^ + (1 - y) ln(1 - p^)): cls_kind 1 (qfl) l = (y - p^)^2 BCE; cls_kind 2 (vfl) l = y BCE for y > 0 and

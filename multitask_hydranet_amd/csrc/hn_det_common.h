@@ -1,6 +1,6 @@
-// The half of the detection loss that does not depend on the regression term: IoU anchor assignment and the focal classification loss
-// (FocalLoss.forward, head_detect/detection_loss.py:132-267).  hn_loss.hip (smooth-L1 regression) and hn_det_iou.hip (GIoU / DIoU / CIoU
-// regression) both build their kernels from these pieces, so the two paths assign and classify with the same instructions.
+// What the detection kernels of more than one source share: the per-image task masks (every masked loss, hn_loss.hip included), the IoU
+// anchor assignment (FocalLoss.forward, head_detect/detection_loss.py:132-267; hn_det_atss.hip restates its IoU) and the finalize kernel
+// of the detection loss.  The loss's terms and its kernel pair are hn_det_loss.hip's.
 #pragma once
 #include "hn_common.h"
 
@@ -48,32 +48,6 @@ __device__ __forceinline__ int det_assign(const float* anc, const float* ann, in
 // an assignment handed to the loss forward (ATSS, hn_det_atss.hip): anything that is not an annotation index, -1 or -2 counts as ignored,
 // so a stray value never indexes the annotations
 __device__ __forceinline__ int det_given_assign(short v, int Mx) { return v >= -2 && v < Mx ? (int)v : -2; }
-
-// focal BCE (alpha 0.25, gamma 2) of one counted anchor's K probabilities, clamped to [1e-4, 1-1e-4]; cid = its class, -1 for background
-__device__ __forceinline__ float det_focal_sum(const float* c, int K, int cid) {
-    float s = 0.f;
-    for (int k = 0; k < K; ++k) {
-        const float p = fminf(fmaxf(c[k], 1e-4f), 1.f - 1e-4f);
-        if (k == cid) s += 0.25f * (1.f - p) * (1.f - p) * -__logf(p);
-        else s += 0.75f * p * p * -__logf(1.f - p);
-    }
-    return s;
-}
-
-// The classification half of the backward for one anchor: its K probabilities in c[] are replaced by fc * d(focal sum)/dp.  as = the
-// anchor's assignment, cid = its class (-1 for background).  The callers stage the block's 256 x K run through LDS and hand each thread
-// its own row.
-__device__ __forceinline__ void det_focal_grad_row(float* c, int K, int as, int cid, float fc) {
-    for (int k = 0; k < K; ++k) {
-        float g = 0.f;
-        const float p = c[k];
-        if (as != -2 && p > 1e-4f && p < 1.f - 1e-4f) {                // the clamp has zero slope outside its range
-            if (k == cid) g = 0.25f * (2.f * (1.f - p) * __logf(p) - (1.f - p) * (1.f - p) / p);
-            else g = 0.75f * (-2.f * p * __logf(1.f - p) + p * p / (1.f - p));
-        }
-        c[k] = fc * g;
-    }
-}
 
 // One block of 1024 threads folds the forward's partial rows part[N][blocks][COLS] = {cls, reg, #pos[, extra]}.  Per image:
 // cls = sum_cls / max(npos, 1), reg = sum_reg / (REG_PER_POS npos) and extra = sum_extra / npos (both 0 without positives);

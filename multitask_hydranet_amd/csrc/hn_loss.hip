@@ -4,7 +4,7 @@
 //     so a 3-level (11+11+10 bit) radix select on the fp32 bit pattern replaces the sort: exact, deterministic (integer atomics only).
 //   * deploy-mode argmax over the class logits (model/model.py:197) -> int64 mask.
 #include "hn_common.h"
-#include "hn_det_common.h"      // det_assign, the focal forward / backward, the finalize kernel: shared with hn_det_iou.hip
+#include "hn_det_common.h"      // the per-image task masks (hn_image_valid, hn_count_valid)
 
 #define HN_SEG_MAXC 16
 
@@ -408,107 +408,6 @@ __global__ __launch_bounds__(256) void seg_count_ties_kernel(const float* loss, 
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(&ties[n], c);
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// Detection loss (FocalLoss.forward, head_detect/detection_loss.py:132-267): IoU assignment (neg < 0.4, pos >= 0.5, else ignored),
-// focal BCE (alpha 0.25, gamma 2) on probabilities clamped to [1e-4, 1-1e-4] divided by max(#pos, 1), smooth-L1 (beta 1/9) on
-// (dy, dx, dh, dw) averaged over positives x 4; batch mean.  One thread per (image, anchor); the per-image Python loop and the
-// A x M IoU matrix of the reference never exist.  assign[n][a]: >= 0 matched annotation, -1 background, -2 ignored.
-// ---------------------------------------------------------------------------------------------------------
-// GIVEN: assign is an input (hn_det_loss_fwd_assigned: ATSS, hn_det_atss.hip) instead of det_assign's output
-template <bool GIVEN>
-__global__ __launch_bounds__(256) void det_loss_fwd_kernel(const float* cls, const float* reg, const float* anchors, const float* ann, int A,
-                                                           int K, int Mx, short* assign, float* part /* [N][blocks][3] */,
-                                                           const unsigned char* valid) {
-    __shared__ float red[4][3];
-    const int n = blockIdx.y;
-    const int a = blockIdx.x * 256 + threadIdx.x;
-    float s_cls = 0.f, s_reg = 0.f, s_pos = 0.f;
-    if (a < A) {
-        const float* anc = anchors + (long)a * 4;
-        const float* an = ann + (long)n * Mx * 5;
-        int as = -2;                                                   // an unlabelled image: every anchor ignored
-        if (GIVEN) {
-            if (hn_image_valid(valid, n)) as = det_given_assign(assign[(long)n * A + a], Mx);
-        } else {
-            float biou;
-            if (hn_image_valid(valid, n)) as = det_assign(anc, an, Mx, biou);
-            assign[(long)n * A + a] = (short)as;
-        }
-        if (as != -2) s_cls = det_focal_sum(cls + ((long)n * A + a) * K, K, as >= 0 ? (int)an[as * 5 + 4] : -1);
-        if (as >= 0) {
-            s_pos = 1.f;
-            const float* b = an + as * 5;
-            const float aw = anc[3] - anc[1], ah = anc[2] - anc[0];
-            const float acx = anc[1] + 0.5f * aw, acy = anc[0] + 0.5f * ah;
-            float gw = b[2] - b[0], gh = b[3] - b[1];
-            const float gcx = b[0] + 0.5f * gw, gcy = b[1] + 0.5f * gh;
-            gw = fmaxf(gw, 1.f);
-            gh = fmaxf(gh, 1.f);
-            const float t[4] = {(gcy - acy) / ah, (gcx - acx) / aw, __logf(gh / ah), __logf(gw / aw)};
-            const float* r = reg + ((long)n * A + a) * 4;
-            for (int q = 0; q < 4; ++q) {
-                const float d = fabsf(t[q] - r[q]);
-                s_reg += d <= 1.f / 9.f ? 0.5f * 9.f * d * d : d - 0.5f / 9.f;
-            }
-        }
-    }
-    s_cls = wave_sum(s_cls); s_reg = wave_sum(s_reg); s_pos = wave_sum(s_pos);
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = s_cls; red[threadIdx.x >> 6][1] = s_reg; red[threadIdx.x >> 6][2] = s_pos; }
-    __syncthreads();
-    if (threadIdx.x < 3) part[((long)n * gridDim.x + blockIdx.x) * 3 + threadIdx.x] =
-        red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-}
-
-__global__ __launch_bounds__(256) void det_loss_bwd_kernel(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A,
-                                                           int K, int Mx, const short* assign, const float* npos, const float* gout /* [2] */,
-                                                           float* dcls, float* dreg, const unsigned char* valid) {
-    // the block's 256 x K probabilities / gradients are one contiguous run in memory: they move through LDS with coalesced 4-byte
-    // accesses (a thread walking its own K floats 36 bytes from its neighbour's wrote partial lines: 0.9 TB/s, 91 us per step)
-    extern __shared__ float tile[];                                    // [256][K]
-    const int n = blockIdx.y;
-    const int a0 = blockIdx.x * 256;
-    const int a = a0 + threadIdx.x;
-    const int nv = A - a0 < 256 ? A - a0 : 256;
-    const float* cblk = cls + ((long)n * A + a0) * K;
-    for (int i = threadIdx.x; i < nv * K; i += 256) tile[i] = cblk[i];
-    __syncthreads();
-    const float p_n = npos[n];
-    const bool lab = hn_image_valid(valid, n);
-    const int nlab = hn_count_valid(valid, N);                         // (lab implies nlab >= 1)
-    const float fc = lab ? gout[0] / (nlab * fmaxf(p_n, 1.f)) : 0.f;
-    const float fr = lab && p_n > 0.f ? gout[1] / (nlab * 4.f * p_n) : 0.f;
-    // (a given assignment keeps its values for an unlabelled image; a stray value counts as ignored here as in the forward, so it never
-    // indexes the annotations)
-    const int as = a < A && lab ? det_given_assign(assign[(long)n * A + a], Mx) : -2;
-    const float* an = ann + (long)n * Mx * 5;
-    if (a < A)                                                         // (K odd or not: stride-K rows, each thread only touches its own)
-        det_focal_grad_row(tile + threadIdx.x * K, K, as, as >= 0 ? (int)an[as * 5 + 4] : -1, fc);
-    __syncthreads();
-    float* dblk = dcls + ((long)n * A + a0) * K;
-    for (int i = threadIdx.x; i < nv * K; i += 256) dblk[i] = tile[i];
-    if (a >= A) return;
-    float* dr = dreg + ((long)n * A + a) * 4;
-    if (as >= 0) {
-        const float* anc = anchors + (long)a * 4;
-        const float* b = an + as * 5;
-        const float aw = anc[3] - anc[1], ah = anc[2] - anc[0];
-        const float acx = anc[1] + 0.5f * aw, acy = anc[0] + 0.5f * ah;
-        float gw = b[2] - b[0], gh = b[3] - b[1];
-        const float gcx = b[0] + 0.5f * gw, gcy = b[1] + 0.5f * gh;
-        gw = fmaxf(gw, 1.f);
-        gh = fmaxf(gh, 1.f);
-        const float t[4] = {(gcy - acy) / ah, (gcx - acx) / aw, __logf(gh / ah), __logf(gw / aw)};
-        const float* r = reg + ((long)n * A + a) * 4;
-        for (int q = 0; q < 4; ++q) {
-            const float d = t[q] - r[q];
-            const float ad = fabsf(d);
-            dr[q] = fr * (ad <= 1.f / 9.f ? -9.f * d : (d > 0.f ? -1.f : 1.f));
-        }
-    } else {
-        dr[0] = dr[1] = dr[2] = dr[3] = 0.f;
-    }
-}
-
 // deploy-mode argmax over C channel logits (NHWC fp32, first maximum wins like torch.argmax) -> int64
 __global__ void argmax_kernel(const float* logits, int ldl, int C, long M, long* out) {
     for (long m = (long)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (long)gridDim.x * blockDim.x) {
@@ -775,70 +674,6 @@ extern "C" int hn_argmax_channels(const float* logits, int ldl, int C, long M, l
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(argmax_kernel, dim3(blocks), dim3(256), 0, st, logits, ldl, C, M, out);
     HN_LAUNCH_CHECK();
-}
-
-extern "C" int hn_det_loss_blocks(int A) { return (A + 255) / 256; }
-
-// fwd: out[0] = classification loss, out[1] = regression loss (batch means); assign int16 [N][A], part fp32 [N][blocks][3], npos fp32 [N]
-// (valid: the det row of the task masks, hn_det_common.h; nullptr = every image labelled)
-static int det_loss_fwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
-                        void* assign, float* part, float* npos, float* out, const unsigned char* valid, hipStream_t st) {
-    HN_CHECK_ARG(cls && reg && anchors && ann && assign && part && npos && out && N > 0 && A > 0 && K > 0 && K <= HN_DET_MAXK && Mx > 0);
-    const int blocks = hn_det_loss_blocks(A);
-    hipLaunchKernelGGL(det_loss_fwd_kernel<false>, dim3(blocks, N), dim3(256), 0, st, cls, reg, anchors, ann, A, K, Mx, (short*)assign, part, valid);
-    hipLaunchKernelGGL((det_loss_finalize_kernel<3, 4>), dim3(1), dim3(1024), 0, st, part, blocks, N, npos, out, valid);
-    HN_LAUNCH_CHECK();
-}
-
-extern "C" int hn_det_loss_fwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
-                               void* assign, float* part, float* npos, float* out, hipStream_t st) {
-    return det_loss_fwd(cls, reg, anchors, ann, N, A, K, Mx, assign, part, npos, out, nullptr, st);
-}
-extern "C" int hn_det_loss_fwd_masked(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
-                                      const unsigned char* valid, void* assign, float* part, float* npos, float* out, hipStream_t st) {
-    HN_CHECK_ARG(valid);
-    return det_loss_fwd(cls, reg, anchors, ann, N, A, K, Mx, assign, part, npos, out, valid, st);
-}
-
-// hn_det_loss_fwd with assign [N][A] as an INPUT (values outside -2 .. Mx - 1 count as ignored); everything else as above
-static int det_loss_fwd_assigned(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
-                                 const void* assign, float* part, float* npos, float* out, const unsigned char* valid, hipStream_t st) {
-    HN_CHECK_ARG(cls && reg && anchors && ann && assign && part && npos && out && N > 0 && A > 0 && K > 0 && K <= HN_DET_MAXK && Mx > 0);
-    const int blocks = hn_det_loss_blocks(A);
-    hipLaunchKernelGGL(det_loss_fwd_kernel<true>, dim3(blocks, N), dim3(256), 0, st, cls, reg, anchors, ann, A, K, Mx, (short*)assign, part, valid);
-    hipLaunchKernelGGL((det_loss_finalize_kernel<3, 4>), dim3(1), dim3(1024), 0, st, part, blocks, N, npos, out, valid);
-    HN_LAUNCH_CHECK();
-}
-
-extern "C" int hn_det_loss_fwd_assigned(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
-                                        const void* assign, float* part, float* npos, float* out, hipStream_t st) {
-    return det_loss_fwd_assigned(cls, reg, anchors, ann, N, A, K, Mx, assign, part, npos, out, nullptr, st);
-}
-extern "C" int hn_det_loss_fwd_assigned_masked(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K,
-                                               int Mx, const unsigned char* valid, const void* assign, float* part, float* npos, float* out,
-                                               hipStream_t st) {
-    HN_CHECK_ARG(valid);
-    return det_loss_fwd_assigned(cls, reg, anchors, ann, N, A, K, Mx, assign, part, npos, out, valid, st);
-}
-
-static int det_loss_bwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
-                        const void* assign, const float* npos, const float* gout, float* dcls, float* dreg, const unsigned char* valid,
-                        hipStream_t st) {
-    HN_CHECK_ARG(cls && reg && anchors && ann && assign && npos && gout && dcls && dreg && N > 0 && A > 0 && K > 0 && Mx > 0);
-    HN_CHECK_ARG(K <= 48);                                             // 256 x K floats of LDS
-    hipLaunchKernelGGL(det_loss_bwd_kernel, dim3(hn_det_loss_blocks(A), N), dim3(256), 256 * (size_t)K * sizeof(float), st, cls, reg, anchors, ann, N, A, K, Mx,
-                       (const short*)assign, npos, gout, dcls, dreg, valid);
-    HN_LAUNCH_CHECK();
-}
-extern "C" int hn_det_loss_bwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
-                               const void* assign, const float* npos, const float* gout, float* dcls, float* dreg, hipStream_t st) {
-    return det_loss_bwd(cls, reg, anchors, ann, N, A, K, Mx, assign, npos, gout, dcls, dreg, nullptr, st);
-}
-extern "C" int hn_det_loss_bwd_masked(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
-                                      const unsigned char* valid, const void* assign, const float* npos, const float* gout, float* dcls,
-                                      float* dreg, hipStream_t st) {
-    HN_CHECK_ARG(valid);
-    return det_loss_bwd(cls, reg, anchors, ann, N, A, K, Mx, assign, npos, gout, dcls, dreg, valid, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------

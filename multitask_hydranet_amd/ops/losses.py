@@ -206,13 +206,28 @@ def argmax_channels(seg_nchw):
 
 
 # --------------------------------------------------------------------------------------------------------------
-# detection loss (focal BCE + smooth-L1 with IoU anchor assignment)
+# detection loss (IoU or given anchor assignment; focal / qfl / vfl classification; smooth-L1 / giou / diou / ciou regression)
 # --------------------------------------------------------------------------------------------------------------
+DET_IOU_KINDS = {"giou": 1, "diou": 2, "ciou": 3}
+DET_CLS_KINDS = {"focal": 0, "qfl": 1, "vfl": 2}
+
+
+def _det_entry(which, reg_kind, cls_kind, given, valid):
+    """(entry-point name, the arguments between Mx and the buffers) of the detection loss's forward (which = "fwd") or backward ("bwd")
+    for reg_kind 0 (smooth-L1) | DET_IOU_KINDS, cls_kind of DET_CLS_KINDS, an assignment handed in or not, a mask row or None"""
+    if cls_kind:       # one pair of names takes the mask and the given assignment as (nullable) arguments
+        return f"hn_det_loss_quality_{which}", (reg_kind, cls_kind, ptr(valid)) + ((int(given),) if which == "fwd" else ())
+    name = ("hn_det_loss_iou_" if reg_kind else "hn_det_loss_") + which + ("_assigned" if given and which == "fwd" else "")
+    return _masked(name, valid), ((reg_kind,) if reg_kind else ()) + tuple(_v(valid))
+
+
 class DetLoss(torch.autograd.Function):
-    """returns a 2-vector (classification loss, regression loss), both batch means like FocalLoss.forward."""
+    """The detection loss of hn_det_loss.hip for every pair of terms: (classification loss, regression loss), both batch means like
+    FocalLoss.forward, and with an IoU-family regression term (reg_kind != 0) the mean IoU of the positives as a third output, a
+    diagnostic and not differentiable."""
 
     @staticmethod
-    def forward(ctx, cls, reg, anchors, ann, given=None, valid=None):
+    def forward(ctx, cls, reg, anchors, ann, reg_kind=0, cls_kind=0, given=None, valid=None):
         n, a, k = cls.shape
         mx = ann.shape[1]
         dev = cls.device
@@ -220,24 +235,25 @@ class DetLoss(torch.autograd.Function):
         cls, reg, ann = cls.contiguous(), reg.contiguous(), ann.contiguous().float()
         anc = anchors.reshape(-1, 4).contiguous()
         blocks = lib().query("hn_det_loss_blocks", a)
-        part = torch.empty((n, blocks, 3), device=dev, dtype=F32)
+        part = torch.empty((n, blocks, 4 if reg_kind else 3), device=dev, dtype=F32)
         npos = torch.empty((n,), device=dev, dtype=F32)
-        out = torch.empty((2,), device=dev, dtype=F32)
-        if given is None:
-            assign = torch.empty((n, a), device=dev, dtype=torch.int16)
-            lib().call(_masked("hn_det_loss_fwd", valid), ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, *_v(valid), ptr(assign), ptr(part),
-                       ptr(npos), ptr(out))
-        else:
-            assign = _given_assign(given, n, a, dev)
-            lib().call(_masked("hn_det_loss_fwd_assigned", valid), ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, *_v(valid), ptr(assign),
-                       ptr(part), ptr(npos), ptr(out))
+        out = torch.empty((3 if reg_kind else 2,), device=dev, dtype=F32)
+        assign = torch.empty((n, a), device=dev, dtype=torch.int16) if given is None else _given_assign(given, n, a, dev)
+        name, args = _det_entry("fwd", reg_kind, cls_kind, given is not None, valid)
+        lib().call(name, ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, *args, ptr(assign), ptr(part), ptr(npos), ptr(out))
+        ctx.kinds = (reg_kind, cls_kind)
         ctx.save_for_backward(cls, reg, anc, ann, assign, npos)
-        # the two losses leave as two outputs (slicing a 2-vector OUTSIDE the node cost two SliceBackward nodes -- fill + copy each -- and
+        # the losses leave as separate outputs (slicing a 2-vector OUTSIDE the node cost two SliceBackward nodes -- fill + copy each -- and
         # an add per step: seven 5 us launches)
-        return out[0:1], out[1:2]
+        if not reg_kind:
+            return out[0:1], out[1:2]
+        pos_iou = out[2:3]
+        ctx.mark_non_differentiable(pos_iou)
+        ctx.set_materialize_grads(False)        # (no zero-filled "gradient" of the diagnostic: a fill launch per step)
+        return out[0:1], out[1:2], pos_iou
 
     @staticmethod
-    def backward(ctx, gcls, greg):
+    def backward(ctx, gcls, greg, _giou=None):
         cls, reg, anc, ann, assign, npos = ctx.saved_tensors
         n, a, k = cls.shape
         dcls, dreg = torch.empty_like(cls), torch.empty_like(reg)
@@ -247,9 +263,10 @@ class DetLoss(torch.autograd.Function):
         else:
             z = zeros((1,), cls.device)
             g = torch.cat([(gcls if gcls is not None else z).reshape(1).to(F32), (greg if greg is not None else z).reshape(1).to(F32)])
-        lib().call(_masked("hn_det_loss_bwd", ctx.valid), ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, ann.shape[1], *_v(ctx.valid),
-                   ptr(assign), ptr(npos), ptr(g), ptr(dcls), ptr(dreg))
-        return dcls, dreg, None, None, None, None
+        name, args = _det_entry("bwd", *ctx.kinds, False, ctx.valid)
+        lib().call(name, ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, ann.shape[1], *args, ptr(assign), ptr(npos), ptr(g), ptr(dcls),
+                   ptr(dreg))
+        return dcls, dreg, None, None, None, None, None, None
 
 
 def _given_assign(assign, n, a, dev):
@@ -265,7 +282,7 @@ def det_loss_hip(classification, regression, anchors, annotations, assign=None, 
     (npos 0; -2 throughout its row of a computed assignment) and the batch means are taken over the labelled images."""
     if assign is None and valid is None:
         return DetLoss.apply(classification, regression, anchors, annotations)
-    return DetLoss.apply(classification, regression, anchors, annotations, assign, valid)
+    return DetLoss.apply(classification, regression, anchors, annotations, 0, 0, assign, valid)
 
 
 def det_atss_assign(anchors, level_sizes, annotations, topk=9, anchors_per_location=9):
@@ -307,101 +324,6 @@ def det_atss_assign(anchors, level_sizes, annotations, topk=9, anchors_per_locat
     return assign, thr
 
 
-DET_IOU_KINDS = {"giou": 1, "diou": 2, "ciou": 3}
-
-
-class DetIoULoss(torch.autograd.Function):
-    """DetLoss with an IoU-family regression term (hn_det_iou.hip): (classification loss, regression loss, mean IoU of the positives),
-    all batch means; the third is a diagnostic and not differentiable."""
-
-    @staticmethod
-    def forward(ctx, cls, reg, anchors, ann, kind, given=None, valid=None):
-        n, a, k = cls.shape
-        mx = ann.shape[1]
-        dev = cls.device
-        ctx.valid = valid = None if valid is None else _task_valid_row(valid, n, dev)
-        cls, reg, ann = cls.contiguous(), reg.contiguous(), ann.contiguous().float()
-        anc = anchors.reshape(-1, 4).contiguous()
-        blocks = lib().query("hn_det_loss_blocks", a)
-        part = torch.empty((n, blocks, 4), device=dev, dtype=F32)
-        npos = torch.empty((n,), device=dev, dtype=F32)
-        out = torch.empty((3,), device=dev, dtype=F32)
-        if given is None:
-            assign = torch.empty((n, a), device=dev, dtype=torch.int16)
-            lib().call(_masked("hn_det_loss_iou_fwd", valid), ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, kind, *_v(valid), ptr(assign),
-                       ptr(part), ptr(npos), ptr(out))
-        else:
-            assign = _given_assign(given, n, a, dev)
-            lib().call(_masked("hn_det_loss_iou_fwd_assigned", valid), ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, kind, *_v(valid),
-                       ptr(assign), ptr(part), ptr(npos), ptr(out))
-        ctx.kind = kind
-        ctx.save_for_backward(cls, reg, anc, ann, assign, npos)
-        pos_iou = out[2:3]
-        ctx.mark_non_differentiable(pos_iou)
-        ctx.set_materialize_grads(False)        # (no zero-filled "gradient" of the diagnostic: a fill launch per step)
-        return out[0:1], out[1:2], pos_iou
-
-    @staticmethod
-    def backward(ctx, gcls, greg, _giou):
-        cls, reg, anc, ann, assign, npos = ctx.saved_tensors
-        n, a, k = cls.shape
-        dcls, dreg = torch.empty_like(cls), torch.empty_like(reg)
-        if (gcls is not None and greg is not None and gcls.dtype == F32 and greg.dtype == F32
-                and greg.data_ptr() == gcls.data_ptr() + 4):       # neighbours in WeightedLossSum.backward's gradient vector: used in place
-            g = gcls
-        else:
-            z = zeros((1,), cls.device)
-            g = torch.cat([(gcls if gcls is not None else z).reshape(1).to(F32), (greg if greg is not None else z).reshape(1).to(F32)])
-        lib().call(_masked("hn_det_loss_iou_bwd", ctx.valid), ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, ann.shape[1], ctx.kind,
-                   *_v(ctx.valid), ptr(assign), ptr(npos), ptr(g), ptr(dcls), ptr(dreg))
-        return dcls, dreg, None, None, None, None, None
-
-
-DET_CLS_KINDS = {"focal": 0, "qfl": 1, "vfl": 2}
-
-
-class DetQualityLoss(torch.autograd.Function):
-    """DetIoULoss with a quality classification term (hn_det_quality.hip; cls_kind 1 = qfl, 2 = vfl): the same three outputs, the same
-    launch count.  One pair of entry points takes the mask and the given assignment as (nullable) arguments."""
-
-    @staticmethod
-    def forward(ctx, cls, reg, anchors, ann, kind, cls_kind, given=None, valid=None):
-        n, a, k = cls.shape
-        mx = ann.shape[1]
-        dev = cls.device
-        ctx.valid = valid = None if valid is None else _task_valid_row(valid, n, dev)
-        cls, reg, ann = cls.contiguous(), reg.contiguous(), ann.contiguous().float()
-        anc = anchors.reshape(-1, 4).contiguous()
-        blocks = lib().query("hn_det_loss_blocks", a)
-        part = torch.empty((n, blocks, 4), device=dev, dtype=F32)
-        npos = torch.empty((n,), device=dev, dtype=F32)
-        out = torch.empty((3,), device=dev, dtype=F32)
-        assign = torch.empty((n, a), device=dev, dtype=torch.int16) if given is None else _given_assign(given, n, a, dev)
-        lib().call("hn_det_loss_quality_fwd", ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, kind, cls_kind,
-                   ptr(valid), 0 if given is None else 1, ptr(assign), ptr(part), ptr(npos), ptr(out))
-        ctx.kind, ctx.cls_kind = kind, cls_kind
-        ctx.save_for_backward(cls, reg, anc, ann, assign, npos)
-        pos_iou = out[2:3]
-        ctx.mark_non_differentiable(pos_iou)
-        ctx.set_materialize_grads(False)        # (no zero-filled "gradient" of the diagnostic: a fill launch per step)
-        return out[0:1], out[1:2], pos_iou
-
-    @staticmethod
-    def backward(ctx, gcls, greg, _giou):
-        cls, reg, anc, ann, assign, npos = ctx.saved_tensors
-        n, a, k = cls.shape
-        dcls, dreg = torch.empty_like(cls), torch.empty_like(reg)
-        if (gcls is not None and greg is not None and gcls.dtype == F32 and greg.dtype == F32
-                and greg.data_ptr() == gcls.data_ptr() + 4):       # neighbours in WeightedLossSum.backward's gradient vector: used in place
-            g = gcls
-        else:
-            z = zeros((1,), cls.device)
-            g = torch.cat([(gcls if gcls is not None else z).reshape(1).to(F32), (greg if greg is not None else z).reshape(1).to(F32)])
-        lib().call("hn_det_loss_quality_bwd", ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, ann.shape[1], ctx.kind, ctx.cls_kind,
-                   ptr(ctx.valid), ptr(assign), ptr(npos), ptr(g), ptr(dcls), ptr(dreg))
-        return dcls, dreg, None, None, None, None, None, None
-
-
 def det_iou_loss_hip(classification, regression, anchors, annotations, kind, assign=None, valid=None, cls_kind="focal"):
     """The detection loss with its regression term replaced by an IoU-family loss; kind = "giou" | "diou" | "ciou".  Returns
     (classification loss [1], regression loss [1], pos_iou [1]).  Anchor assignment (IoU >= 0.5 positive, < 0.4 background, between
@@ -428,7 +350,7 @@ def det_iou_loss_hip(classification, regression, anchors, annotations, kind, ass
     valid: the det row of the task masks, as for det_loss_hip; pos_iou is averaged over the labelled images as well.
 
     cls_kind: "focal" (the default) makes exactly the calls above.  "qfl" (quality focal loss, Li et al. 2020) and "vfl" (varifocal
-    loss, Zhang et al. 2021) replace the classification term by one whose target is the quality of the box (hn_det_quality.hip); the
+    loss, Zhang et al. 2021) replace the classification term by one whose target is the quality of the box (hn_det_loss.hip); the
     assignment, the regression loss, pos_iou and the regression gradient stay the focal call's, bit for bit.  For a counted anchor
     (assignment not -2: ignored anchors and every anchor of an unlabelled image contribute nothing and get gradient 0) and class k:
 
@@ -449,11 +371,9 @@ def det_iou_loss_hip(classification, regression, anchors, annotations, kind, ass
         raise ValueError(f"kind must be one of {sorted(DET_IOU_KINDS)}, got {kind!r}")
     if cls_kind not in DET_CLS_KINDS:
         raise ValueError(f"cls_kind must be one of {sorted(DET_CLS_KINDS)}, got {cls_kind!r}")
-    if cls_kind != "focal":
-        return DetQualityLoss.apply(classification, regression, anchors, annotations, DET_IOU_KINDS[kind], DET_CLS_KINDS[cls_kind], assign, valid)
-    if assign is None and valid is None:
-        return DetIoULoss.apply(classification, regression, anchors, annotations, DET_IOU_KINDS[kind])
-    return DetIoULoss.apply(classification, regression, anchors, annotations, DET_IOU_KINDS[kind], assign, valid)
+    if cls_kind == "focal" and assign is None and valid is None:
+        return DetLoss.apply(classification, regression, anchors, annotations, DET_IOU_KINDS[kind])
+    return DetLoss.apply(classification, regression, anchors, annotations, DET_IOU_KINDS[kind], DET_CLS_KINDS[cls_kind], assign, valid)
 
 
 

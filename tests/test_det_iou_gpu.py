@@ -1,4 +1,4 @@
-"""GPU: the IoU-family box regression losses (detection.loss_reg_type = giou | diou | ciou; csrc/hn_det_iou.hip) against the float64
+"""GPU: the IoU-family box regression losses (detection.loss_reg_type = giou | diou | ciou; csrc/hn_det_loss.hip) against the float64
 restatement tests/det_iou_ref.py.  Bounds are the project's for the smooth-L1 detection loss (test_det_loss_matches_reference_loop):
 losses 2e-5 relative, dcls / dreg 2e-4 of the reference's maximum; tests/test_det_iou_cpu.py measures what float32 alone costs on the
 same inputs (1e-7 / 5e-7).  The classification half must keep hn_det_loss_fwd/bwd's bits."""

@@ -152,7 +152,7 @@ def test_library_exports_the_entry_points_and_rejects_bad_arguments(built):
     dll = ctypes.CDLL(built.SO_PATH)
     for name in ("hn_det_loss_quality_fwd", "hn_det_loss_quality_bwd"):
         assert name in sig and hasattr(dll, name)
-    assert "hn_det_quality.hip" in built.SOURCES
+    assert "hn_det_loss.hip" in built.SOURCES
     l = built.lib()
     # HN_CHECK_ARG returns 1 before any launch: the pointers are never dereferenced (1 stands for 'not null'); valid may be null
     fwd = lambda cls=1, K=9, kind=1, ck=1, given=0, assign=1: l.raw("hn_det_loss_quality_fwd")(cls, 1, 1, 1, 2, 300, K, 8, kind, ck, None, given,

@@ -1,4 +1,4 @@
-"""GPU: the quality focal / varifocal detection losses (detection.loss_cls_type = qfl | vfl; csrc/hn_det_quality.hip) against the float64
+"""GPU: the quality focal / varifocal detection losses (detection.loss_cls_type = qfl | vfl; csrc/hn_det_loss.hip) against the float64
 restatement tests/det_quality_ref.py.  Bounds are the project's for the detection losses (test_det_iou_gpu.py): losses and pos_iou 2e-5
 relative, dcls / dreg 2e-4 of the reference's maximum -- and dcls once more over the positive anchors' rows alone, against the maximum
 over those rows; tests/test_det_quality_cpu.py measures what float32 alone costs on the same inputs (6e-7 / 1.4e-6).  The regression

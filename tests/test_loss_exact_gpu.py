@@ -1,5 +1,5 @@
-"""The loss kernels of csrc/hn_loss.hip (and the pieces of csrc/hn_det_common.h they are built from) held to the integer / float64
-reference of tests/loss_ref.py through the C entry points, so that the test, not a wrapper, chooses the dispatch variant and k.
+"""The loss kernels of csrc/hn_loss.hip and csrc/hn_det_loss.hip (and the pieces of csrc/hn_det_common.h they are built from) held to the
+integer / float64 reference of tests/loss_ref.py through the C entry points, so that the test, not a wrapper, chooses the dispatch variant and k.
 tests/test_loss_ref_cpu.py pins that reference to torch double and np.sort and checks the margins of the inputs used here.
 
 Entry point and dispatch variant reached by each test
@@ -19,8 +19,8 @@ Entry point and dispatch variant reached by each test
       with the logits 4 bytes off alignment); hist_select_256 on injected bytes; hn_lane_cls_loss_bwd.
   test_focal_seg_loss             hn_seg_focal_fwd / _bwd, the powf branches (gamma 1.5, 1) and gamma 2, alpha 1 and 0.25, C 2, 5, 16.
   test_lane_loc_loss              hn_lane_loc_loss_fwd / _bwd at L 3, 33, 42, 322, M % 8 != 0.
-  test_det_smooth_l1_loss         hn_det_loss_fwd / _bwd: det_loss_fwd_kernel<false>, det_loss_finalize_kernel<3, 4> with N on both
-                                  sides of its 16-image pass, det_loss_bwd_kernel with partial 256-anchor blocks.
+  test_det_smooth_l1_loss         hn_det_loss_fwd / _bwd: det_loss_fwd_kernel<false, false, false>, det_loss_finalize_kernel<3, 4> with N
+                                  on both sides of its 16-image pass, det_loss_bwd_kernel<false, false> with partial 256-anchor blocks.
   test_weighted_sum_*             hn_weighted_sum, forward and gradients, and its argument checks.
 
 Injected bit patterns (loss_ref.seg_pattern / lane_pattern): a seg pixel with logits (0, -b, ..., -b), target 1 and cw[1] = 1 has the loss
