@@ -555,6 +555,25 @@ int hn_det_loss_quality_fwd(const float* cls, const float* reg, const float* anc
 int hn_det_loss_quality_bwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx, int kind,
                             int cls_kind, const unsigned char* valid, const void* assign, const float* npos, const float* gout, float* dcls,
                             float* dreg, hipStream_t stream);
+/* Task-aligned anchor assignment (detection.assigner = tal; hn_det_tal.hip, the rule is stated there and in ops.det_tal_assign): per box
+ * the topk anchors with the largest metric t = score * IoU^6 among those whose centre lies inside the box, IoU being the iou of
+ * hn_det_loss_iou_fwd for the anchor's own regression; conflicts go to the larger IoU.  regression fp32 [N][A][4] and classification fp32
+ * [N][A][K] (post-sigmoid, K <= 32) are read as constants; anchors and regression 16-byte aligned; N <= 65535, Mx <= 32767,
+ * 1 <= topk <= 2048.  ws: hn_det_tal_ws_bytes(...) bytes (-1 for arguments the call would reject).  Writes assign int16 [N][A] (>= 0
+ * annotation index, -1 background; never -2) and target fp32 [N][A]: (t / tmax) * umax of an assigned anchor with the maxima taken over its
+ * box's assigned anchors, else 0.  Three launches. */
+long hn_det_tal_ws_bytes(int N, int A, int Mx, int topk);
+int hn_det_tal_assign(const float* anchors, const float* regression, const float* classification, const float* ann, int N, int A, int K, int Mx,
+                      int topk, void* ws, void* assign, float* target, hipStream_t stream);
+/* hn_det_loss_quality_fwd / _bwd with the positives' classification target handed in: y = target[n][a] (fp32 [N][A], e.g.
+ * hn_det_tal_assign's) instead of the box's IoU, in the forward and in the backward.  assign_given must be 1.  The regression loss, out[2],
+ * npos and dreg are hn_det_loss_quality_fwd / _bwd's on the same assign, bit for bit. */
+int hn_det_loss_aligned_fwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx, int kind,
+                            int cls_kind, const unsigned char* valid, int assign_given, void* assign, const float* target, float* part,
+                            float* npos, float* out, hipStream_t stream);
+int hn_det_loss_aligned_bwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx, int kind,
+                            int cls_kind, const unsigned char* valid, const void* assign, const float* target, const float* npos,
+                            const float* gout, float* dcls, float* dreg, hipStream_t stream);
 /* torch.argmax(seg, dim=1) of deploy mode (model/model.py:197): fp32 NHWC logits -> int64 class ids, first maximum wins. */
 /* Lane losses (head_lane/lanedetect_loss.py:18-78).  cls: logits / one-hot target fp32 [M][2]; out[0] = positive term, out[1] = OHEM
  * negative term (NEGATIVE_RATIO 15, ALPHA 10: the k-th smallest background log-prob is found by a radix select, not a sort);

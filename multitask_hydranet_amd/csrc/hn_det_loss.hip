@@ -50,9 +50,6 @@
 #include "hn_common.h"
 #include "hn_det_common.h"
 
-#define HN_DET_IOU_EPS 1e-7f
-#define HN_DET_IOU_CLIP 4.135166556742356f                             // log(1000 / 16)
-
 // ---- regression terms of one positive anchor: r = its (dy, dx, dh, dw), anc = its anchor, b = its annotation ----
 
 // smooth-L1 against the encoded target: without GRAD loss = the sum over the four coordinates, with GRAD g[4] = d loss / d r (loss is
@@ -79,80 +76,7 @@ __device__ __forceinline__ void det_smooth_l1(const float* r, const float* anc, 
     }
 }
 
-// The box function of the IoU-family losses: the anchor's decoded prediction against its annotation.  Every instantiation decodes,
-// overlaps and differentiates a box with these instructions; the quality terms' target is this function's iou.
-// loss and iou of one positive anchor; with GRAD also g[4] = d loss / d (dy, dx, dh, dw).  The gradient goes through the box corners
-// (x1, y1, x2, y2): a min / max passes it to the side that wins, w h and (for ciou) v add their direct dependence on the sides.
-// exp / atan are the precise ones: a few dozen positives per image pay for them, and the decode must not add error to a loss of ~1e-1.
-template <bool GRAD>
-__device__ __forceinline__ void det_iou_box(const float* r, const float* anc, const float* b, int kind, float& loss, float& iou, float* g) {
-    const float ha = anc[2] - anc[0], wa = anc[3] - anc[1];
-    const float cya = 0.5f * (anc[0] + anc[2]), cxa = 0.5f * (anc[1] + anc[3]);
-    const float cy = r[0] * ha + cya, cx = r[1] * wa + cxa;
-    const float h = expf(fminf(r[2], HN_DET_IOU_CLIP)) * ha, w = expf(fminf(r[3], HN_DET_IOU_CLIP)) * wa;
-    const float px1 = cx - 0.5f * w, px2 = cx + 0.5f * w, py1 = cy - 0.5f * h, py2 = cy + 0.5f * h;
-    float gw = b[2] - b[0], gh = b[3] - b[1];
-    const float gcx = b[0] + 0.5f * gw, gcy = b[1] + 0.5f * gh;
-    gw = fmaxf(gw, 1.f);
-    gh = fmaxf(gh, 1.f);
-    const float tx1 = gcx - 0.5f * gw, tx2 = gcx + 0.5f * gw, ty1 = gcy - 0.5f * gh, ty2 = gcy + 0.5f * gh;
-    const float iw = fminf(px2, tx2) - fmaxf(px1, tx1), ih = fminf(py2, ty2) - fmaxf(py1, ty1);
-    const float iwc = fmaxf(iw, 0.f), ihc = fmaxf(ih, 0.f);
-    const float inter = iwc * ihc;
-    const float uni = w * h + gw * gh - inter + HN_DET_IOU_EPS;
-    iou = inter / uni;
-    const float cw = fmaxf(px2, tx2) - fminf(px1, tx1), ch = fmaxf(py2, ty2) - fminf(py1, ty1);
-    // d loss / d {inter, w h (the predicted area), cw, ch, cx, cy, w, h}: the last four are the direct dependences only
-    float d_inter = -(uni + inter) / (uni * uni), d_area = inter / (uni * uni);
-    float d_cw = 0.f, d_ch = 0.f, d_cx = 0.f, d_cy = 0.f, d_w = 0.f, d_h = 0.f;
-    if (kind == 1) {
-        const float ac = cw * ch + HN_DET_IOU_EPS;
-        loss = 1.f - iou + (ac - uni) / ac;
-        if (GRAD) {
-            d_inter += 1.f / ac;
-            d_area -= 1.f / ac;
-            d_cw = uni / (ac * ac) * ch;
-            d_ch = uni / (ac * ac) * cw;
-        }
-    } else {
-        const float ex = cx - gcx, ey = cy - gcy;
-        const float rho2 = ex * ex + ey * ey;
-        const float c2 = cw * cw + ch * ch + HN_DET_IOU_EPS;
-        loss = 1.f - iou + rho2 / c2;
-        if (GRAD) {
-            d_cx = 2.f * ex / c2;
-            d_cy = 2.f * ey / c2;
-            d_cw = -2.f * rho2 / (c2 * c2) * cw;
-            d_ch = -2.f * rho2 / (c2 * c2) * ch;
-        }
-        if (kind == 3) {
-            const float k4 = 0.40528473456935109f;                     // 4 / pi^2
-            const float da = atanf(gw / gh) - atanf(w / h);
-            const float v = k4 * da * da;
-            const float alpha = v / (1.f - iou + v + HN_DET_IOU_EPS);
-            loss += alpha * v;
-            if (GRAD) {
-                const float s = alpha * 2.f * k4 * da / (w * w + h * h);  // d atan(w / h) = (h dw - w dh) / (w^2 + h^2)
-                d_w = -s * h;
-                d_h = s * w;
-            }
-        }
-    }
-    if (GRAD) {
-        const float d_iw = iw > 0.f ? d_inter * ihc : 0.f, d_ih = ih > 0.f ? d_inter * iwc : 0.f;
-        // iw = min(px2, tx2) - max(px1, tx1), cw = max(px2, tx2) - min(px1, tx1): each corner takes the gradient of the term it decides
-        const float g_x2 = (px2 < tx2 ? d_iw : 0.f) + (px2 > tx2 ? d_cw : 0.f);
-        const float g_x1 = -(px1 > tx1 ? d_iw : 0.f) - (px1 < tx1 ? d_cw : 0.f);
-        const float g_y2 = (py2 < ty2 ? d_ih : 0.f) + (py2 > ty2 ? d_ch : 0.f);
-        const float g_y1 = -(py1 > ty1 ? d_ih : 0.f) - (py1 < ty1 ? d_ch : 0.f);
-        const float G_cx = g_x1 + g_x2 + d_cx, G_cy = g_y1 + g_y2 + d_cy;
-        const float G_w = 0.5f * (g_x2 - g_x1) + d_area * h + d_w, G_h = 0.5f * (g_y2 - g_y1) + d_area * w + d_h;
-        g[0] = G_cy * ha;
-        g[1] = G_cx * wa;
-        g[2] = r[2] <= HN_DET_IOU_CLIP ? G_h * h : 0.f;                 // d h / d dh = h, 0 where the clip is active
-        g[3] = r[3] <= HN_DET_IOU_CLIP ? G_w * w : 0.f;
-    }
-}
+// (the box function of the IoU-family terms, det_iou_box, is hn_det_common.h's: the task-aligned assigner measures with it too)
 
 // ---- classification terms of one counted anchor: c = its K probabilities, cid = its class (-1 for background) ----
 
@@ -236,7 +160,8 @@ __device__ __forceinline__ void det_quality_grad_row(float* c, int K, int as, in
 template <bool IOU, bool QUALITY, bool GIVEN>
 __global__ __launch_bounds__(256) void det_loss_fwd_kernel(const float* cls, const float* reg, const float* anchors, const float* ann, int A,
                                                            int K, int Mx, int kind, int cls_kind, short* assign,
-                                                           float* part /* [N][blocks][COLS] */, const unsigned char* valid) {
+                                                           float* part /* [N][blocks][COLS] */, const unsigned char* valid,
+                                                           const float* target /* [N][A] or nullptr (QUALITY only) */) {
     static_assert(IOU || !QUALITY, "the quality terms' target is the box's iou");
     constexpr int COLS = IOU ? 4 : 3;
     __shared__ float red[4][COLS];
@@ -263,7 +188,12 @@ __global__ __launch_bounds__(256) void det_loss_fwd_kernel(const float* cls, con
         if (as != -2) {
             const float* c = cls + ((long)n * A + a) * K;
             const int cid = as >= 0 ? (int)an[as * 5 + 4] : -1;
-            s_cls = QUALITY ? det_quality_sum(c, K, cid, s_iou, cls_kind) : det_focal_sum(c, K, cid);
+            if (QUALITY) {                                             // a given target (hn_det_tal.hip's) replaces the positives' iou as y
+                const float y = target && as >= 0 ? target[(long)n * A + a] : s_iou;
+                s_cls = det_quality_sum(c, K, cid, y, cls_kind);
+            } else {
+                s_cls = det_focal_sum(c, K, cid);
+            }
         }
     }
     s_cls = wave_sum(s_cls); s_reg = wave_sum(s_reg); s_pos = wave_sum(s_pos);
@@ -280,7 +210,8 @@ __global__ __launch_bounds__(256) void det_loss_fwd_kernel(const float* cls, con
 template <bool IOU, bool QUALITY>
 __global__ __launch_bounds__(256) void det_loss_bwd_kernel(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A,
                                                            int K, int Mx, int kind, int cls_kind, const short* assign, const float* npos,
-                                                           const float* gout /* [2] */, float* dcls, float* dreg, const unsigned char* valid) {
+                                                           const float* gout /* [2] */, float* dcls, float* dreg, const unsigned char* valid,
+                                                           const float* target /* [N][A] or nullptr (QUALITY only) */) {
     static_assert(IOU || !QUALITY, "the quality terms' target is the box's iou");
     // the block's 256 x K probabilities / gradients are one contiguous run in memory: they move through LDS with coalesced 4-byte
     // accesses (a thread walking its own K floats 36 bytes from its neighbour's wrote partial lines: 0.9 TB/s, 91 us per step); every
@@ -309,6 +240,7 @@ __global__ __launch_bounds__(256) void det_loss_bwd_kernel(const float* cls, con
         const float* r = reg + ((long)n * A + a) * 4;
         if (IOU) det_iou_box<true>(r, anchors + (long)a * 4, an + as * 5, kind, loss, q, g);
         else det_smooth_l1<true>(r, anchors + (long)a * 4, an + as * 5, loss, g);
+        if (QUALITY && target) q = target[(long)n * A + a];
     }
     if (a < A) {                                                       // (K odd or not: stride-K rows, each thread only touches its own)
         float* c = tile + threadIdx.x * K;
@@ -328,23 +260,24 @@ __global__ __launch_bounds__(256) void det_loss_bwd_kernel(const float* cls, con
 extern "C" int hn_det_loss_blocks(int A) { return (A + 255) / 256; }   // partial rows per image
 
 // The launchers behind every hn_det_loss* entry point.  reg_kind: 0 smooth-L1, 1 giou, 2 diou, 3 ciou; cls_kind: 0 focal, 1 qfl, 2 vfl
-// (1, 2 only with reg_kind != 0); valid: the det row of the task masks (nullptr = every image labelled).
+// (1, 2 only with reg_kind != 0); valid: the det row of the task masks (nullptr = every image labelled); target: fp32 [N][A], a positive
+// anchor's y under cls_kind 1, 2 instead of its box's iou (nullptr = the iou; only the aligned entry points pass one).
 // fwd: out[0] = classification loss, out[1] = regression loss[, out[2] = mean IoU of the positives unless reg_kind 0] (batch means of
 // per-image means); assign int16 [N][A] (written, or read when assign_given: values outside -2 .. Mx - 1 count as ignored), part fp32
 // [N][blocks][3 for reg_kind 0, else 4], npos fp32 [N]
 static int det_loss_fwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
                         int reg_kind, int cls_kind, const unsigned char* valid, int assign_given, void* assign, float* part, float* npos,
-                        float* out, hipStream_t st) {
+                        float* out, hipStream_t st, const float* target = nullptr) {
     HN_CHECK_ARG(cls && reg && anchors && ann && assign && part && npos && out && N > 0 && A > 0 && K > 0 && K <= HN_DET_MAXK && Mx > 0);
     HN_CHECK_ARG(reg_kind >= 0 && reg_kind <= 3 && cls_kind >= 0 && cls_kind <= (reg_kind ? 2 : 0) && (assign_given == 0 || assign_given == 1));
     static void (*const kernels[3][2])(const float*, const float*, const float*, const float*, int, int, int, int, int, short*, float*,
-                                       const unsigned char*) = {
+                                       const unsigned char*, const float*) = {
         {det_loss_fwd_kernel<false, false, false>, det_loss_fwd_kernel<false, false, true>},
         {det_loss_fwd_kernel<true, false, false>, det_loss_fwd_kernel<true, false, true>},
         {det_loss_fwd_kernel<true, true, false>, det_loss_fwd_kernel<true, true, true>}};
     const int blocks = hn_det_loss_blocks(A);
     hipLaunchKernelGGL(kernels[!reg_kind ? 0 : !cls_kind ? 1 : 2][assign_given], dim3(blocks, N), dim3(256), 0, st, cls, reg, anchors, ann, A, K,
-                       Mx, reg_kind, cls_kind, (short*)assign, part, valid);
+                       Mx, reg_kind, cls_kind, (short*)assign, part, valid, target);
     if (reg_kind) hipLaunchKernelGGL((det_loss_finalize_kernel<4, 1>), dim3(1), dim3(1024), 0, st, part, blocks, N, npos, out, valid);
     else hipLaunchKernelGGL((det_loss_finalize_kernel<3, 4>), dim3(1), dim3(1024), 0, st, part, blocks, N, npos, out, valid);
     HN_LAUNCH_CHECK();
@@ -352,15 +285,15 @@ static int det_loss_fwd(const float* cls, const float* reg, const float* anchors
 
 static int det_loss_bwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
                         int reg_kind, int cls_kind, const unsigned char* valid, const void* assign, const float* npos, const float* gout,
-                        float* dcls, float* dreg, hipStream_t st) {
+                        float* dcls, float* dreg, hipStream_t st, const float* target = nullptr) {
     HN_CHECK_ARG(cls && reg && anchors && ann && assign && npos && gout && dcls && dreg && N > 0 && A > 0 && K > 0 && Mx > 0);
     HN_CHECK_ARG(K <= HN_DET_MAXK);                                     // 256 x K floats of LDS
     HN_CHECK_ARG(reg_kind >= 0 && reg_kind <= 3 && cls_kind >= 0 && cls_kind <= (reg_kind ? 2 : 0));
     static void (*const kernels[3])(const float*, const float*, const float*, const float*, int, int, int, int, int, int, const short*,
-                                    const float*, const float*, float*, float*, const unsigned char*) = {
+                                    const float*, const float*, float*, float*, const unsigned char*, const float*) = {
         det_loss_bwd_kernel<false, false>, det_loss_bwd_kernel<true, false>, det_loss_bwd_kernel<true, true>};
     hipLaunchKernelGGL(kernels[!reg_kind ? 0 : !cls_kind ? 1 : 2], dim3(hn_det_loss_blocks(A), N), dim3(256), 256 * (size_t)K * sizeof(float), st,
-                       cls, reg, anchors, ann, N, A, K, Mx, reg_kind, cls_kind, (const short*)assign, npos, gout, dcls, dreg, valid);
+                       cls, reg, anchors, ann, N, A, K, Mx, reg_kind, cls_kind, (const short*)assign, npos, gout, dcls, dreg, valid, target);
     HN_LAUNCH_CHECK();
 }
 
@@ -444,4 +377,19 @@ extern "C" int hn_det_loss_quality_bwd(const float* cls, const float* reg, const
                                        const float* gout, float* dcls, float* dreg, hipStream_t st) {
     HN_CHECK_ARG(kind >= 1 && cls_kind >= 1);
     return det_loss_bwd(cls, reg, anchors, ann, N, A, K, Mx, kind, cls_kind, valid, assign, npos, gout, dcls, dreg, st);
+}
+
+// the quality pair with the positives' classification target handed in (hn_det_tal_assign's aligned target, read with its assignment):
+// y = target[n][a] for a positive anchor in the forward and in the backward; the regression term, out[2], npos and dreg do not read it
+extern "C" int hn_det_loss_aligned_fwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                                       int kind, int cls_kind, const unsigned char* valid, int assign_given, void* assign, const float* target,
+                                       float* part, float* npos, float* out, hipStream_t st) {
+    HN_CHECK_ARG(kind >= 1 && cls_kind >= 1 && target && assign_given == 1);     // a target belongs to a given assignment
+    return det_loss_fwd(cls, reg, anchors, ann, N, A, K, Mx, kind, cls_kind, valid, 1, assign, part, npos, out, st, target);
+}
+extern "C" int hn_det_loss_aligned_bwd(const float* cls, const float* reg, const float* anchors, const float* ann, int N, int A, int K, int Mx,
+                                       int kind, int cls_kind, const unsigned char* valid, const void* assign, const float* target,
+                                       const float* npos, const float* gout, float* dcls, float* dreg, hipStream_t st) {
+    HN_CHECK_ARG(kind >= 1 && cls_kind >= 1 && target);
+    return det_loss_bwd(cls, reg, anchors, ann, N, A, K, Mx, kind, cls_kind, valid, assign, npos, gout, dcls, dreg, st, target);
 }

@@ -158,13 +158,19 @@ class HydraNet(nn.Module):
                 self.loss_detect = functools.partial(K.det_iou_loss_hip, kind=self.loss_reg_type, cls_kind=self.loss_cls_type)
             # detection.assigner: which anchors are positive.  max_iou (or no key) is the reference's fixed rule (IoU >= 0.5 positive, < 0.4
             # background, between ignored), computed inside the loss forward; atss picks per box the atss_topk nearest locations of every
-            # level and thresholds their IoUs at mean + std (ops/losses.py det_atss_assign).  Works with every loss_reg_type.  HIP only.
+            # level and thresholds their IoUs at mean + std (ops/losses.py det_atss_assign); tal (task-aligned, TOOD) picks per box the
+            # tal_topk anchors whose own prediction is best at both tasks, by score * IoU^6, and hands qfl / vfl its normalised alignment
+            # target in place of the raw IoU (ops/losses.py det_tal_assign).  Each works with every loss_reg_type and loss_cls_type.
+            # HIP only.
             self.det_assigner = cfgs["detection"].get("assigner", "max_iou")
-            if self.det_assigner not in ("max_iou", "atss"):
-                raise ValueError("detection.assigner must be one of 'max_iou', 'atss', got %r" % (self.det_assigner,))
+            if self.det_assigner not in ("max_iou", "atss", "tal"):
+                raise ValueError("detection.assigner must be one of 'max_iou', 'atss', 'tal', got %r" % (self.det_assigner,))
             self.atss_topk = cfgs["detection"].get("atss_topk", 9)
             if isinstance(self.atss_topk, bool) or not isinstance(self.atss_topk, int) or self.atss_topk < 1:
                 raise ValueError("detection.atss_topk must be an integer >= 1, got %r" % (self.atss_topk,))
+            self.tal_topk = cfgs["detection"].get("tal_topk", 13)
+            if isinstance(self.tal_topk, bool) or not isinstance(self.tal_topk, int) or self.tal_topk < 1:
+                raise ValueError("detection.tal_topk must be an integer >= 1, got %r" % (self.tal_topk,))
         else:
             self.detectheader, self.loss_detect = None, None
         if self.train_seg:
@@ -950,6 +956,11 @@ class HydraNet(nn.Module):
                                               self.anchors_per_location)
                 cl, rl, *iou = self.loss_detect(d["classification"], d["regression"], d["anchors"], gt_dict["gt_det"], assign=assign,
                                                 **tv.get("det", {}))
+            elif self.det_assigner == "tal":
+                assign, target = K.det_tal_assign(d["anchors"], d["regression"], d["classification"], gt_dict["gt_det"], self.tal_topk)
+                aligned = {} if self.loss_cls_type == "focal" else {"target": target}      # (the focal term's target stays 0 / 1)
+                cl, rl, *iou = self.loss_detect(d["classification"], d["regression"], d["anchors"], gt_dict["gt_det"], assign=assign,
+                                                **aligned, **tv.get("det", {}))
             else:
                 cl, rl, *iou = self.loss_detect(d["classification"], d["regression"], d["anchors"], gt_dict["gt_det"], **tv.get("det", {}))
             self.det_pos_iou = iou[0].detach().reshape(()) if iou else None      # (IoU types only: the positives' mean IoU, a device scalar)

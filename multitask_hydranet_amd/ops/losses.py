@@ -212,11 +212,13 @@ DET_IOU_KINDS = {"giou": 1, "diou": 2, "ciou": 3}
 DET_CLS_KINDS = {"focal": 0, "qfl": 1, "vfl": 2}
 
 
-def _det_entry(which, reg_kind, cls_kind, given, valid):
+def _det_entry(which, reg_kind, cls_kind, given, valid, aligned=False):
     """(entry-point name, the arguments between Mx and the buffers) of the detection loss's forward (which = "fwd") or backward ("bwd")
-    for reg_kind 0 (smooth-L1) | DET_IOU_KINDS, cls_kind of DET_CLS_KINDS, an assignment handed in or not, a mask row or None"""
+    for reg_kind 0 (smooth-L1) | DET_IOU_KINDS, cls_kind of DET_CLS_KINDS, an assignment handed in or not, a mask row or None; aligned:
+    the quality pair that reads a target after the assignment"""
     if cls_kind:       # one pair of names takes the mask and the given assignment as (nullable) arguments
-        return f"hn_det_loss_quality_{which}", (reg_kind, cls_kind, ptr(valid)) + ((int(given),) if which == "fwd" else ())
+        name = "hn_det_loss_aligned_" if aligned else "hn_det_loss_quality_"
+        return name + which, (reg_kind, cls_kind, ptr(valid)) + ((int(given),) if which == "fwd" else ())
     name = ("hn_det_loss_iou_" if reg_kind else "hn_det_loss_") + which + ("_assigned" if given and which == "fwd" else "")
     return _masked(name, valid), ((reg_kind,) if reg_kind else ()) + tuple(_v(valid))
 
@@ -227,7 +229,7 @@ class DetLoss(torch.autograd.Function):
     diagnostic and not differentiable."""
 
     @staticmethod
-    def forward(ctx, cls, reg, anchors, ann, reg_kind=0, cls_kind=0, given=None, valid=None):
+    def forward(ctx, cls, reg, anchors, ann, reg_kind=0, cls_kind=0, given=None, valid=None, target=None):
         n, a, k = cls.shape
         mx = ann.shape[1]
         dev = cls.device
@@ -239,10 +241,13 @@ class DetLoss(torch.autograd.Function):
         npos = torch.empty((n,), device=dev, dtype=F32)
         out = torch.empty((3 if reg_kind else 2,), device=dev, dtype=F32)
         assign = torch.empty((n, a), device=dev, dtype=torch.int16) if given is None else _given_assign(given, n, a, dev)
-        name, args = _det_entry("fwd", reg_kind, cls_kind, given is not None, valid)
-        lib().call(name, ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, *args, ptr(assign), ptr(part), ptr(npos), ptr(out))
+        if target is not None:
+            target = _given_target(target, given, n, a, dev)
+        tgt = () if target is None else (ptr(target),)
+        name, args = _det_entry("fwd", reg_kind, cls_kind, given is not None, valid, target is not None)
+        lib().call(name, ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, mx, *args, ptr(assign), *tgt, ptr(part), ptr(npos), ptr(out))
         ctx.kinds = (reg_kind, cls_kind)
-        ctx.save_for_backward(cls, reg, anc, ann, assign, npos)
+        ctx.save_for_backward(cls, reg, anc, ann, assign, npos, target)
         # the losses leave as separate outputs (slicing a 2-vector OUTSIDE the node cost two SliceBackward nodes -- fill + copy each -- and
         # an add per step: seven 5 us launches)
         if not reg_kind:
@@ -254,8 +259,9 @@ class DetLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gcls, greg, _giou=None):
-        cls, reg, anc, ann, assign, npos = ctx.saved_tensors
+        cls, reg, anc, ann, assign, npos, target = ctx.saved_tensors
         n, a, k = cls.shape
+        tgt = () if target is None else (ptr(target),)
         dcls, dreg = torch.empty_like(cls), torch.empty_like(reg)
         if (gcls is not None and greg is not None and gcls.dtype == F32 and greg.dtype == F32
                 and greg.data_ptr() == gcls.data_ptr() + 4):       # neighbours in WeightedLossSum.backward's gradient vector: used in place
@@ -263,10 +269,10 @@ class DetLoss(torch.autograd.Function):
         else:
             z = zeros((1,), cls.device)
             g = torch.cat([(gcls if gcls is not None else z).reshape(1).to(F32), (greg if greg is not None else z).reshape(1).to(F32)])
-        name, args = _det_entry("bwd", *ctx.kinds, False, ctx.valid)
-        lib().call(name, ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, ann.shape[1], *args, ptr(assign), ptr(npos), ptr(g), ptr(dcls),
+        name, args = _det_entry("bwd", *ctx.kinds, False, ctx.valid, target is not None)
+        lib().call(name, ptr(cls), ptr(reg), ptr(anc), ptr(ann), n, a, k, ann.shape[1], *args, ptr(assign), *tgt, ptr(npos), ptr(g), ptr(dcls),
                    ptr(dreg))
-        return dcls, dreg, None, None, None, None, None, None
+        return dcls, dreg, None, None, None, None, None, None, None
 
 
 def _given_assign(assign, n, a, dev):
@@ -274,6 +280,15 @@ def _given_assign(assign, n, a, dev):
     if assign.dtype != torch.int16 or tuple(assign.shape) != (n, a) or assign.device != dev:
         raise ValueError(f"assign must be an int16 [{n}, {a}] tensor on {dev}, got {assign.dtype} {tuple(assign.shape)} on {assign.device}")
     return assign.contiguous()
+
+
+def _given_target(target, assign, n, a, dev):
+    """a classification target handed to a quality loss next to its assignment: fp32 [N, A] on the loss's device"""
+    if assign is None:
+        raise ValueError("target belongs to a given assignment: pass assign as well (det_tal_assign returns both)")
+    if target.dtype != F32 or tuple(target.shape) != (n, a) or target.device != dev:
+        raise ValueError(f"target must be an fp32 [{n}, {a}] tensor on {dev}, got {target.dtype} {tuple(target.shape)} on {target.device}")
+    return target.detach().contiguous()
 
 
 def det_loss_hip(classification, regression, anchors, annotations, assign=None, valid=None):
@@ -324,7 +339,53 @@ def det_atss_assign(anchors, level_sizes, annotations, topk=9, anchors_per_locat
     return assign, thr
 
 
-def det_iou_loss_hip(classification, regression, anchors, annotations, kind, assign=None, valid=None, cls_kind="focal"):
+def det_tal_assign(anchors, regression, classification, annotations, topk=13):
+    """Task-aligned anchor assignment (TAL; Feng et al., TOOD, 2021) on HIP kernels (hn_det_tal.hip, three launches, no host
+    synchronisation, capturable).  anchors [A, 4] or [1, A, 4] fp32 (y1, x1, y2, x2); regression [N, A, 4] fp32 (dy, dx, dh, dw);
+    classification [N, A, K] fp32, post-sigmoid; annotations [N, Mx, 5] (x1, y1, x2, y2, class), class -1 marks padding.  Both
+    predictions are detached and read as constants: no gradient flows through the assigner.  Returns (assign int16 [N, A]: the matched
+    annotation's index or -1, target fp32 [N, A]: the aligned classification target of an assigned anchor, else 0), which
+    det_iou_loss_hip(..., assign=, target=) reads.  alpha = 1 and beta = 6 are fixed.
+
+    The rule, per image, with k = topk:
+      1. An image without valid annotations has every anchor -1 and every target 0.
+      2. u(a, j) is the `iou` of det_iou_loss_hip's box function for anchor a's regression against box j: the deploy decode with the
+         log(1000/16) clip on dh and dw, target sides clamped to at least 1, eps 1e-7 (the same device function on the same inputs as
+         the loss).
+      3. s(a, j) = classification[a, class_j], unclamped.  A class id outside 0 .. K - 1 gives s = 0.
+      4. t(a, j) = s * ((u*u)*(u*u)) * (u*u) in fp32.
+      5. Anchor a is eligible for box j when its centre lies inside the raw annotation by more than 0.01 px (ATSS's rule 8:
+         min(acx - x1, acy - y1, x2 - acx, y2 - acy) > 0.01) and t > 0.  A NaN or zero metric is never eligible; a NaN anywhere in the
+         anchor's regression makes its t NaN.
+      6. The candidates of box j are its k eligible anchors with the largest (t, then lower anchor index); all of them if fewer than k
+         are eligible.
+      7. An anchor that is a candidate of several boxes goes to the box with the largest u.  Ties go to the lowest annotation index.
+      8. Every other anchor is -1.  There is no ignore zone: -2 never appears.
+      9. For box j, tmax and umax are the maxima of t and u over the anchors finally assigned to j, after rule 7.  The target of an
+         assigned anchor is (t / tmax) * umax, both operations individually rounded.  Every other anchor's target is 0.
+    Padding rows are never read."""
+    anc = anchors.detach().reshape(-1, 4).contiguous()
+    reg = regression.detach().contiguous()
+    cls = classification.detach().contiguous()
+    ann = annotations.detach().contiguous().float()
+    if anc.dtype != F32 or ann.dim() != 3 or ann.shape[2] != 5:
+        raise ValueError("anchors must be fp32 [A, 4] and annotations [N, Mx, 5]")
+    n, mx, a, dev = ann.shape[0], ann.shape[1], anc.shape[0], anc.device
+    if reg.dtype != F32 or tuple(reg.shape) != (n, a, 4) or cls.dtype != F32 or cls.dim() != 3 or tuple(cls.shape[:2]) != (n, a):
+        raise ValueError(f"regression must be fp32 [{n}, {a}, 4] and classification fp32 [{n}, {a}, K], got {reg.dtype} {tuple(reg.shape)} "
+                         f"and {cls.dtype} {tuple(cls.shape)}")
+    nbytes = lib().query("hn_det_tal_ws_bytes", n, a, mx, int(topk))
+    if nbytes < 0:
+        raise ValueError(f"det_tal_assign: needs 1 <= N <= 65535, 1 <= Mx <= 32767, A >= 1 and 1 <= topk <= 2048, got N = {n}, Mx = {mx}, "
+                         f"A = {a}, topk = {topk}")
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    assign = torch.empty((n, a), device=dev, dtype=torch.int16)
+    target = torch.empty((n, a), device=dev, dtype=F32)
+    lib().call("hn_det_tal_assign", ptr(anc), ptr(reg), ptr(cls), ptr(ann), n, a, cls.shape[2], mx, int(topk), ptr(ws), ptr(assign), ptr(target))
+    return assign, target
+
+
+def det_iou_loss_hip(classification, regression, anchors, annotations, kind, assign=None, valid=None, cls_kind="focal", target=None):
     """The detection loss with its regression term replaced by an IoU-family loss; kind = "giou" | "diou" | "ciou".  Returns
     (classification loss [1], regression loss [1], pos_iou [1]).  Anchor assignment (IoU >= 0.5 positive, < 0.4 background, between
     ignored, first maximum wins, an image without boxes all background) and the focal classification loss are det_loss_hip's, bit for
@@ -366,11 +427,19 @@ def det_iou_loss_hip(classification, regression, anchors, annotations, kind, ass
                       dl/dp = 0.75 (-2 p ln(1 - p) + p^2 / (1 - p))
 
     Per image the sum of l over counted anchors and classes is divided by max(npos, 1); the output is the mean over the images (over
-    the labelled images under a mask, 0 without any): the focal term's reduction.  beta, alpha and gamma are fixed."""
+    the labelled images under a mask, 0 without any): the focal term's reduction.  beta, alpha and gamma are fixed.
+
+    target: None, or with cls_kind "qfl" / "vfl" and an assign an fp32 [N, A] tensor (det_tal_assign's): a positive anchor's y is
+    target[n, a] instead of q, a constant in the forward and in the backward (hn_det_loss_aligned_fwd / _bwd).  The regression loss,
+    pos_iou and the regression gradient do not read it."""
     if kind not in DET_IOU_KINDS:
         raise ValueError(f"kind must be one of {sorted(DET_IOU_KINDS)}, got {kind!r}")
     if cls_kind not in DET_CLS_KINDS:
         raise ValueError(f"cls_kind must be one of {sorted(DET_CLS_KINDS)}, got {cls_kind!r}")
+    if target is not None:
+        if cls_kind == "focal":
+            raise ValueError("target needs cls_kind 'qfl' or 'vfl': the focal term's target is 0 / 1")
+        return DetLoss.apply(classification, regression, anchors, annotations, DET_IOU_KINDS[kind], DET_CLS_KINDS[cls_kind], assign, valid, target)
     if cls_kind == "focal" and assign is None and valid is None:
         return DetLoss.apply(classification, regression, anchors, annotations, DET_IOU_KINDS[kind])
     return DetLoss.apply(classification, regression, anchors, annotations, DET_IOU_KINDS[kind], DET_CLS_KINDS[cls_kind], assign, valid)
