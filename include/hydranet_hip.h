@@ -587,6 +587,19 @@ int hn_lane_loc_loss_fwd(const float* pred, const float* target, const void* pma
                          float* rowloss, float* rownorm, float* out, hipStream_t stream);
 int hn_lane_loc_loss_bwd(const float* pred, const float* target, const void* pmask, const float* rownorm, const float* aux,
                          const float* gout, long M, int L, int wcol, float alpha, float* dpred, hipStream_t stream);
+/* Lane line-IoU location loss (lane.loss_loc_type: liou; CLRNet, CVPR 2022, section 3.4; DESIGN 4y) in place of the loc pair above.
+ * pred / target fp32 [M][L] with L = 2 P + 2 (else 1): x-offsets at columns [0, P) and [P + 2, L), the two lengths at P and P + 1; a column
+ * is valid iff target != 0.  e > 0 (finite, else 1) is the half width in target units.  Per positive row with n valid x-columns and
+ * d = |pred - target|: I = sum (2e - d), U = sum (2e + d), term 1 - I / U (0 when n = 0), plus the loc loss's own term of the two length
+ * columns (x`alpha` huber over nrm = max(#valid columns of the row, 1)).  out[0] = the sum over the positive rows / aux[1], out[1] = the
+ * mean I / U over the positive rows with n > 0 (0 without one).  rowI, rowU, rownorm, rowloss: fp32 [M] workspace, all written for every
+ * row (I = U = 0 on a row that is not positive); bwd reads rowU and rownorm and writes all of dpred [M][L], exactly 0 at invalid columns
+ * and on rows that are not positive.  pmask / aux as left by hn_lane_cls_loss_fwd or its _masked twin, which already carry a task mask.
+ * Two launches forward, one backward; no atomics (two runs give the same bits). */
+int hn_lane_liou_loss_fwd(const float* pred, const float* target, const void* pmask, const float* aux, long M, int L, int P, float e,
+                          float alpha, float* rowI, float* rowU, float* rownorm, float* rowloss, float* out, hipStream_t stream);
+int hn_lane_liou_loss_bwd(const float* pred, const float* target, const void* pmask, const float* rowU, const float* rownorm,
+                          const float* aux, const float* gout, long M, int L, int P, float e, float alpha, float* dpred, hipStream_t stream);
 /* Per-image task masks (gt_dict["task_valid"], DESIGN 4u): every loss entry point above has a `_masked` twin that also takes `valid`, one
  * contiguous uint8 row of N bytes on the device (1 = image n is labelled for the task; NULL returns 1 before any launch).  The rule: the
  * losses equal the unmasked losses of the sub-batch of labelled images, taken in batch order; without a labelled image every loss is 0;

@@ -170,6 +170,18 @@ __device__ __forceinline__ float wave_sum(float v) {
            (__builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)) + __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48)));
 }
 
+// sum over a block of up to 1024 threads (a multiple of 64; all threads call it and all get the total): wave sums, then the waves left
+// to right through LDS.  red: >= 16 floats of LDS; calls in a row may share it (a call's first barrier follows every read of the last).
+__device__ __forceinline__ float block_sum_1024(float v, float* red) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float t = 0.f;
+    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += red[i];
+    return t;
+}
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // Opt-in for more than 64 KiB of dynamic LDS.  The attribute is per (kernel, device): `done` is one bit per device id, set after every

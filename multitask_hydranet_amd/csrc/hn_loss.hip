@@ -692,15 +692,6 @@ __device__ __forceinline__ float ord2f(unsigned int o) {
     const unsigned int u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
     return __uint_as_float(u);
 }
-__device__ __forceinline__ float block_sum_1024(float v, float* red) {  // red: >= 16 floats of LDS; all threads get the total
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.f;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += red[i];
-    return t;
-}
 // k-th element's bin of a 256-bin LDS histogram, found by all threads together: thread b < 256 takes bin b, an inclusive prefix sum runs
 // inside each of the four waves (shuffles) and across them (LDS), and the one thread whose bin satisfies excl < k <= incl publishes
 // (bin, k - excl).  (One thread walking the 256 bins was ~10 us per radix pass: 256 dependent LDS reads.)  All 1024 threads call it.

@@ -129,6 +129,7 @@ class HydraNet(nn.Module):
         self.levels_on_streams = False      # hipGraph branches cost more than they hide on gfx950 (55 vs 43 ms)
         self.grad_scope = None              # "lane" | "det" | "seg": head-only fine-tuning phase (see _forward)
         self.det_pos_iou = None             # mean IoU of the positive anchors at the last cal_loss under an IoU loss_reg_type (device scalar)
+        self.lane_pos_liou = None           # mean line IoU of the positive lane anchors at the last cal_loss under lane.loss_loc_type: liou
 
         spec = _Spec(self)
         self._declare_backbone(spec)
@@ -186,6 +187,19 @@ class HydraNet(nn.Module):
         if self.train_lane:
             self._declare_lane(spec)
             self.loss_cls, self.loss_reg = K.lane_cls_loss_hip, K.lane_loc_loss_hip      # HIP; losses.py keeps the torch forms as test references
+            # lane.loss_loc_type: the location term of the positive anchors.  smooth_l1 (or no key) is the reference's per-point loss; liou
+            # regresses a row's valid x-offsets as one thick line, the overlap measure lane F1 is made of (ops/losses.py
+            # lane_liou_loss_hip).  lane.liou_half_width is the line's half width in input pixels; gt_loc carries its offsets in intervals
+            # under lane.scale_invariance (the encoder divides them by lane.interval), so the half width is divided likewise.  HIP only.
+            self.lane_loc_type = cfgs["lane"].get("loss_loc_type", "smooth_l1")
+            if self.lane_loc_type == "liou":
+                e = K.lane_liou_half_width(cfgs["lane"].get("liou_half_width", 15))
+                if cfgs["lane"]["scale_invariance"]:
+                    e = K.lane_liou_half_width(e / float(cfgs["lane"]["interval"]))
+                self.lane_liou_half_width = e                      # in the units of gt_loc
+                self.loss_reg = functools.partial(K.lane_liou_loss_hip, half_width=e)
+            elif self.lane_loc_type != "smooth_l1":
+                raise ValueError("lane.loss_loc_type must be one of 'smooth_l1', 'liou', got %r" % (self.lane_loc_type,))
         else:
             self.laneheader, self.loss_cls, self.loss_reg = None, None, None
         self._bind_callables()
@@ -975,8 +989,13 @@ class HydraNet(nn.Module):
                 pc = pred_dict["lane"]["predict_cls"]
                 lkw = dict(tv["lane"], rows_per_image=pc.numel() // 2 // pc.shape[0])
             pos, neg, pmask, pnum = self.loss_cls(gt_dict["gt_cls"], pred_dict["lane"]["predict_cls"], **lkw)
-            loc = self.loss_reg(pmask, pnum, gt_dict["gt_loc"], pred_dict["lane"]["predict_loc"],
-                                points_per_line=self.lane_points_per_line, **lkw)
+            if self.lane_loc_type == "liou":            # (P from the row length: lane_points_per_line is the smooth-L1 weights' column)
+                loc, liou = self.loss_reg(pmask, pnum, gt_dict["gt_loc"], pred_dict["lane"]["predict_loc"], **lkw)
+                self.lane_pos_liou = liou.detach().reshape(())      # the positives' mean line IoU, a device scalar
+            else:
+                loc = self.loss_reg(pmask, pnum, gt_dict["gt_loc"], pred_dict["lane"]["predict_loc"],
+                                    points_per_line=self.lane_points_per_line, **lkw)
+                self.lane_pos_liou = None
             self._guard(pos, "cal lane pos loss diverge!", allow_zero=masked)
             self._guard(neg, "cal lane neg loss diverge!", allow_zero=masked)
             self._guard(loc, "cal lane loc loss diverge!", allow_zero=masked)

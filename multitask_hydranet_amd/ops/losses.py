@@ -555,6 +555,70 @@ def lane_loc_loss_hip(pmask, positive_num, loc_targets, loc_preds, alpha=10.0, p
     return LaneLocLoss.apply(pmask, positive_num, loc_targets, loc_preds, points_per_line, alpha)
 
 
+class LaneLIoULoss(torch.autograd.Function):
+    """The line-IoU location loss of hn_lane_liou.hip: (loss, mean line IoU of the positive rows), the second a diagnostic and not
+    differentiable.  Two launches forward, one backward, as LaneLocLoss."""
+
+    @staticmethod
+    def forward(ctx, pmask, aux, loc_targets, loc_preds, ppl, e, alpha):
+        L = loc_preds.shape[-1]
+        p = loc_preds.reshape(-1, L).float().contiguous()
+        t = loc_targets.reshape(-1, L).float().contiguous()
+        m = p.shape[0]
+        dev = p.device
+        rows = torch.empty((4, m), device=dev, dtype=F32)            # I, U, normaliser, loss of every row
+        out = torch.empty((2,), device=dev, dtype=F32)
+        lib().call("hn_lane_liou_loss_fwd", ptr(p), ptr(t), ptr(pmask), ptr(aux), m, L, int(ppl), float(e), float(alpha), ptr(rows[0]),
+                   ptr(rows[1]), ptr(rows[2]), ptr(rows[3]), ptr(out))
+        ctx.meta = (int(ppl), float(e), float(alpha), loc_preds.shape)
+        ctx.save_for_backward(p, t, pmask, rows, aux)
+        pos_liou = out[1]
+        ctx.mark_non_differentiable(pos_liou)
+        ctx.set_materialize_grads(False)        # (no zero-filled "gradient" of the diagnostic: a fill launch per step)
+        return out[0], pos_liou
+
+    @staticmethod
+    def backward(ctx, gout, _gliou=None):
+        if gout is None:
+            return None, None, None, None, None, None, None
+        p, t, pmask, rows, aux = ctx.saved_tensors
+        ppl, e, alpha, shape = ctx.meta
+        m, L = p.shape
+        dp = torch.empty((m, L), device=p.device, dtype=F32)
+        g = gout.reshape(1).to(F32)
+        lib().call("hn_lane_liou_loss_bwd", ptr(p), ptr(t), ptr(pmask), ptr(rows[1]), ptr(rows[2]), ptr(aux), ptr(g), m, L, ppl, e, alpha, ptr(dp))
+        return None, None, None, dp.view(shape), None, None, None
+
+
+def lane_liou_half_width(half_width):
+    """the half width of a line-IoU loss as a float; ValueError unless it is a finite number > 0"""
+    if isinstance(half_width, bool) or not isinstance(half_width, (int, float)) or not (0.0 < float(half_width) < float("inf")):
+        raise ValueError(f"the line-IoU half width must be a finite number > 0, got {half_width!r}")
+    return float(half_width)
+
+
+def lane_liou_loss_hip(pmask, positive_num, loc_targets, loc_preds, half_width, alpha=10.0, points_per_line=None, valid=None, rows_per_image=None):
+    """Line-IoU location loss (CLRNet, section 3.4; hn_lane_liou.hip) in place of lane_loc_loss_hip: every positive row's valid
+    x-offsets are regressed as ONE thick line, 1 - sum(2e - |p - t|) / sum(2e + |p - t|) with e = half_width in the units of loc_targets,
+    and its two lengths keep the smooth-L1 term (x alpha over the row's valid-column count).  -> (loss, pos_liou): pos_liou, the mean
+    line IoU of the positive rows with a valid x-offset, is a detached device scalar.  points_per_line: P of the [.., 2 P + 2] rows
+    (default: from the row length).  valid / rows_per_image: as for lane_loc_loss_hip (pmask / positive_num carry the mask)."""
+    e = lane_liou_half_width(half_width)
+    L = loc_preds.shape[-1]
+    ppl = (L - 2) // 2 if points_per_line is None else int(points_per_line)
+    if ppl < 1 or L != 2 * ppl + 2:
+        raise ValueError(f"line-IoU rows have 2 * points_per_line + 2 columns: got {L} columns for points_per_line = {ppl}")
+    if tuple(loc_targets.shape) != tuple(loc_preds.shape):
+        raise ValueError(f"loc_targets {tuple(loc_targets.shape)} and loc_preds {tuple(loc_preds.shape)} differ in shape")
+    if valid is not None:
+        m = loc_preds.numel() // L
+        rows = _lane_rows(valid, rows_per_image, m)
+        if rows < 1 or m % rows:
+            raise ValueError(f"rows_per_image = {rows} does not divide the {m} lane rows")
+        _task_valid_row(valid, m // rows, loc_preds.device)
+    return LaneLIoULoss.apply(pmask, positive_num, loc_targets, loc_preds, ppl, e, alpha)
+
+
 # --------------------------------------------------------------------------------------------------------------
 # HydraTrainer.cal_total_loss (model/train.py:192-203) as one launch forward and one backward instead of ~22 scalar torch kernels.
 # --------------------------------------------------------------------------------------------------------------
