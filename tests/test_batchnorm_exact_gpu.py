@@ -10,21 +10,19 @@ E. shapes and edges: C from 8 to 2048 (ragged 128-channel chunks, C8 = 256), M f
 F. accuracy at large per-channel offsets (E[z^2] - mean^2 from fp32 partial sums).
 Every output lives between sentinel guard bands (tests/guards.py); a mismatch names the pass, the channel and the row block."""
 import ctypes
-import zlib
 
 import pytest
 import torch
 
 from tests import bn_ref as B
+from tests import exact_checks as X
+from tests.exact_checks import BF16, F32, F64, U, EXACT_LIMIT, D, gen, gpu_bf16, exact, within, bf_interval, slack_fwd
 from tests.guards import Guarded, dev
 
 pytestmark = pytest.mark.gpu
 
-BF16, F32, F64 = torch.bfloat16, torch.float32, torch.float64
-U = 2.0 ** -24                 # fp32 unit roundoff
 FIN_ULPS = 4                   # finalize outputs: |err| <= FIN_ULPS * U * (the magnitudes the fp32 expression combines)
 SHIFT_ULPS = 2 * FIN_ULPS      # shift = beta - mean * scale also carries the error of scale
-EXACT_LIMIT = 1 << 24
 
 
 @pytest.fixture(scope="module")
@@ -37,45 +35,15 @@ def K():
     return ops
 
 
-_LIVE = []
-
-
 @pytest.fixture(autouse=True)
 def _release():
     yield
-    if _LIVE:
-        torch.cuda.synchronize()
-        _LIVE.clear()
-
-
-def D(t):
-    """t on the GPU, kept alive until the test ends (a temporary whose data_ptr() is passed to a launch could be freed, and its block
-    handed to the next allocation, before the kernel runs)"""
-    t = t.to(dev())
-    _LIVE.append(t)
-    return t
-
-
-def gen(name):
-    g = torch.Generator()
-    g.manual_seed(zlib.crc32(name.encode()) & 0xFFFFFF)
-    return g
+    X.release()
 
 
 def f32(x):
     """the fp32 value a float argument becomes at the C boundary, as a Python float"""
     return float(torch.tensor(x, dtype=F32))
-
-
-def gpu_bf16(v, width=None):
-    """float64 CPU values (bf16-representable) -> bf16 [M, C] on the GPU; width > C: a channel slice of a wider buffer whose other
-    columns hold unrelated values"""
-    m, c = v.shape
-    if width and width > c:
-        full = torch.full((m, width), 3.0, dtype=F64)
-        full[:, :c] = v
-        return full.to(BF16).to(dev())[:, :c]
-    return v.to(BF16).to(dev())
 
 
 def ints(m, c, lo, hi, g):
@@ -88,63 +56,6 @@ def ldof(t):
 
 def call(K, name, *args):
     K.lib().call(name, *args)
-
-
-def rows_blame(rb):
-    return lambda r: f"row block {r // rb} (rows {r // rb * rb}..{r // rb * rb + rb - 1})" if rb else ""
-
-
-def exact(got, want, name, what="partial row"):
-    """fp32 [P, C] == float64 bit for bit; a mismatch names the partial row (row block) and channel"""
-    g = got.detach().double().cpu()
-    bad = ~(g == want)
-    n = int(bad.sum())
-    if n:
-        idx = bad.nonzero()[:6].tolist()
-        lines = [f"  {what} {r}, channel {c}: got {float(g[r, c])!r} want {float(want[r, c])!r}" for r, c in idx]
-        pytest.fail(f"{name}: {n} of {g.numel()} values differ\n" + "\n".join(lines))
-
-
-def within(got, want, bound, name, what="channel"):
-    """|got - want| <= bound elementwise (1-D per-channel vectors or [rows, C])"""
-    g = got.detach().double().cpu()
-    err = (g - want).abs()
-    bad = ~(err <= bound)
-    n = int(bad.sum())
-    if n:
-        idx = bad.nonzero()[:6].tolist()
-        lines = []
-        for ii in idx:
-            t = tuple(ii)
-            lines.append(f"  {what} {t[0] if len(t) == 1 else t}: got {float(g[t])!r} want {float(want[t])!r} "
-                         f"(err {float(err[t]):.3e} > bound {float(bound[t] if torch.is_tensor(bound) else bound):.3e})")
-        pytest.fail(f"{name}: {n} of {g.numel()} values outside the bound\n" + "\n".join(lines))
-
-
-def bf_interval(got, y, s, name, rb=None):
-    """every bf16 value of got [M, C] must be the bf16 rounding of some value in [y - s, y + s] (rounding is monotone: the set is the bf16
-    values between the roundings of the two ends).  Names channel and row block of the first failures."""
-    s = s + 2 * U * y.abs() + 1e-38                     # (the ends pass through fp32 on their way to bf16)
-    lo = (y - s).float().to(BF16).double()
-    hi = (y + s).float().to(BF16).double()
-    g = got.detach().double().cpu()
-    bad = ~((g >= lo) & (g <= hi))
-    n = int(bad.sum())
-    if n:
-        idx = bad.nonzero()[:6].tolist()
-        blame = rows_blame(rb)
-        lines = [f"  row {r} {blame(r)}, channel {c}: got {float(g[r, c])!r}, allowed [{float(lo[r, c])!r}, {float(hi[r, c])!r}] "
-                 f"(float64 value {float(y[r, c])!r})" for r, c in idx]
-        pytest.fail(f"{name}: {n} of {g.numel()} bf16 outputs outside their interval\n" + "\n".join(lines))
-
-
-def slack_fwd(x, y, mags, act):
-    """fp32 evaluation slack of y = act(x), x = sc*z + sh [+ res terms]: a few ulps of the magnitudes the pre-activation combines, times
-    the activation's slope, plus the error of __expf-based activations (relative (2 + |x|) ulps, absolute for ELU's exp(x) - 1)"""
-    s = 4 * U * mags * B.act_slope(act)
-    if act in (B.ACT_SWISH, B.ACT_ELU, B.ACT_SIGMOID):
-        s = s + 8 * U * (2 + x.abs()) * (y.abs() + 1)
-    return s
 
 
 def coef_of(cf):
