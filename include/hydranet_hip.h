@@ -267,7 +267,8 @@ int hn_conv3x3_phase(const void* x0, int mode, int n_img, int H, int W, int C0, 
                      int act, void* out, int ldc, int k, const void* addend, int ld_add, hipStream_t stream);
 /* deploy forward of the seg head's output layer: Conv3x3(ReflectionPad2d(1)(nearest_up2(x0))) (head_seg/segmentation.py:101-104, phase
  * form: w = effective weights [4k][9][KP] from hn_pack_weight_ex, bias [4k]) fused with torch.argmax over the k classes
- * (model/model.py:197): mask int64 [N][2H][2W], first maximum wins; the fp32 logits are never written.  C0 <= 64, 4k <= 32. */
+ * (model/model.py:197): mask int64 [N][2H][2W], first maximum wins; the fp32 logits are never written.  C0 <= 64, KP == 64, 4k <= 32,
+ * W * k even (the staged tile's rows of 2 W k floats are whole 16-byte pieces), mask 16-byte aligned; HN_ERR_ARG otherwise. */
 int hn_conv3x3_out_argmax(const void* x0, int n_img, int H, int W, int C0, int ld0, const void* w, int k, int KP, const float* bias, long* mask,
                           hipStream_t stream);
 int hn_wgrad_plan_phase(int n_img, int H, int W, int Nout, int KP, int phase_span, int* splits, long* rows_per_split, long* ws_bytes);

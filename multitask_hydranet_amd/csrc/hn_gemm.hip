@@ -3583,7 +3583,9 @@ extern "C" int hn_conv_gemm_nt_stat(const void* x0, const void* x1, int mode, in
                                     int add_mode, int emode, const void* ez, int ld_ez, const float* ecoef, hipStream_t st) {
     HN_CHECK_ARG((emode == 1 || emode == 2) && psum && (psq || emode == 1) && ez && ecoef && (Nout & 7) == 0 && (ld_ez & 3) == 0 && !out_f32 &&
                  act == HN_ACT_NONE && (mode <= 1 || mode == 5) && (reinterpret_cast<uintptr_t>(ez) & 7) == 0);
-    GemmNT p = nt_conv(x0, x1, mode, H, W, C0, C1, ld0, ld1, up, M, w, Nout, KP, taps, bias, act, out, ldc, rpi, img_stride, psum, psq);
+    // emode 1 has no second row: psq is not written (the kernels store a second row whenever they are given one)
+    GemmNT p = nt_conv(x0, x1, mode, H, W, C0, C1, ld0, ld1, up, M, w, Nout, KP, taps, bias, act, out, ldc, rpi, img_stride, psum,
+                       emode == 1 ? nullptr : psq);
     nt_addend(p, addend, ld_add, add_mode);
     p.emode = emode; p.ez = (const bf16*)ez; p.ld_ez = ld_ez; p.ecoef = ecoef;
     return run_gemm_nt(p, n_img, out_f32, st);

@@ -2,7 +2,9 @@
 wgrad_reduce_kind, wgrad_group_plan, gconv_group_plan, pick_bc, small_tile, launch_direct's tile choice), with the shipped knob values.
 tests/test_gemm_plans_cpu.py holds it to the library's own plan queries and to the instantiations the source launches;
 tests/test_gemm_exact_gpu.py uses it to assert which branch every exact case lands on, and to name the split / patch / tile of a
-mismatching element."""
+mismatching element.  launch_direct's form choice beyond the plain call (phase, depth-to-space, arg-max and fold forms, the two
+persistent seg-head predicates with their patch count and threshold) and the tiling of the plain-row entry points (imgw, lvl, lvlout,
+stat3) serve tests/test_gemm_forms_exact_gpu.py and tests/test_gemm_epilogue_exact_gpu.py in the same way."""
 import os
 import re
 
@@ -192,6 +194,117 @@ def direct_kernel(mode, nout, kp, out_f32, ldc, aligned=True):
 
 def stat_tile(m, nout):
     return 64 if small_tile(m, nout) else 128
+
+
+# ---- launch_direct's form choice beyond the plain call: phase / depth-to-space / arg-max / fold forms, the persistent seg-head kernels --------
+PERSIST_MIN_PATCHES = 1024   # `npatch >= 1024` of both persistent predicates
+ACT_NONE, ACT_ELU = 0, 3
+
+
+def npatch(n, h, w):
+    """16 x 16 output patches of the (low-resolution) grid: what launch_direct compares with the persistent threshold"""
+    return n * cdiv(h, 16) * cdiv(w, 16)
+
+
+def seg_phase64_persistent(n, h, w, nout, kp, c0, act, phase_mode, phase_span, d2s, out_f32=False, addend=False, stats=False, clamp=True,
+                           ld0=None, ldc=64, aligned=True):
+    """the predicate of seg_phase64_conv_kernel (the last decoder block's 64 -> 4 x 64 phase-form conv)"""
+    ld0 = c0 if ld0 is None else ld0
+    return (clamp and not out_f32 and d2s == 64 and phase_mode == 1 and phase_span == 64 and kp == 64 and c0 == 64 and nout == 256
+            and not stats and not addend and act in (ACT_ELU, ACT_NONE) and ld0 % 8 == 0 and ldc % 8 == 0 and ldc >= 64 and aligned
+            and npatch(n, h, w) >= PERSIST_MIN_PATCHES)
+
+
+def seg_out_persistent(n, h, w, nout, kp, c0, act, phase_mode, d2s, out_f32=True, addend=False, stats=False, clamp=True, ld0=None,
+                       aligned=True):
+    """the predicate of seg_out_conv_kernel<amax> (the seg output conv, fp32 depth-to-space logits or their arg-max)"""
+    ld0 = c0 if ld0 is None else ld0
+    return bool(clamp and out_f32 and d2s and kp == 64 and c0 == 64 and nout == 4 * d2s and nout <= 32 and not stats and not addend
+                and phase_mode == 0 and act == ACT_NONE and ld0 % 8 == 0 and (32 * d2s) % 4 == 0 and (2 * w * d2s) % 4 == 0 and aligned
+                and npatch(n, h, w) >= PERSIST_MIN_PATCHES)
+
+
+def persistent_ranges(n, h, w, kernel):
+    """(patches per workgroup, workgroups [per phase for seg_phase64]): seg_phase64 walks 64 patch ranges x 4 phases, seg_out 256 ranges"""
+    npt = npatch(n, h, w)
+    ppw = cdiv(npt, 64 if kernel == "seg_phase64" else 256)
+    return ppw, cdiv(npt, ppw)
+
+
+def direct_form(mode, n, h, w, nout, kp, c0, out_f32, ldc, act=ACT_NONE, phase_mode=0, phase_span=0, d2s=0, amax=False, fold=0,
+                addend=False, stats=False, aligned=True, ld0=None):
+    """the kernel and form launch_direct takes for any direct 3x3 launch.  n, h, w: the grid the kernel runs on (mode 4 phase / d2s forms:
+    the LOW-resolution grid; mode 3: the padded grid).  -> dict(kernel, bc, wpre, persistent) with kernel one of
+    seg_phase64 | seg_out<true|false> | direct<bc,f32|bf16[,wpre][,phase|,dphase][,d2s][,amax][,foldN]> | direct_narrow<64>"""
+    diag = mode == 5
+    clamp = mode == 4
+    if not diag and seg_phase64_persistent(n, h, w, nout, kp, c0, act, phase_mode, phase_span, d2s, out_f32, addend, stats, clamp, ld0, ldc, aligned):
+        return dict(kernel="seg_phase64", bc=64, wpre=False, persistent=True)
+    if not diag and seg_out_persistent(n, h, w, nout, kp, c0, act, phase_mode, d2s, out_f32, addend, stats, clamp, ld0, aligned):
+        return dict(kernel="seg_out<%s>" % ("true" if amax else "false"), bc=32, wpre=False, persistent=True)
+    bc = 64 if diag else (16 if nout <= 16 else (32 if nout <= 32 else (64 if nout <= 64 else 128)))
+    if phase_mode == 1 and phase_span < bc:
+        bc = 64                                               # a cout tile must lie inside one phase
+    staged_ok = ldc % 8 == 0 and nout % 8 == 0 and aligned and (not d2s or (d2s % 8 == 0 and nout % bc == 0))
+    if bc >= 64 and not out_f32 and not staged_ok:
+        assert not diag
+        bc = 32
+    nsteps = 4 if phase_mode else 9
+    wpre = not diag and kp <= 64 and nsteps * bc * 128 <= 32768
+    narrow = bc == 64 and not out_f32 and not diag and not wpre and kp <= 32 and nsteps == 9
+    if narrow:
+        return dict(kernel="direct_narrow<64>", bc=bc, wpre=True, persistent=False)
+    tags = ["f32" if out_f32 else "bf16"]
+    if wpre:
+        tags.append("wpre")
+    if phase_mode:
+        tags.append("phase" if phase_mode == 1 else "dphase")
+    if d2s and not phase_mode:
+        tags.append("d2s")
+    if amax:
+        tags.append("amax")
+    if fold:
+        tags.append("fold%d" % fold)
+    return dict(kernel="direct<%d,%s>" % (bc, ",".join(tags)), bc=bc, wpre=wpre, persistent=False)
+
+
+def phase_fwd_form(n, h, w, k, c0, act, addend=False, ldc=None):
+    """hn_conv3x3_phase mode 4 on the low-resolution grid (n, h, w)"""
+    return direct_form(4, n, h, w, 4 * k, kp32(c0), c0, False, ldc or k, act=act, phase_mode=1, phase_span=k, d2s=k, addend=addend)
+
+
+def seg_out_form(n, h, w, k, c0=64, amax=False):
+    """hn_conv_gemm_nt mode 4 with img_stride = -k (fp32 depth-to-space logits) / hn_conv3x3_out_argmax"""
+    return direct_form(4, n, h, w, 4 * k, kp32(c0), c0, True, 4 * k, d2s=k, amax=amax)
+
+
+def phase_dgrad_form(n, h, w, k, nout, fold=0, ldc=None):
+    """hn_conv3x3_phase mode 3 / the phase form of hn_conv3x3_dgrad_fold on the padded grid (n, h + 2, w + 2) of the low-resolution map"""
+    return direct_form(3, n, h + 2, w + 2, nout, kp32(4 * k), 4 * k, False, ldc or nout, phase_mode=2, phase_span=k, fold=fold)
+
+
+def fold_form(n, h, w, cz, nout, phase_k, plain, s2d):
+    """dgrad_fold_impl: -> (status, form) with status 0 ok / 1 HN_ERR_ARG / 3 HN_ERR_UNSUPPORTED (the refusals the header documents) and
+    form = the GemmNT::fold value with the direct kernel's name"""
+    if s2d and (h % 2 or w % 2):
+        return 1, None
+    if phase_k and (cz != 4 * phase_k or phase_k % 64):
+        return 1, None
+    if nout % 8 or nout <= 32 or h < 4 or w < 4:
+        return 3, None
+    fold = 1 if not s2d else (3 if plain else 2)
+    if phase_k:
+        return 0, phase_dgrad_form(n, h, w, phase_k, nout, fold=fold)
+    return 0, direct_form(3, n, h + 2, w + 2, nout, kp32(cz), cz, False, nout, fold=fold)
+
+
+def nt_entry_kernel(entry, m, nout, kp):
+    """the gemm_nt_kernel tiling of the plain-row entry points hn_conv_gemm_nt_imgw / _lvl / _lvlout / _stat3 (all mode 0, one tap,
+    through run_gemm_nt's tile choice); stat3 exists on the 64 x 64 tiling only (None: HN_ERR_ARG)"""
+    assert entry in ("imgw", "lvl", "lvlout", "stat3")
+    if entry == "stat3" and not small_tile(m, nout):
+        return None
+    return nt_kernel(0, m, nout, kp, 1)
 
 
 # ---- what the product source launches ------------------------------------------------------------------------------------------
