@@ -672,6 +672,17 @@ long hn_det_post_ws_bytes(int N, int cap);
 int hn_det_postprocess(const float* anchors, const float* regression, const float* classification, int N, int A, int K, int img_h, int img_w,
                        float threshold, float iou_threshold, int cap, void* ws, float* rois, long* class_ids, float* scores, int* kept,
                        int* total, hipStream_t stream);
+/* The same pipeline with the suppression rule as an option (DESIGN.md 4z).  nms_kind: 0 hard (the rule above), 1 diou (suppress when
+ * IoU - rho^2 / c^2 > iou_threshold: rho = distance of the centres, c = diagonal of the enclosing box), 2 soft_linear, 3 soft_gaussian
+ * (Soft-NMS: the highest working score is emitted and decays every other by 1 - IoU when IoU > iou_threshold, or by exp(-IoU^2 / sigma);
+ * a box leaves when its score is no longer > score_floor; scores holds the decayed scores, still in descending order).  max_det: at most
+ * that many boxes per image (0: no limit; total keeps its meaning).  class_agnostic != 0: no class offset.  nms_kind 0, max_det 0,
+ * class_agnostic 0 give hn_det_postprocess's outputs bit for bit.  ws: hn_det_post_ws_bytes_ex(N, cap, nms_kind) bytes of scratch. */
+long hn_det_post_ws_bytes_ex(int N, int cap, int nms_kind);
+int hn_det_postprocess_ex(const float* anchors, const float* regression, const float* classification, int N, int A, int K, int img_h,
+                          int img_w, float threshold, float iou_threshold, int cap, void* ws, float* rois, long* class_ids, float* scores,
+                          int* kept, int* total, int nms_kind, float sigma, float score_floor, int max_det, int class_agnostic,
+                          hipStream_t stream);
 
 /* Lane decode + lane NMS (LaneHeader.decode, head_lane/lanedetect.py:103-116 = softmax + LaneCodec.decode_lane, lane_codec.py:116-219 +
  * nms_with_pos, lane_codec_utils.py:487-543) for a batch: one workgroup per image.  predict_cls fp32 [N][hw][2] (logits), predict_loc fp32

@@ -1,7 +1,8 @@
 // Device-side stages either side of the forward/backward hot path:
 //   1. detection post-process: box decode + clip + per-anchor max / arg-max class + score threshold compaction + stable score sort +
 //      class-offset greedy NMS + gather, for a whole batch, no host round trip between the stages
-//      (head_detect/detection_loss.py:7-108, model/model.py:193-198; torchvision.ops.batched_nms semantics, see postprocess.py)
+//      (head_detect/detection_loss.py:7-108, model/model.py:193-198; torchvision.ops.batched_nms semantics, see postprocess.py);
+//      hn_det_postprocess_ex: the same with the suppression rule as an option -- DIoU-NMS, Soft-NMS, max_det, class-agnostic
 //   2. lane decode + lane NMS (head_lane/lane_codec.py:116-219, head_lane/lane_codec_utils.py:487-543, head_lane/lanedetect.py:103-116)
 //   3. input pre-processing: BGR uint8 HWC frame -> bilinear resize -> RGB -> /255, ImageNet mean / std -> fp32 NCHW
 //      (demo.py:26-50,191-196; dataset/utility.py:213-227)
@@ -104,30 +105,69 @@ __device__ __forceinline__ float iou_rn4(const float4 a, const float4 b) {
     return __fdiv_rn(inter, __fsub_rn(__fadd_rn(area_a, area_b), inter));
 }
 
-// suppression bit mask of image n: bit (i, j) = (j > i) and IoU(i, j) > thr.  grid (word columns, row chunks of 64, image)
-__global__ __launch_bounds__(64) void det_mask_kernel(const float4* sboxes, int cap, const int* count, float thr, unsigned long long* mask,
-                                                      int words_cap) {
+// The suppression rules of hn_det_postprocess_ex.  The operators below are written under `fp contract(off)`: every one
+// is an fp32 operation rounded on its own (see ema_lerp_rn in hn_common.h), which a numpy float32 restatement reproduces bit for bit.
+#define HN_NMS_HARD 0
+#define HN_NMS_DIOU 1
+#define HN_NMS_SOFT_LINEAR 2
+#define HN_NMS_SOFT_GAUSSIAN 3
+
+__device__ __forceinline__ float iou_strict(const float4 a, const float4 b) {
+#pragma clang fp contract(off)
+    const float area_a = (a.z - a.x) * (a.w - a.y);
+    const float area_b = (b.z - b.x) * (b.w - b.y);
+    float iw = fminf(a.z, b.z) - fmaxf(a.x, b.x);
+    float ih = fminf(a.w, b.w) - fmaxf(a.y, b.y);
+    iw = iw > 0.f ? iw : 0.f;
+    ih = ih > 0.f ? ih : 0.f;
+    const float inter = iw * ih;
+    const float uni = (area_a + area_b) - inter;
+    return __fdiv_rn(inter, uni);
+}
+
+// DIoU-NMS criterion (Zheng et al., AAAI 2020): IoU - rho^2 / c^2, rho = distance of the two centres, c = diagonal of the smallest
+// enclosing box; the penalty is 0 when c^2 is not > 0.  A NaN IoU stays NaN (it suppresses nothing).
+__device__ __forceinline__ float diou_strict(const float4 a, const float4 b) {
+#pragma clang fp contract(off)
+    const float iou = iou_strict(a, b);
+    const float dx = __fdiv_rn(b.x + b.z, 2.f) - __fdiv_rn(a.x + a.z, 2.f);
+    const float dy = __fdiv_rn(b.y + b.w, 2.f) - __fdiv_rn(a.y + a.w, 2.f);
+    const float rho2 = dx * dx + dy * dy;
+    const float ex = fmaxf(a.z, b.z) - fminf(a.x, b.x);
+    const float ey = fmaxf(a.w, b.w) - fminf(a.y, b.y);
+    const float c2 = ex * ex + ey * ey;
+    const float pen = c2 > 0.f ? __fdiv_rn(rho2, c2) : 0.f;
+    return iou - pen;
+}
+
+// suppression bit mask of image n: bit (i, j) = (j > i) and criterion(i, j) > thr, the criterion being the IoU (CRIT = HN_NMS_HARD) or
+// the DIoU (HN_NMS_DIOU).  grid (word columns, row chunks of 64, image).  Box i of image n is boxes[(n * cap + i) * bstride]: the
+// class-offset boxes (bstride 1) or, class-agnostic, the boxes inside the sorted candidates (bstride 2).
+template <int CRIT>
+__global__ __launch_bounds__(64) void det_mask_kernel(const float4* boxes, int bstride, int cap, const int* count, float thr,
+                                                      unsigned long long* mask, int words_cap) {
     const int n = blockIdx.z;
     int cnt = count[n];
     if (cnt > cap) cnt = cap;
     const int wj = blockIdx.x, i0 = blockIdx.y * 64;
     if (i0 >= cnt || wj * 64 >= cnt) return;
-    const float4* b = sboxes + (long)n * cap;
+    const float4* b = boxes + (long)n * cap * bstride;
     const int j = wj * 64 + threadIdx.x;
     float4 bj = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (j < cnt) bj = b[j];
+    if (j < cnt) bj = b[(long)j * bstride];
     const int i1 = i0 + 64 < cnt ? i0 + 64 : cnt;
     for (int i = i0; i < i1; ++i) {
         bool sup = false;
-        if (j < cnt && j > i) sup = iou_rn4(b[i], bj) > thr;
+        if (j < cnt && j > i) sup = (CRIT == HN_NMS_DIOU ? diou_strict(b[(long)i * bstride], bj) : iou_rn4(b[(long)i * bstride], bj)) > thr;
         const unsigned long long bits = __ballot(sup);
         if (threadIdx.x == 0) mask[((long)n * cap + i) * words_cap + wj] = bits;
     }
 }
 
-// one wave per image walks the boxes in order (greedy NMS) and writes the kept candidates compactly, in descending-score order
+// one wave per image walks the boxes in order (greedy NMS) and writes the kept candidates compactly, in descending-score order; the walk
+// stops after max_det kept boxes (0: no limit)
 __global__ __launch_bounds__(64) void det_scan_kernel(const unsigned long long* mask, int cap, int words_cap, const int* count, const DetCand* sorted,
-                                                      float* rois, long* class_ids, float* scores, int* kept) {
+                                                      int max_det, float* rois, long* class_ids, float* scores, int* kept) {
     constexpr int NW = 8;                                  // up to 64 * 64 * 8 = 32768 candidates per image
     const int n = blockIdx.x;
     int cnt = count[n];
@@ -139,6 +179,7 @@ __global__ __launch_bounds__(64) void det_scan_kernel(const unsigned long long* 
     const int lane = threadIdx.x;
     int nk = 0;
     for (int i = 0; i < cnt; ++i) {
+        if (max_det > 0 && nk >= max_det) break;
         const int wi = i >> 6;
         unsigned long long wv = 0ull;
 #pragma unroll
@@ -169,9 +210,201 @@ __global__ void zero_i32_kernel(int* p, int n, int v) {
     if (i < n) p[i] = v;
 }
 
-extern "C" long hn_det_post_ws_bytes(int N, int cap) {
+// ---- Soft-NMS (Bodla et al., ICCV 2017): one workgroup of 1024 threads per image ------------------------------------------------------
+// Candidate j of the sorted order belongs to thread j % 1024 for the whole walk, so the working scores and alive flags need no barrier
+// of their own.  A selection step is a workgroup arg-max over the key (working score descending, sorted index ascending) packed into one
+// 64-bit integer: DPP row maxima and four v_readlane per wave, then one LDS pass over the 16 waves' maxima, double buffered by the
+// step's parity (ONE barrier per step).  The decay against a step's winner and the local arg-max of the next step are one pass over the
+// thread's candidates.  No atomics, no float reduction: the result is the same bits every run.
+constexpr int SOFT_NT = 1024;
+constexpr int SOFT_LDS_N = 8192;       // candidates whose working score + alive flag live in LDS (5 bytes each, 40 KiB); more: the workspace
+constexpr int SOFT_RB = 4;             // boxes per thread held in registers (the first 4096 candidates); the rest are re-read through L2
+
+template <int CTRL>
+__device__ __forceinline__ unsigned long long dpp_mov_u64(unsigned long long v) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)v, CTRL, 0xf, 0xf, false);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), CTRL, 0xf, 0xf, false);
+    return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ unsigned long long max_u64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
+__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int l) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
+    return ((unsigned long long)hi << 32) | lo;
+}
+// maximum over the 64 lanes of a wave (every lane gets it; call with all lanes active)
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+    v = max_u64(v, dpp_mov_u64<0x128>(v));   // row_ror:8
+    v = max_u64(v, dpp_mov_u64<0x124>(v));   // row_ror:4
+    v = max_u64(v, dpp_mov_u64<0x122>(v));   // row_ror:2
+    v = max_u64(v, dpp_mov_u64<0x121>(v));   // row_ror:1
+    return max_u64(max_u64(readlane_u64(v, 0), readlane_u64(v, 16)), max_u64(readlane_u64(v, 32), readlane_u64(v, 48)));
+}
+// larger key = larger score, then smaller index; never 0 for a candidate (index < 32768), so 0 says "none alive"
+__device__ __forceinline__ unsigned long long soft_key(float t, int j) {
+    return ((unsigned long long)((unsigned)float_order_key(t) ^ 0x80000000u) << 32) | (unsigned)~(unsigned)j;
+}
+
+__device__ __forceinline__ float soft_weight(float iou, float thr, int gauss, double sigma) {
+    if (gauss) {                                           // fp32 rounding of the float64 exp(-iou^2 / sigma); iou == 0 gives exactly 1
+        if (iou == iou && iou != 0.f) return (float)exp(-((double)iou * (double)iou) / sigma);
+        return 1.f;
+    }
+    return iou > thr ? __fsub_rn(1.f, iou) : 1.f;          // (a NaN IoU compares false)
+}
+
+// the walk of one image; t / alive: cnt working scores and flags in LDS or in the workspace.  Writes the emitted candidates' scores and
+// sorted indices in output order, returns their number.
+__device__ __forceinline__ int soft_walk(unsigned long long* red, float* t, unsigned char* alive, const DetCand* sn, const float4* b, int bstride,
+                                         int cnt, float thr, int gauss, double sigma, float score_floor, int max_det, float* scores_n,
+                                         int* eidx_n) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float4 breg[SOFT_RB];
+    unsigned long long best = 0ull;
+#pragma unroll
+    for (int r = 0; r < SOFT_RB; ++r) {
+        const int j = r * SOFT_NT + tid;
+        breg[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (j < cnt) {
+            breg[r] = b[(long)j * bstride];
+            const float s = sn[j].score;
+            t[j] = s; alive[j] = 1;
+            best = max_u64(best, soft_key(s, j));
+        }
+    }
+    for (int j = SOFT_RB * SOFT_NT + tid; j < cnt; j += SOFT_NT) {
+        const float s = sn[j].score;
+        t[j] = s; alive[j] = 1;
+        best = max_u64(best, soft_key(s, j));
+    }
+    int nk = 0;
+    for (int step = 0;; ++step) {
+        const unsigned long long wk = wave_max_u64(best);
+        unsigned long long* rd = red + (step & 1) * 16;
+        if (lane == 0) rd[wave] = wk;
+        __syncthreads();
+        unsigned long long win = 0ull;
+#pragma unroll
+        for (int i = 0; i < SOFT_NT / 64; ++i) win = max_u64(win, rd[i]);
+        if (win == 0ull) break;                                                 // nothing alive (uniform)
+        const int m = __builtin_amdgcn_readfirstlane((int)~(unsigned)win);
+        if (tid == 0) {
+            scores_n[nk] = float_from_key((int)((unsigned)(win >> 32) ^ 0x80000000u));
+            eidx_n[nk] = m;
+        }
+        ++nk;
+        if (max_det > 0 && nk >= max_det) break;
+        const float4 bm = b[(long)m * bstride];
+        best = 0ull;
+        auto visit = [&](int j, const float4 bj) {
+            if (!alive[j]) return;
+            if (j == m) { alive[j] = 0; return; }
+            const float tj = __fmul_rn(t[j], soft_weight(iou_strict(bm, bj), thr, gauss, sigma));
+            if (tj > score_floor) {
+                t[j] = tj;
+                best = max_u64(best, soft_key(tj, j));
+            } else {
+                alive[j] = 0;
+            }
+        };
+#pragma unroll
+        for (int r = 0; r < SOFT_RB; ++r) {
+            const int j = r * SOFT_NT + tid;
+            if (j < cnt) visit(j, breg[r]);
+        }
+        for (int j = SOFT_RB * SOFT_NT + tid; j < cnt; j += SOFT_NT) visit(j, b[(long)j * bstride]);
+    }
+    return nk;
+}
+
+__global__ __launch_bounds__(SOFT_NT) void det_soft_nms_kernel(const DetCand* sorted, const float4* boxes, int bstride, int cap, const int* count,
+                                                               int lds_n, float thr, int gauss, double sigma, float score_floor, int max_det,
+                                                               float* t_ws, unsigned char* alive_ws, int* eidx, float* rois, long* class_ids,
+                                                               float* scores, int* kept) {
+    extern __shared__ __attribute__((aligned(16))) char soft_smem[];           // [2][16] keys, lds_n floats, lds_n flags
+    unsigned long long* red = reinterpret_cast<unsigned long long*>(soft_smem);
+    const int n = blockIdx.x;
+    int cnt = count[n];
+    if (cnt > cap) cnt = cap;
+    const DetCand* sn = sorted + (long)n * cap;
+    const float4* b = boxes + (long)n * cap * bstride;
+    int* eidx_n = eidx + (long)n * cap;
+    int nk;
+    if (cnt <= lds_n)
+        nk = soft_walk(red, reinterpret_cast<float*>(soft_smem + 256), reinterpret_cast<unsigned char*>(soft_smem + 256 + (long)lds_n * 4), sn, b,
+                       bstride, cnt, thr, gauss, sigma, score_floor, max_det, scores + (long)n * cap, eidx_n);
+    else
+        nk = soft_walk(red, t_ws + (long)n * cap, alive_ws + (long)n * cap, sn, b, bstride, cnt, thr, gauss, sigma, score_floor, max_det,
+                       scores + (long)n * cap, eidx_n);
+    __threadfence_block();                                                      // thread 0's index list is read back by the whole workgroup
+    __syncthreads();
+    for (int e = threadIdx.x; e < nk; e += SOFT_NT) {
+        const DetCand d = sn[eidx_n[e]];
+        float* r = rois + ((long)n * cap + e) * 4;
+        r[0] = d.x1; r[1] = d.y1; r[2] = d.x2; r[3] = d.y2;
+        class_ids[(long)n * cap + e] = d.cls;
+    }
+    if (threadIdx.x == 0) kept[n] = nk;
+}
+
+static inline bool det_nms_soft(int kind) { return kind == HN_NMS_SOFT_LINEAR || kind == HN_NMS_SOFT_GAUSSIAN; }
+
+extern "C" long hn_det_post_ws_bytes_ex(int N, int cap, int nms_kind) {
     const long words = (cap + 63) / 64;
-    return (long)N * cap * (2 * sizeof(DetCand) + sizeof(float4)) + (long)N * cap * words * 8 + 2L * N * sizeof(int) + 256;
+    const long front = (long)N * cap * (2 * sizeof(DetCand) + sizeof(float4)) + 2L * N * sizeof(int) + 256;
+    if (det_nms_soft(nms_kind)) return front + (long)N * cap * (sizeof(float) + sizeof(int) + 1);      // working scores, index list, flags
+    return front + (long)N * cap * words * 8;                                                           // the suppression bit mask
+}
+
+extern "C" long hn_det_post_ws_bytes(int N, int cap) { return hn_det_post_ws_bytes_ex(N, cap, HN_NMS_HARD); }
+
+// select + rank (the pipeline in front of every suppression rule), then the rule: mask + scan (hard, diou) or the soft walk
+static int det_post_launch(const float* anchors, const float* regression, const float* classification, int N, int A, int K, int img_h, int img_w,
+                           float threshold, float iou_threshold, int cap, void* ws, float* rois, long* class_ids, float* scores, int* kept,
+                           int* total, int kind, float sigma, float score_floor, int max_det, int class_agnostic, hipStream_t st) {
+    char* w = (char*)ws;
+    DetCand* cand = (DetCand*)w; w += (long)N * cap * sizeof(DetCand);
+    DetCand* sorted = (DetCand*)w; w += (long)N * cap * sizeof(DetCand);
+    float4* sboxes = (float4*)w; w += (long)N * cap * sizeof(float4);
+    // class-agnostic: the boxes as they are, read from inside the sorted candidates (a DetCand is two float4, the box is the second)
+    const float4* boxes = class_agnostic ? reinterpret_cast<const float4*>(sorted) + 1 : sboxes;
+    const int bstride = class_agnostic ? 2 : 1;
+    // workspace behind the three candidate arrays: the bit mask (hard, diou) or the working scores and the index list (soft), the per-image
+    // maximum coordinate, and (soft) the alive flags
+    const bool soft = det_nms_soft(kind);
+    const int words = (cap + 63) / 64;
+    unsigned long long* mask = nullptr;
+    float* t_ws = nullptr;
+    int* eidx = nullptr;
+    if (soft) {
+        t_ws = (float*)w; w += (long)N * cap * sizeof(float);
+        eidx = (int*)w; w += (long)N * cap * sizeof(int);
+    } else {
+        mask = (unsigned long long*)w; w += (long)N * cap * words * 8;
+    }
+    int* maxkey = (int*)w; w += (long)N * sizeof(int);
+    unsigned char* alive_ws = (unsigned char*)w;
+    hipLaunchKernelGGL(zero_i32_kernel, dim3(cdiv(N, 64)), dim3(64), 0, st, total, N, 0);
+    hipLaunchKernelGGL(zero_i32_kernel, dim3(cdiv(N, 64)), dim3(64), 0, st, maxkey, N, (int)0x80000000);
+    hipLaunchKernelGGL(det_select_kernel, dim3(cdiv(A, 256), N), dim3(256), 0, st, anchors, regression, classification, A, K, threshold,
+                       (float)(img_w - 1), (float)(img_h - 1), cand, cap, total, maxkey);
+    hipLaunchKernelGGL(det_rank_kernel, dim3(cdiv(cap, 256), N), dim3(256), 0, st, (const DetCand*)cand, cap, (const int*)total,
+                       (const int*)maxkey, sorted, sboxes);
+    if (soft) {
+        const int lds_n = ((cap < SOFT_LDS_N ? cap : SOFT_LDS_N) + 15) & ~15;
+        hipLaunchKernelGGL(det_soft_nms_kernel, dim3(N), dim3(SOFT_NT), (size_t)256 + (size_t)lds_n * 5, st, (const DetCand*)sorted, boxes, bstride,
+                           cap, (const int*)total, lds_n, iou_threshold, kind == HN_NMS_SOFT_GAUSSIAN ? 1 : 0, (double)sigma, score_floor, max_det,
+                           t_ws, alive_ws, eidx, rois, class_ids, scores, kept);
+        HN_LAUNCH_CHECK();
+    }
+    if (kind == HN_NMS_DIOU)
+        hipLaunchKernelGGL(det_mask_kernel<HN_NMS_DIOU>, dim3(words, cdiv(cap, 64), N), dim3(64), 0, st, boxes, bstride, cap, (const int*)total,
+                           iou_threshold, mask, words);
+    else
+        hipLaunchKernelGGL(det_mask_kernel<HN_NMS_HARD>, dim3(words, cdiv(cap, 64), N), dim3(64), 0, st, boxes, bstride, cap, (const int*)total,
+                           iou_threshold, mask, words);
+    hipLaunchKernelGGL(det_scan_kernel, dim3(N), dim3(64), 0, st, (const unsigned long long*)mask, cap, words, (const int*)total,
+                       (const DetCand*)sorted, max_det, rois, class_ids, scores, kept);
+    HN_LAUNCH_CHECK();
 }
 
 /* anchors fp32 [A][4] (y1,x1,y2,x2), regression [N][A][4], classification [N][A][K] (post-sigmoid).  cap <= 32768 = capacity per image.
@@ -183,24 +416,24 @@ extern "C" int hn_det_postprocess(const float* anchors, const float* regression,
                                   float* scores, int* kept, int* total, hipStream_t st) {
     HN_CHECK_ARG(anchors && regression && classification && ws && rois && class_ids && scores && kept && total);
     HN_CHECK_ARG(N > 0 && A > 0 && K > 0 && cap > 0 && cap <= 32768);
-    char* w = (char*)ws;
-    DetCand* cand = (DetCand*)w; w += (long)N * cap * sizeof(DetCand);
-    DetCand* sorted = (DetCand*)w; w += (long)N * cap * sizeof(DetCand);
-    float4* sboxes = (float4*)w; w += (long)N * cap * sizeof(float4);
-    const int words = (cap + 63) / 64;
-    unsigned long long* mask = (unsigned long long*)w; w += (long)N * cap * words * 8;
-    int* maxkey = (int*)w;
-    hipLaunchKernelGGL(zero_i32_kernel, dim3(cdiv(N, 64)), dim3(64), 0, st, total, N, 0);
-    hipLaunchKernelGGL(zero_i32_kernel, dim3(cdiv(N, 64)), dim3(64), 0, st, maxkey, N, (int)0x80000000);
-    hipLaunchKernelGGL(det_select_kernel, dim3(cdiv(A, 256), N), dim3(256), 0, st, anchors, regression, classification, A, K, threshold,
-                       (float)(img_w - 1), (float)(img_h - 1), cand, cap, total, maxkey);
-    hipLaunchKernelGGL(det_rank_kernel, dim3(cdiv(cap, 256), N), dim3(256), 0, st, (const DetCand*)cand, cap, (const int*)total,
-                       (const int*)maxkey, sorted, sboxes);
-    hipLaunchKernelGGL(det_mask_kernel, dim3(words, cdiv(cap, 64), N), dim3(64), 0, st, (const float4*)sboxes, cap, (const int*)total,
-                       iou_threshold, mask, words);
-    hipLaunchKernelGGL(det_scan_kernel, dim3(N), dim3(64), 0, st, (const unsigned long long*)mask, cap, words, (const int*)total,
-                       (const DetCand*)sorted, rois, class_ids, scores, kept);
-    HN_LAUNCH_CHECK();
+    return det_post_launch(anchors, regression, classification, N, A, K, img_h, img_w, threshold, iou_threshold, cap, ws, rois, class_ids, scores,
+                           kept, total, HN_NMS_HARD, 0.5f, threshold, 0, 0, st);
+}
+
+/* hn_det_postprocess with the suppression rule as an option.  nms_kind: 0 hard (the rule above), 1 diou (suppress when
+ * IoU - rho^2 / c^2 > iou_threshold), 2 soft_linear, 3 soft_gaussian (Soft-NMS: the winner decays the others' scores by 1 - IoU when
+ * IoU > iou_threshold, or by exp(-IoU^2 / sigma); a box leaves when its score is no longer > score_floor; the scores returned are the
+ * decayed ones).  max_det: at most that many boxes per image (0: no limit).  class_agnostic != 0: no class offset.  With nms_kind 0,
+ * max_det 0 and class_agnostic 0 the outputs are hn_det_postprocess's, bit for bit.  ws: hn_det_post_ws_bytes_ex(N, cap, nms_kind) bytes. */
+extern "C" int hn_det_postprocess_ex(const float* anchors, const float* regression, const float* classification, int N, int A, int K, int img_h,
+                                     int img_w, float threshold, float iou_threshold, int cap, void* ws, float* rois, long* class_ids,
+                                     float* scores, int* kept, int* total, int nms_kind, float sigma, float score_floor, int max_det,
+                                     int class_agnostic, hipStream_t st) {
+    HN_CHECK_ARG(anchors && regression && classification && ws && rois && class_ids && scores && kept && total);
+    HN_CHECK_ARG(N > 0 && A > 0 && K > 0 && cap > 0 && cap <= 32768);
+    HN_CHECK_ARG(nms_kind >= HN_NMS_HARD && nms_kind <= HN_NMS_SOFT_GAUSSIAN && sigma > 0.f && sigma <= 3.0e38f && max_det >= 0);
+    return det_post_launch(anchors, regression, classification, N, A, K, img_h, img_w, threshold, iou_threshold, cap, ws, rois, class_ids, scores,
+                           kept, total, nms_kind, sigma, score_floor, max_det, class_agnostic, st);
 }
 
 // =====================================================================================================================================

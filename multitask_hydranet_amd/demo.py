@@ -52,8 +52,11 @@ def seg_palette(colors: dict) -> dict:
 class Demo:
     """the state demo.py sets up before its frame loop (demo.py:68-134)"""
 
-    def __init__(self, cfgs: dict, weights: Optional[str] = None, device="cuda:0", fold_batchnorm: bool = True, lane_seg_filter=None):
-        """lane_seg_filter: True (the deploy header's constants) or a lane_codec.LaneSegFilter -- every process* call then caps the decoded
+    def __init__(self, cfgs: dict, weights: Optional[str] = None, device="cuda:0", fold_batchnorm: bool = True, lane_seg_filter=None,
+                 det_nms=None):
+        """det_nms: a postprocess.NmsOptions -- the suppression rule every process* call decodes its boxes with; None: the
+        rule of the cfg's detection.nms_* keys, the reference's hard NMS without them.
+        lane_seg_filter: True (the deploy header's constants) or a lane_codec.LaneSegFilter -- every process* call then caps the decoded
         lanes and filters them by the seg head's marking class on the device; each call's own lane_seg_filter argument
         overrides it (False: off for that call).  Needs a configuration that runs the seg head and the lane head."""
         from . import HydraNet
@@ -77,8 +80,16 @@ class Demo:
         if weights:
             self.net.load_state_dict(torch.load(weights, map_location="cpu"))    # (`module.` prefixes are stripped by load_state_dict)
         self.net.eval()
+        from .postprocess import NmsOptions
+        if det_nms is not None and not isinstance(det_nms, NmsOptions):
+            raise ValueError("det_nms is a postprocess.NmsOptions or None, not %r" % (det_nms,))
+        self.det_nms = det_nms if det_nms is not None else getattr(self.net, "det_nms", None)
         if fold_batchnorm:
             self.net.prepare_inference()
+
+    def _det_nms_kw(self):
+        """detectheader.decode's nms argument: only when a rule is set, so that without one the call is what it always was"""
+        return {} if self.det_nms is None else {"nms": self.det_nms}
 
     def _lane_filter(self, asked, default):
         """the LaneSegFilter a call runs with: its own argument (True: the deploy defaults, False: none), else the constructor's"""
@@ -127,7 +138,7 @@ class Demo:
         if self.train_detect:                                                                 # demo.py:236-242
             det = outputs["detection"]
             res["detections"] = net.detectheader.decode(img, det["regression"], det["classification"], det["anchors"], conf_thres=self.det_conf,
-                                                        iou_thres=self.det_iou)
+                                                        iou_thres=self.det_iou, **self._det_nms_kw())
         torch.cuda.synchronize(self.device)
         res["visual"] = imgs[0]
         res["ms"] = 1000.0 * (time.time() - tic)
@@ -193,7 +204,7 @@ class Demo:
         if self.train_detect:
             det = outputs["detection"]
             res["detections"] = net.detectheader.decode(img, det["regression"], det["classification"], det["anchors"], conf_thres=self.det_conf,
-                                                        iou_thres=self.det_iou)
+                                                        iou_thres=self.det_iou, **self._det_nms_kw())
             frames = net.detectheader.display(res["detections"], frames, self.obj_list, org_size, (self.net_w, self.net_h))
         res["jpeg"] = jpeg_encode.encode_batch(frames, quality, subsampling, entropy)[0]
         res["visual"] = frames
@@ -244,7 +255,7 @@ class Demo:
         if self.train_detect:
             det = outputs["detection"]
             det_args = ((img.shape[2], img.shape[3]), det["anchors"], det["regression"], det["classification"], self.det_conf, self.det_iou)
-            launched = postprocess_device(*det_args)
+            launched = postprocess_device(*det_args, nms=self.det_nms)
         if self.train_lane:
             cls_preds, loc_preds = outputs["lane"]["predict_cls"], outputs["lane"]["predict_loc"]
             if flt is None:
@@ -255,7 +266,7 @@ class Demo:
                                                                            False, seg_mask=mask, seg_filter=flt, return_stats=True)
             res["lanes"] = [net.laneheader.scale_to_org(s, self.net_w, self.net_h, org_w, org_h)["Lines"] for s in nms_sets]
         if self.train_detect:
-            res["detections"] = postprocess(*det_args, launched=launched)
+            res["detections"] = postprocess(*det_args, nms=self.det_nms, launched=launched)
         # the drawing, in the reference's order: lanes, seg overlay, boxes
         if self.train_lane:
             frames = net.laneheader.visual(frames, res["lanes"], org_w, filter_vertical=True)
@@ -427,6 +438,11 @@ def main(argv=None):
     ap.add_argument("--lane-seg-ratio", type=float, default=None, help="the overlap a lane needs, exclusive (--lane-seg-filter; 0.01)")
     ap.add_argument("--lane-seg-width", type=int, default=None, help="thickness the lanes are painted with, pixels (--lane-seg-filter; 20)")
     ap.add_argument("--lane-seg-class", type=int, default=None, help="the seg class id that counts as marking (--lane-seg-filter; 2)")
+    ap.add_argument("--nms", choices=("hard", "diou", "soft_linear", "soft_gaussian"), default=None, help="the suppression rule of the box decode "
+                    "(postprocess.NmsOptions); without any --nms* / --max-det flag: the cfg's detection.nms_* keys, else the reference's hard NMS")
+    ap.add_argument("--nms-sigma", type=float, default=None, help="sigma of --nms soft_gaussian (0.5)")
+    ap.add_argument("--max-det", type=int, default=None, help="boxes drawn per frame at most (0: no limit)")
+    ap.add_argument("--nms-class-agnostic", action="store_true", help="boxes of different classes suppress each other")
     ap.add_argument("--count", type=int, default=4)
     ap.add_argument("--out", default=None, help="directory for the annotated JPEGs (--images) or frame_%%04d.npy (blended frames), and results.json; "
                     "the annotated AVI (--video)")
@@ -450,7 +466,12 @@ def main(argv=None):
     if args.save_seg and not cfgs["train"]["train_seg"]:
         raise ValueError("--save-seg: %s runs no seg head (train.train_seg is off)" % args.cfg)
     torch.manual_seed(0)
-    demo = Demo(cfgs, args.weights, lane_seg_filter=lane_filter)
+    det_nms = None
+    if args.nms is not None or args.nms_sigma is not None or args.max_det is not None or args.nms_class_agnostic:
+        from .postprocess import NmsOptions
+        det_nms = NmsOptions(kind=args.nms or "hard", sigma=0.5 if args.nms_sigma is None else args.nms_sigma, max_det=args.max_det or 0,
+                             class_agnostic=args.nms_class_agnostic)
+    demo = Demo(cfgs, args.weights, lane_seg_filter=lane_filter, det_nms=det_nms)
     if not args.weights:
         # random initialisation: every anchor scores ~0.5, far more candidates than any real frame has (the device NMS holds 32 768)
         print("no --weights: random initialisation, detection threshold raised to 0.95 for this run")

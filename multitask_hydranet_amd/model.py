@@ -172,8 +172,13 @@ class HydraNet(nn.Module):
             self.tal_topk = cfgs["detection"].get("tal_topk", 13)
             if isinstance(self.tal_topk, bool) or not isinstance(self.tal_topk, int) or self.tal_topk < 1:
                 raise ValueError("detection.tal_topk must be an integer >= 1, got %r" % (self.tal_topk,))
+            # detection.nms_type / nms_sigma / nms_score_floor / max_det / nms_class_agnostic: the suppression rule of the box decode
+            # (postprocess.NmsOptions, hn_det_postprocess_ex): hard (or no key at all: the reference's NMS through the entry point it has
+            # always used), diou, soft_linear, soft_gaussian.  Inference only: detectheader.decode, forward(x, "deploy") with
+            # deploy_postprocess, and through decode the COCO mAP of HydraTrainer.valid.  HIP only.
+            self.det_nms = _det_nms_options(cfgs["detection"])
         else:
-            self.detectheader, self.loss_detect = None, None
+            self.detectheader, self.loss_detect, self.det_nms = None, None, None
         if self.train_seg:
             self._declare_seg(spec)
             s = cfgs["segment"]
@@ -312,7 +317,7 @@ class HydraNet(nn.Module):
             self.segheader.decode = seg_decode
         if self.train_detect:
             object.__setattr__(self.detectheader, "_fwd", lambda x, fused: flushed(me()._det(x, [K_to_nhwc(t) for t in fused])))
-            self.detectheader.decode = _det_decode
+            self.detectheader.decode = _det_decode if self.det_nms is None else functools.partial(_det_decode, nms=self.det_nms)
             from .coco_json import invert_affine       # DetectionHeader.invert_affine (head_detect/detection.py:217-230; train.py:334-336)
             self.detectheader.invert_affine = invert_affine
             from .draw import display                  # DetectionHeader.display (head_detect/display.py:49-84) on the device
@@ -904,7 +909,7 @@ class HydraNet(nn.Module):
             from .postprocess import postprocess_device
             conf, iou = self.deploy_postprocess[:2]
             dep = dep + (postprocess_device((x.shape[2], x.shape[3]), anchors, reg, cls, conf, iou,
-                                            *(self.deploy_postprocess[2:3] or (4096,))),)
+                                            *(self.deploy_postprocess[2:3] or (4096,)), nms=self.det_nms),)
         return dep
 
     def _seg_loss(self, logits, target, valid=None):
@@ -1050,9 +1055,35 @@ def _drawing_helper(fn, what):
     return helper
 
 
-def _det_decode(imgs, regressions, classifications, anchors, conf_thres=0.6, iou_thres=0.3):
+def _det_decode(imgs, regressions, classifications, anchors, conf_thres=0.6, iou_thres=0.3, nms=None):
     from .postprocess import postprocess
     if imgs is None:
         return None
     return postprocess((imgs.shape[2], imgs.shape[3]), torch.stack([anchors[0]] * imgs.shape[0], 0).detach(), regressions.detach(),
-                       classifications.detach(), conf_thres, iou_thres)
+                       classifications.detach(), conf_thres, iou_thres, nms=nms)
+
+
+_DET_NMS_KEYS = ("nms_type", "nms_sigma", "nms_score_floor", "max_det", "nms_class_agnostic")
+
+
+def _det_nms_options(det_cfg):
+    """the postprocess.NmsOptions of a cfg's detection section; None when it has none of the keys (the decode then is what it always was)"""
+    from .postprocess import NMS_KINDS, NmsOptions
+    if not any(k in det_cfg for k in _DET_NMS_KEYS):
+        return None
+    kind = det_cfg.get("nms_type", "hard")
+    if kind not in NMS_KINDS:
+        raise ValueError("detection.nms_type must be one of 'hard', 'diou', 'soft_linear', 'soft_gaussian', got %r" % (kind,))
+    sigma = det_cfg.get("nms_sigma", 0.5)
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)) or not math.isfinite(sigma) or not sigma > 0:
+        raise ValueError("detection.nms_sigma must be a finite number > 0, got %r" % (sigma,))
+    floor = det_cfg.get("nms_score_floor", None)
+    if floor is not None and (isinstance(floor, bool) or not isinstance(floor, (int, float)) or math.isnan(floor)):
+        raise ValueError("detection.nms_score_floor must be a number, got %r" % (floor,))
+    max_det = det_cfg.get("max_det", 0)
+    if isinstance(max_det, bool) or not isinstance(max_det, int) or max_det < 0:
+        raise ValueError("detection.max_det must be an integer >= 0 (0: no limit), got %r" % (max_det,))
+    agnostic = det_cfg.get("nms_class_agnostic", False)
+    if not isinstance(agnostic, bool):
+        raise ValueError("detection.nms_class_agnostic must be true or false, got %r" % (agnostic,))
+    return NmsOptions(kind=kind, sigma=sigma, score_floor=floor, max_det=max_det, class_agnostic=agnostic)

@@ -215,6 +215,26 @@ def _(anchors, regression, classification, img_h, img_w, threshold, iou_threshol
             f.new_empty((n,), dtype=torch.int32)]
 
 
+@torch.library.custom_op(f"{NS}::det_postprocess_ex", mutates_args=(), device_types="cuda")
+def det_postprocess_ex(anchors: Tensor, regression: Tensor, classification: Tensor, img_h: int, img_w: int, threshold: float, iou_threshold: float,
+                       cap: int, nms_kind: str, sigma: float, score_floor: float, max_det: int, class_agnostic: bool) -> List[Tensor]:
+    """det_postprocess with the suppression rule of postprocess.NmsOptions (nms_kind: hard | diou | soft_linear | soft_gaussian; score_floor
+    is explicit here: pass the threshold for the default) -> the same five tensors"""
+    from .postprocess import NmsOptions, postprocess_device
+    nms = NmsOptions(kind=nms_kind, sigma=sigma, score_floor=score_floor, max_det=max_det, class_agnostic=class_agnostic)
+    r = postprocess_device((img_h, img_w), anchors, regression, classification, threshold, iou_threshold, cap, nms=nms)
+    return [r["rois"], r["class_ids"], r["scores"], r["kept"], r["total"]]
+
+
+@det_postprocess_ex.register_fake
+def _(anchors, regression, classification, img_h, img_w, threshold, iou_threshold, cap, nms_kind, sigma, score_floor, max_det, class_agnostic):
+    n = regression.shape[0]
+    c = min(cap, regression.shape[1])
+    f = regression
+    return [f.new_empty((n, c, 4)), f.new_empty((n, c), dtype=torch.int64), f.new_empty((n, c)), f.new_empty((n,), dtype=torch.int32),
+            f.new_empty((n,), dtype=torch.int32)]
+
+
 @torch.library.custom_op(f"{NS}::preprocess_bgr", mutates_args=(), device_types="cuda")
 def preprocess_bgr(frames: Tensor, out_h: int, out_w: int) -> Tensor:
     """uint8 [N,H,W,3] BGR -> fp32 [N,3,out_h,out_w] RGB, ImageNet-normalised (demo.py:186-196)"""
