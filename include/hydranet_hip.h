@@ -749,7 +749,8 @@ int hn_lane_metric_batch(const double* pts, const int* tab, int N, int n_lanes, 
                          int lane_width, void* ws, long ws_bytes, void* counts, long n_counts, hipStream_t stream);
 
 /* Streaming confusion counts for the segmentation mIoU (head_seg/seg_metrics.py:12-47): conf uint64 [(C+1)*(C+1)] += counts of
- * (pred, target) pairs, both clamped to C (the ignore bucket).  pred int64 [M]; target int64 or float32 [M]. */
+ * (pred, target) pairs, both clamped to C (the ignore bucket): an id above C or below 0 counts there (the reference raises on a
+ * negative id).  pred int64 [M]; target int64 or float32 [M] (truncated toward zero).  1 <= C <= 63. */
 int hn_seg_confusion(const long* pred, const void* target, int target_is_float, long M, int C, void* conf, hipStream_t stream);
 
 int hn_argmax_channels(const float* logits, int ldl, int C, long M, long* out, hipStream_t stream);

@@ -708,7 +708,8 @@ extern "C" int hn_resize_bgr8(const void* src, long src_bytes, const void* desc,
 }
 
 // =====================================================================================================================================
-// 4. segmentation confusion counts (streaming mIoU): conf[(p * (C+1)) + t] += 1 with p, t clamped to C (the ignore bucket)
+// 4. segmentation confusion counts (streaming mIoU): conf[(p * (C+1)) + t] += 1 with p, t clamped to C (the ignore bucket); ids outside
+//    [0, C] on either side -- negative ones included -- land in that bucket (the reference raises on a negative id)
 // =====================================================================================================================================
 __global__ __launch_bounds__(256) void seg_confusion_kernel(const long* pred, const void* target, int target_is_float, long M, int C,
                                                             unsigned long long* conf) {
@@ -719,8 +720,8 @@ __global__ __launch_bounds__(256) void seg_confusion_kernel(const long* pred, co
     for (long m = (long)blockIdx.x * 256 + threadIdx.x; m < M; m += (long)gridDim.x * 256) {
         long p = pred[m];
         long t = target_is_float ? (long)((const float*)target)[m] : ((const long*)target)[m];
-        p = p > C ? C : (p < 0 ? 0 : p);
-        t = t > C ? C : (t < 0 ? 0 : t);
+        p = (p > C || p < 0) ? C : p;
+        t = (t > C || t < 0) ? C : t;
         atomicAdd(&hist[p * (C + 1) + t], 1u);
     }
     __syncthreads();

@@ -1,7 +1,12 @@
 """Streaming segmentation IoU on the device (reference: head_seg/seg_metrics.py:12-101 stat_scores_multiple_classes + IntersectionOverUnion,
 used by train.py's validation loop).  update() adds one batch to a (C+1) x (C+1) uint64 confusion matrix with ONE kernel launch (integer
 atomics: exact and order independent; the reference accumulates float32 counters, which stop being exact above 2^24 pixels per class);
-compute() derives the per-class scores with the reference's rules (absent_score, ignore_index removal)."""
+compute() derives the per-class scores with the reference's rules (absent_score, ignore_index removal).
+
+Class ids above n_classes count in the extra (ignored) bucket, as in the reference (clamp_max).  NEGATIVE ids, in the prediction or the
+target, count in that bucket too; the reference raises on them (a negative scatter_add_ / bincount index), so there is no reference
+value to match and the one outcome ruled out is counting them as class 0 (tests/test_post_exact_gpu.py pins it).  Float targets are
+truncated toward zero (4.99 is class 4)."""
 from __future__ import annotations
 
 from typing import Optional

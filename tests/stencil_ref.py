@@ -33,6 +33,61 @@ def _tap(xp, ky, kx, s, Ho, Wo):
     return xp[:, ky:ky + s * (Ho - 1) + 1:s, kx:kx + s * (Wo - 1) + 1:s]
 
 
+# ---- stem: dense 3x3 / stride 2 / zero pad 1 from the NCHW frame; x [N][3][H][W], w [32][3][3][3] = w[co][ci][ky][kx] ----------------------
+def stem_out_hw(H, W):
+    """the kernel's `Ho = H >> 1, Wo = W >> 1`.  For an even size that is conv2d(stride 2, padding 1)'s (H + 1) // 2.  For an odd size it
+    is one less: output row oy reads input rows 2 oy - 1 .. 2 oy + 1 <= H - 2, so the rows 0 .. (H >> 1) - 1 are conv2d's first rows
+    unchanged, conv2d's last row (centred on input row H - 1) is not computed, and input row H - 1 is never read (the same for columns).
+    hn_stem_fwd refuses odd sizes (HN_ERR_ARG), so that truncation is never launched."""
+    return H >> 1, W >> 1
+
+
+def _stem_taps(x):
+    """(t, view [N, Ho, Wo]) for t = ci * 9 + ky * 3 + kx: input pixel (2 oy + ky - 1, 2 ox + kx - 1) of channel ci, 0 outside the frame"""
+    n, c, H, W = x.shape
+    assert c == 3
+    Ho, Wo = stem_out_hw(H, W)
+    xp = _z((n, 3, H + 2, W + 2), x)
+    xp[:, :, 1:H + 1, 1:W + 1] = x.to(F64)
+    for ci in range(3):
+        for ky in range(3):
+            for kx in range(3):
+                yield ci * 9 + ky * 3 + kx, xp[:, ci, ky:ky + 2 * (Ho - 1) + 1:2, kx:kx + 2 * (Wo - 1) + 1:2]
+
+
+def stem(x, w):
+    """z [N, Ho, Wo, 32]: z[n, oy, ox, co] = sum over (ci, ky, kx) of x[n, ci, 2 oy + ky - 1, 2 ox + kx - 1] * w[co, ci, ky, kx]"""
+    n, _, H, W = x.shape
+    Ho, Wo = stem_out_hw(H, W)
+    wt = w.to(F64).reshape(32, 27)
+    out = _z((n, Ho, Wo, 32), x)
+    for t, v in _stem_taps(x):
+        out += v.unsqueeze(-1) * wt[:, t]
+    return out
+
+
+def stem_patches(x):
+    """the im2col rows the kernel leaves for the weight gradient: [N, Ho, Wo, 32], column ci * 9 + ky * 3 + kx = that tap, columns 27..31 zero"""
+    n, _, H, W = x.shape
+    Ho, Wo = stem_out_hw(H, W)
+    out = _z((n, Ho, Wo, 32), x)
+    for t, v in _stem_taps(x):
+        out[..., t] = v
+    return out
+
+
+def stem_lds_path(N, H, W):
+    """bool [N, Ho, Wo]: True where the pixel leaves through the XOR-swizzled LDS rows (`!(Wo & 1) && (bidx + 1) * 256 <= total`: a whole
+    256-thread block of an even-width grid), False where its thread stores its own rows.  A thread owns the pixel pair (2 p, 2 p + 1) of
+    a row, `Wp = (Wo + 1) >> 1` pairs per row; the last pair of an odd row is a lone pixel."""
+    Ho, Wo = stem_out_hw(H, W)
+    Wp = (Wo + 1) >> 1
+    total = N * Ho * Wp
+    n, oy, ox = torch.meshgrid(torch.arange(N), torch.arange(Ho), torch.arange(Wo), indexing="ij")
+    bidx = ((n * Ho + oy) * Wp + ox // 2) // 256
+    return ((bidx + 1) * 256 <= total) & (Wo % 2 == 0)
+
+
 # ---- grouped 3x3, group width 8, zero pad 1; w [C][8][3][3] = w[o][i][ky][kx] -------------------------------------------------------------
 def gconv(x, w, stride):
     n, Hi, Wi, c = x.shape

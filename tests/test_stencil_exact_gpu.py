@@ -1049,3 +1049,70 @@ def test_fuse_dweights(K):
         for i in range(nw):
             if praw[i] <= 0:
                 assert float(got[i]) == 0.0
+
+
+# =====================================================================================================================================
+# stem: dense 3x3 / stride 2 from the fp32 NCHW frame, with its bf16 im2col rows
+# =====================================================================================================================================
+STEM = [
+    # name, N, H, W, store paths the case takes
+    ("partial_block", 2, 16, 24, "rows"),                  # 96 pixel pairs: thread-owned rows only
+    ("whole_blocks", 2, 64, 128, "lds"),                   # 2048 pairs: eight whole blocks through LDS
+    ("block_and_tail", 1, 34, 68, "both"),                 # 289 pairs: one whole block and a tail of 33
+    ("odd_wo", 3, 18, 22, "rows"),                         # Wo = 11: every row ends in a lone pixel
+    ("one_pixel", 1, 2, 2, "rows"),
+]
+
+
+def stem_hint(n, h, w):
+    lds = R.stem_lds_path(n, h, w)
+    wo = w >> 1
+
+    def hint(idx):
+        b, y, x = idx[:3]
+        out = ["XOR-swizzled LDS store path" if bool(lds[b, y, x]) else "thread-owned rows store path"]
+        out.append("second pixel of its thread" if x & 1 else ("lone pixel ending an odd row" if x == wo - 1 else "first pixel of its thread"))
+        if y in (0, (h >> 1) - 1) or x in (0, wo - 1):
+            out.append("border")
+        return ", ".join(out)
+    return hint
+
+
+@pytest.mark.parametrize("with_patches", [False, True], ids=["patches_null", "patches"])
+@pytest.mark.parametrize("case", STEM, ids=[c[0] for c in STEM])
+def test_stem_fwd(K, case, with_patches):
+    name, n, h, w, paths = case
+    budget(name, 27, 3, 3)                                  # 27 taps of |x| <= 3 times |w| <= 3: 243 <= 256, z is exact in bf16
+    lds = R.stem_lds_path(n, h, w)
+    assert {"rows": not bool(lds.any()), "lds": bool(lds.all()), "both": bool(lds.any()) and not bool(lds.all())}[paths]
+    ho, wo = R.stem_out_hw(h, w)
+    g = gen("stem" + name)
+    x, wt = ints((n, 3, h, w), -3, 3, g), ints((32, 3, 3, 3), -3, 3, g)
+    xg, wg = D(x.float().contiguous()), D(wt.float().contiguous())
+    z = out_bf(n * ho * wo, 32)
+    p = out_bf(n * ho * wo, 32)
+    call(K, "hn_stem_fwd", xg.data_ptr(), wg.data_ptr(), z.ptr(), p.ptr() if with_patches else None, n, h, w)
+    torch.cuda.synchronize()
+    z.check(f"hn_stem_fwd {name} z")
+    p.check(f"hn_stem_fwd {name} patches")
+    hint = stem_hint(n, h, w)
+    exact(z.view, R.stem(x, wt), f"hn_stem_fwd {name} z (patches {'on' if with_patches else 'null'})", hint)
+    if with_patches:
+        want = R.stem_patches(x)
+        exact(p.view, want, f"hn_stem_fwd {name} patches", hint, what="(n, y, x, tap)")
+        assert float(p.view.detach().double()[:, 27:].abs().sum()) == 0, f"hn_stem_fwd {name}: columns 27..31 of the patch rows are not zero"
+    else:
+        assert bool((p.buf.view(torch.int16) == 0x7FC1).all()), f"hn_stem_fwd {name} wrote patches without being given a buffer"
+
+
+def test_stem_refuses_an_odd_frame(K):
+    """`H >> 1` on an odd frame would drop conv2d's last output row (stencil_ref.stem_out_hw): the entry point refuses it, nothing is written"""
+    xg, wg = D(torch.zeros(1, 3, 17, 24)), D(torch.zeros(32, 3, 3, 3))
+    z, p = out_bf(8 * 12, 32), out_bf(8 * 12, 32)
+    raw = K.lib().raw("hn_stem_fwd")
+    st = torch.cuda.current_stream().cuda_stream
+    assert raw(xg.data_ptr(), wg.data_ptr(), z.ptr(), p.ptr(), 1, 17, 24, st) == 1
+    assert raw(xg.data_ptr(), wg.data_ptr(), z.ptr(), p.ptr(), 1, 16, 23, st) == 1
+    torch.cuda.synchronize()
+    for o in (z, p):
+        assert bool((o.buf.view(torch.int16) == 0x7FC1).all())

@@ -38,6 +38,47 @@ def nhwc(x):
 SIZES = [(2, 2), (2, 3), (3, 2), (3, 3), (4, 4), (4, 5), (5, 4), (5, 5), (7, 9), (1, 1), (6, 10)]
 
 
+STEM_SIZES = [(2, 2), (2, 4), (4, 2), (16, 24), (18, 22), (34, 68), (7, 10), (10, 7), (5, 5), (3, 2)]
+
+
+@pytest.mark.parametrize("hw", STEM_SIZES)
+def test_stem_against_torch(hw):
+    """even sizes: conv2d(stride 2, padding 1) itself.  Odd sizes: `H >> 1` drops conv2d's last row / column, keeps the others unchanged
+    and never reads the frame's last row / column (stencil_ref.stem_out_hw)"""
+    h, w = hw
+    n = 2
+    x, wt = rnd(n, 3, h, w), rnd(32, 3, 3, 3, seed=1)
+    y = F.conv2d(x, wt, stride=2, padding=1)
+    ho, wo = R.stem_out_hw(h, w)
+    assert (ho, wo) == (h // 2, w // 2) and y.shape[2:] == ((h + 1) // 2, (w + 1) // 2)
+    z = R.stem(x, wt)
+    assert z.shape == (n, ho, wo, 32)
+    close(z, nhwc(y[:, :, :ho, :wo]), "stem")
+    if h % 2 or w % 2:
+        x2 = x.clone()
+        if h % 2:
+            x2[:, :, h - 1, :] = 1e6
+        if w % 2:
+            x2[:, :, :, w - 1] = 1e6
+        assert torch.equal(R.stem(x2, wt), z), "the last row / column of an odd frame is read"
+    # patches: the unfold of the frame, tap ci * 9 + ky * 3 + kx, and z = patches . w
+    p = R.stem_patches(x)
+    u = F.unfold(x, 3, padding=1, stride=2).reshape(n, 27, (h + 1) // 2, (w + 1) // 2)[:, :, :ho, :wo]
+    assert torch.equal(p[..., :27], u.permute(0, 2, 3, 1)) and float(p[..., 27:].abs().sum()) == 0
+    close(p[..., :27] @ wt.reshape(32, 27).t(), z, "patches . w")
+
+
+def test_stem_store_paths():
+    """which pixels leave through LDS, for the shapes of the GPU test"""
+    assert not bool(R.stem_lds_path(2, 16, 24).any())                     # 96 pixel pairs: a partial block only
+    assert bool(R.stem_lds_path(2, 64, 128).all())                        # 2048 pairs: eight whole blocks
+    m = R.stem_lds_path(1, 34, 68)                                        # 289 pairs: one whole block and a tail of 33
+    assert int(m.sum()) == 512 and int((~m).sum()) == 17 * 34 - 512 and bool(m.reshape(-1)[:512].all())
+    assert not bool(R.stem_lds_path(3, 18, 22).any())                     # odd Wo = 11: thread-owned rows, every row ends in a lone pixel
+    assert R.stem_lds_path(1, 2, 2).shape == (1, 1, 1)
+    assert not bool(R.stem_lds_path(6, 32, 22).any()) and 6 * 16 * 6 >= 512   # odd Wo with whole blocks: still thread-owned
+
+
 @pytest.mark.parametrize("stride", [1, 2])
 @pytest.mark.parametrize("hw", SIZES)
 @pytest.mark.parametrize("c", [8, 24])
@@ -348,6 +389,9 @@ def test_argument_refusals(lib):
     """HN_CHECK_ARG returns 1 before any launch: the pointers are never dereferenced (1 stands for 'not null')"""
     P = 1
     r = lib.raw
+    assert r("hn_stem_fwd")(P, P, P, P, 1, 17, 24, None) == 1                                  # odd H: `H >> 1` would drop conv2d's last row
+    assert r("hn_stem_fwd")(P, P, P, None, 2, 16, 23, None) == 1                               # odd W
+    assert r("hn_stem_fwd")(P, P, P, P, 1, 1, 2, None) == 1                                    # H < 2
     assert r("hn_maxpool_fwd")(P, 8, P, 8, 1, 5, 4, 8, 0, None) == 1                           # odd H
     assert r("hn_maxpool_bwd")(P, 8, P, 8, P, 8, None, 1, 4, 5, 8, 0, None) == 1               # odd W
     assert r("hn_maxpool_bwd2")(P, 8, P, 8, P, 8, None, P, 1, 3, 4, 8, 0, 0, None) == 1
