@@ -75,6 +75,20 @@ int hn_nt_stat_rows(long M, int Nout);
 /* pixel rows summed into one partial row (64 or 128; the last tile may be ragged): a caller that reads the rows per IMAGE (the SE
  * gate-gradient partials, emode 1) needs H*W to be a multiple of it -- M / hn_nt_stat_rows is NOT the tile size when M is ragged */
 int hn_nt_stat_tile(long M, int Nout);
+/* hn_conv_gemm_nt for large maps of plain pixel rows with a short K (mode 0, one tap, one operand, bf16 output, no rpi mapping), as a
+ * persistent streaming launch: the [Nout][KP] weights stay in LDS, each workgroup walks 64-row pixel tiles of a static partition with the
+ * next tiles' operand DMA under the current tile's MFMAs and epilogue (no workgroup ever waits for another).
+ * Domain: hn_nt_stream_ok(M, C0, Nout, KP) -- KP <= 128, KP % 32 == 0, 64 < Nout <= 128, Nout % 8 == 0, C0 % 8 == 0, C0 <= KP and M in the
+ * range where hn_nt_stat_tile(M, Nout) == 64 -- with ld0 % 8 == 0, ldc % 8 == 0 and 16-byte aligned x, w, out.  Anything else returns
+ * HN_ERR_UNSUPPORTED and nothing is written.
+ * Contract: hn_conv_gemm_nt's on that domain, BIT FOR BIT: out = act(bf16(sum + bias)) with the same MFMA K order and rounding points, and
+ * psum / psq (optional) = the same [hn_nt_stat_rows(M, Nout)][Nout] partial rows -- row t = the sums over the live rows of pixel tile t
+ * (rows [64 t, 64 t + 64)) of q and q^2, q = bf16(sum + bias) before the activation, in the same summation order.
+ * wg_limit: 0 = a grid sized from the device (two workgroups per CU, at most one per tile); k > 0 = k workgroups, capped by that device
+ * size (tests: multi-tile walks, uneven shares and idle workgroups on tiny shapes; a tuning handle). */
+int hn_conv_gemm_nt_stream(const void* x, int ld0, long M, int C0, const void* w, int Nout, int KP, const float* bias, int act, void* out,
+                           int ldc, float* psum, float* psq, int wg_limit, hipStream_t stream);
+int hn_nt_stream_ok(long M, int C0, int Nout, int KP);
 /* mode 5 with psum/psq: one partial row per 16x16 output patch */
 int hn_direct_stat_rows(int n_img, int H, int W);
 /* Plain-rows 1x1 GEMM (hn_conv_gemm_nt mode 0, one tap, bf16 out) with ONE PACKED WEIGHT MATRIX PER IMAGE: rows [n * rows_per_image,

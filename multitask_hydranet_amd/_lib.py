@@ -31,7 +31,8 @@ def policy(name: str, default: str) -> str:
 SO_PATH = os.path.join(_PKG, "libhydranet_hip_tuning.so" if TUNING else "libhydranet_hip.so")
 SOURCES = ["hn_gemm.hip", "hn_norm.hip", "hn_fused.hip", "hn_stencil.hip", "hn_loss.hip", "hn_lovasz.hip", "hn_post.hip", "hn_xstage.hip", "hn_coco.hip",
            "hn_lane_encode.hip", "hn_augment.hip", "hn_jpeg.hip", "hn_jpeg_enc.hip", "hn_jpeg_huff.hip", "hn_jpeg_scan.hip", "hn_draw.hip", "hn_lane_metric.hip", "hn_png.hip", "hn_png_enc.hip",
-           "hn_lane_filter.hip", "hn_state.hip", "hn_accum.hip", "hn_ckpt.hip", "hn_det_loss.hip", "hn_det_atss.hip", "hn_det_tal.hip", "hn_lane_liou.hip"]
+           "hn_lane_filter.hip", "hn_state.hip", "hn_accum.hip", "hn_ckpt.hip", "hn_det_loss.hip", "hn_det_atss.hip", "hn_det_tal.hip", "hn_lane_liou.hip",
+           "hn_gemm_stream.hip"]
 
 _ERR = {1: "bad argument", 2: "kernel launch failure", 3: "unsupported shape"}
 

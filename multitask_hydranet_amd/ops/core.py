@@ -340,6 +340,31 @@ def pack_dw_weight(w: torch.Tensor):
 # --------------------------------------------------------------------------------------------------------------
 # raw kernel wrappers (no autograd)
 # --------------------------------------------------------------------------------------------------------------
+NT_STREAM = policy("HN_NT_STREAM", "1") != "0"   # large-map short-K 1x1 GEMMs on hn_conv_gemm_nt_stream (same results bit for bit; False: hn_conv_gemm_nt)
+NT_STREAM_MAX_ROWS = 262144                      # the 64-row statistics tiling of hn_conv_gemm_nt ends here (its small_tile branch)
+# Smallest row count routed to the streaming kernel, from the per-shape table of profiles/nt_stream.md (tools/bench_nt_stream.py, 112 -> 112):
+# at 32 768 rows it beats the 64 x 64 tile by 8 % (15 % with statistics) against a replay spread of the tile kernel of 0.4 % (1.5 %), and at
+# every larger measured shape (131 072, 174 592 rows) by 14-36 % against spreads of 1-6 %; at 8 192 and 2 048 rows (one tile or less per
+# workgroup: nothing to pipeline, a longer prologue) it is 1-4 % slower.
+NT_STREAM_MIN_ROWS = 32768
+
+
+def nt_stream_ok(m: int, c0: int, nout: int, kp: int) -> bool:
+    """the domain of hn_conv_gemm_nt_stream (hn_nt_stream_ok states the same predicate on the library side)"""
+    return (0 < m <= NT_STREAM_MAX_ROWS and 0 < kp <= 128 and kp % 32 == 0 and 64 < nout <= 128 and nout % 8 == 0
+            and 0 < c0 <= kp and c0 % 8 == 0)
+
+
+def nt_stream_route(x0, x1, mode, taps, m, c0, nout, kp, out, out_f32, ldc, rpi, xform, addend) -> bool:
+    """k_gemm_nt launches that take the streaming kernel: plain pixel rows of one tensor, bf16 output, no epilogue options beyond bias /
+    activation / BatchNorm statistics, inside the kernel's domain and large enough to gain from it"""
+    if not NT_STREAM or mode != 0 or taps != 1 or x1 is not None or out_f32 or rpi or xform is not None or addend is not None:
+        return False
+    if m < NT_STREAM_MIN_ROWS or not nt_stream_ok(m, c0, nout, kp):
+        return False
+    return ld(x0) % 8 == 0 and ldc % 8 == 0 and x0.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0
+
+
 def k_gemm_nt(x0, x1, mode, grid, wp, nout, kp, taps, bias=None, act=ACT_NONE, out=None, out_f32=False, up=0, stats=False,
               c0=None, c1=None, rpi=0, img_stride=0, ldc=None, xform=None, addend=None, add_pre=False, add_s2=False, estat=None):
     """grid = (N, H, W) of the OUTPUT pixel grid.  Returns (out, psum, psq).
@@ -373,6 +398,8 @@ def k_gemm_nt(x0, x1, mode, grid, wp, nout, kp, taps, bias=None, act=ACT_NONE, o
         lib().call("hn_conv_gemm_nt_stat", ptr(x0), ptr(x1), mode, n, h, w, c0, c1, ld(x0), ld(x1) if x1 is not None else 0, up, m,
                    ptr(wp), nout, kp, taps, ptr(bias), act, ptr(out), 0, ldc, rpi, img_stride, ptr(psum), ptr(psq), ptr(addend),
                    ld(addend) if addend is not None else 0, 1 if add_s2 else 0, emode, ptr(ez), ld(ez), ptr(ecoef))
+    elif nt_stream_route(x0, x1, mode, taps, m, c0, nout, kp, out, out_f32, ldc, rpi, xform, addend):
+        lib().call("hn_conv_gemm_nt_stream", ptr(x0), ld(x0), m, c0, ptr(wp), nout, kp, ptr(bias), act, ptr(out), ldc, ptr(psum), ptr(psq), 0)
     elif xform is None and addend is None:
         lib().call("hn_conv_gemm_nt", ptr(x0), ptr(x1), mode, n, h, w, c0, c1, ld(x0), ld(x1) if x1 is not None else 0, up, m,
                    ptr(wp), nout, kp, taps, ptr(bias), act, ptr(out), 1 if out_f32 else 0, ldc, rpi, img_stride, ptr(psum), ptr(psq))
