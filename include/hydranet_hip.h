@@ -39,7 +39,7 @@ int hn_pack_weight_ex(const float* w, void* wp, void* wt, int Cout, int Cin_tota
 int hn_phase_fold(const float* dw_eff, const float* dw1, const float* db_eff, float* dw, float* db, int K, int C0, int C1, hipStream_t stream);
 /* every conv weight of a model in one launch: jobs = DEVICE table njobs x 8 int64 {w, wp, wt, Cout, Cin, taps, first_block, ci_tiles}; job j
  * owns one block per 32 x 32 (cout, cin) tile -- (KP(Cout)/32) * ci_tiles blocks with ci_tiles = KP(Cin)/32 -- starting at first_block;
- * the tile passes through LDS so that both operand layouts are written in contiguous runs.  taps = 1 or 9.  block_job (optional, DEVICE
+ * the tile passes through LDS so that both operand layouts are written in contiguous runs.  taps = 1 or 9 (a job with any other value packs nothing).  block_job (optional, DEVICE
  * int32 [total_blocks]) = job index of every block (otherwise each block searches the table). */
 int hn_pack_weights_batched(const long* jobs, int njobs, long total_blocks, const int* block_job, hipStream_t stream);
 /* the remaining per-step packs of a model (depthwise taps = hn_dw_pack, grouped-conv stencil operands = hn_gconv_pack, block-diagonal MFMA

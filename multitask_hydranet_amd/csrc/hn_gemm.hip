@@ -4214,7 +4214,7 @@ extern "C" int hn_conv_gemm_tn_phase(const void* x0, int n_img, int H, int W, in
 
 /* jobs: DEVICE table of njobs x 8 int64 {w, wp, wt, Cout, Cin, taps, first_block, ci_tiles}; job j owns blocks [first_block_j,
  * first_block_{j+1}) of 256 threads, one per 32 x 32 (cout, cin) tile: (KP(Cout)/32) * ci_tiles with ci_tiles = KP(Cin)/32; total_blocks =
- * their sum.  taps <= 9. */
+ * their sum.  taps = 1 or 9 (a job with any other value packs nothing). */
 extern "C" int hn_pack_weights_batched(const long* jobs, int njobs, long total_blocks, const int* block_job, hipStream_t st) {
     HN_CHECK_ARG(jobs && njobs > 0 && total_blocks > 0);
     hipLaunchKernelGGL(pack_w_batched_kernel, dim3((unsigned)total_blocks), dim3(256), 0, st, jobs, njobs, block_job);

@@ -1146,13 +1146,22 @@ __global__ __launch_bounds__(256) void adam_step_kernel(const long* jobs, const 
     const long n = jb[4];
     const long i0 = (((long)blockIdx.x - jb[5]) * 256 + threadIdx.x) * 4;
     if (i0 >= n) return;
+    // Every operation below is rounded on its own: plain operators under contract(off), one per statement, and the correctly rounded
+    // square root.  (The __f*_rn intrinsics do not give that here: to this compiler __fmul_rn / __fadd_rn are the plain operators under
+    // HIP's default -ffp-contract=fast-honor-pragmas -- the four product-and-sum pairs below compiled to v_pk_fma_f32 -- and __fsqrt_rn is
+    // the native v_sqrt_f32 without its refinement; ema_lerp_rn in hn_common.h met the same.  tests/adam_ref.py restates the sequence in
+    // numpy float32 and tests/test_adam_exact_gpu.py holds p, m and v to it bit for bit.)
     auto one = [&](float pv, float gv, float& mv, float& vv) {
-        if constexpr (GUARDED) gv = __fmul_rn(gv, coef);                               // clip_grad_norm_'s grad.mul_(clip_coef), not stored
-        if (wd != 0.f) gv = __fadd_rn(gv, __fmul_rn(wd, pv));
-        mv = __fadd_rn(mv, __fmul_rn(w1, __fsub_rn(gv, mv)));                          // exp_avg.lerp_(grad, 1 - beta1)
-        vv = __fadd_rn(__fmul_rn(vv, b2), __fmul_rn(w2, __fmul_rn(gv, gv)));           // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
-        const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(vv), bc2_sqrt), eps);
-        return __fsub_rn(pv, __fmul_rn(lr_over_bc1, __fdiv_rn(mv, denom)));            // param.addcdiv_(exp_avg, denom, value = -step_size)
+#pragma clang fp contract(off)
+        if constexpr (GUARDED) gv = gv * coef;                                         // clip_grad_norm_'s grad.mul_(clip_coef), not stored
+        if (wd != 0.f) { const float t = wd * pv; gv = gv + t; }
+        const float d = gv - mv, t1 = w1 * d;
+        mv = mv + t1;                                                                  // exp_avg.lerp_(grad, 1 - beta1)
+        const float g2 = gv * gv, t2 = w2 * g2, t3 = vv * b2;
+        vv = t3 + t2;                                                                  // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
+        const float r = __builtin_sqrtf(vv), q = r / bc2_sqrt, denom = q + eps;
+        const float u = mv / denom, t4 = lr_over_bc1 * u;
+        return pv - t4;                                                                // param.addcdiv_(exp_avg, denom, value = -step_size)
     };
     // ONE arithmetic instruction stream for both operand forms (whole aligned float4s / element by element): the vector and the scalar
     // branch used to carry their own copies of `one`, and the two compiled forms differed by an ulp on a few elements per tensor -- a

@@ -64,6 +64,21 @@ def exact(got, want, name, what="partial row"):
         pytest.fail(f"{name}: {n} of {g.numel()} values differ\n" + "\n".join(lines))
 
 
+def same_bits(got, want, name, what="index"):
+    """integer views of two tensors (bf16 as int16, fp32 as int32, bytes as uint8) equal bit for bit -- -0 is not +0, and a NaN sentinel
+    a kernel left in place is a mismatch; names the first bad indices with both patterns in hex"""
+    g = got.detach().cpu()
+    w = want.reshape(g.shape)
+    assert g.dtype == w.dtype and not g.dtype.is_floating_point, f"{name}: same_bits compares integer views ({g.dtype} against {w.dtype})"
+    bad = g != w
+    n = int(bad.sum())
+    if n:
+        mask = (1 << (8 * g.element_size())) - 1
+        lines = [f"  {what} {tuple(i)}: got 0x{int(g[tuple(i)]) & mask:0{2 * g.element_size()}x} want 0x{int(w[tuple(i)]) & mask:0{2 * g.element_size()}x}"
+                 for i in bad.nonzero()[:6].tolist()]
+        pytest.fail(f"{name}: {n} of {g.numel()} values differ bit for bit\n" + "\n".join(lines))
+
+
 def within(got, want, bound, name, what="channel"):
     """|got - want| <= bound elementwise (1-D per-channel vectors or [rows, C])"""
     g = got.detach().double().cpu()
