@@ -1,6 +1,6 @@
 """Sentinel guard bands around kernel outputs, shared by the exact kernel tests (test_gemm_exact_gpu.py, test_batchnorm_exact_gpu.py, test_loss_exact_gpu.py,
 test_se_exact_gpu.py, test_eltwise_exact_gpu.py, test_gemm_forms_exact_gpu.py, test_gemm_epilogue_exact_gpu.py, test_post_exact_gpu.py,
-test_pack_exact_gpu.py, test_adam_exact_gpu.py, test_copy_many_exact_gpu.py, test_grad_tail_exact_gpu.py).
+test_pack_exact_gpu.py, test_adam_exact_gpu.py, test_copy_many_exact_gpu.py, test_grad_tail_exact_gpu.py, test_lovasz_exact_gpu.py).
 
 An output is a view into a larger buffer filled with a NaN bit pattern that no kernel produces: BAND elements before and after the output
 and, when the row stride ld exceeds the column count, the ld - cols columns between its rows.  check() fails on any guard element a
