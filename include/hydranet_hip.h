@@ -776,6 +776,24 @@ int hn_argmax_channels(const float* logits, int ldl, int C, long M, long* out, h
 int hn_weighted_sum(const void* const* xs, const float* w, const float* gw, const int* grp, int n, const float* gout, float* out, float* grads,
                     hipStream_t stream);
 
+/* The same sum under learned homoscedastic-uncertainty weights (train.loss_balance: uncertainty; Kendall, Gal and Cipolla 2018), one
+ * launch of one wave, no atomics, no allocation: with s~_i = min(max(s[slot_i], -clamp), clamp) and e_i = expf(-s~_i),
+ *   total = [ sum_g ( sum_{i in g, active} (x_i*w_i)*e_i ) * gw_g ] + sum_{i active} s~_i      (term i is active when x_i != 0)
+ * in hn_weighted_sum's order, the s~ added last in term order, every operation rounded on its own; at s = 0 total and grads are
+ * hn_weighted_sum's bits.  slot (HOST [n], strictly increasing, < n_slots <= 8): the entry of s / ds that term i owns; s (DEVICE fp32
+ * [n_slots]) is read at those entries only.  0 < clamp <= 80.  record (DEVICE fp32 [16], always): e_i by term, then 1.0 / 0.0 = term i
+ * active, the rest 0.0 -- written by a call with `out`, read by a call without.  With grads (needs gout and ds): grads [n] =
+ * ((gout * gw_g) * w_i) * e_i; ds (DEVICE fp32 [2 * n_slots]), every entry written: ds[slot_i] = gout * (1 - t_i * gw_g) for an active
+ * term whose s is inside the clamp, or at / outside it when a descent step moves it back inside, else 0.0; ds[n_slots + slot] = 1.0 for
+ * the slot of an active term, else 0.0. */
+int hn_balanced_sum(const void* const* xs, const float* w, const float* gw, const int* grp, const int* slot, int n, int n_slots,
+                    const float* s, float clamp, const float* gout, float* out, float* record, float* grads, float* ds, hipStream_t stream);
+
+/* Before / after the Adam step of the log-variances: hold (DEVICE fp32 [3 * n]) takes s, m, v (act == NULL), or gives them back to every
+ * slot i with !(act[i] > 0) (act: DEVICE fp32 [n], hn_balanced_sum's activity or its mean over accumulated micro-batches), so that an
+ * inactive or untrained slot keeps its value and both moments to the bit.  n <= 8. */
+int hn_balance_hold(float* s, float* m, float* v, float* hold, const float* act, int n, hipStream_t stream);
+
 /* Adam step of all parameters in one launch (torch.optim.Adam as model/train.py:147 constructs it: L2 weight decay on the gradient, bias
  * correction, eps outside the square root; not amsgrad).  jobs (DEVICE) = n x 6 int64 {p, g, m, v (fp32 pointers), numel, first_block};
  * a block = 256 threads x 4 consecutive elements of one tensor; block_job (DEVICE int32 [total_blocks]) = job index of every block;

@@ -1107,6 +1107,121 @@ extern "C" int hn_weighted_sum(const void* const* xs, const float* w, const floa
     HN_LAUNCH_CHECK();
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The same sum under learned homoscedastic-uncertainty weights (Kendall, Gal and Cipolla, CVPR 2018; train.loss_balance): one
+// log-variance s per term, clamped to [-S, S],
+//   e_i = expf(-s~_i)     t_i = (x_i * w_i) * e_i     total = [ sum_g ( sum_{i in g} t_i ) * gw_g ] + sum_{i active} s~_i
+// the bracket in weighted_sum_kernel's order, the regulariser added last in term order, every operation rounded on its own.  A term is
+// ACTIVE when x_i != 0 (a masked task, a head without positives): an inactive term adds neither t_i nor s~_i and its ds is 0 -- ds = 1
+// would push s down without bound.  Backward: dx_i = ((gout * gw_g) * w_i) * e_i; ds_i = gout * (1 - t_i * gw_g) inside the clamp, and at
+// or outside it only when a descent step (s -= lr * ds) moves s back inside.  At s = 0: expf(0) = 1, x * 1 and + 0 are exact, so total
+// and every dx_i are weighted_sum_kernel's bits.
+// record (fp32 [2 * HN_MAX_LOSS_TERMS], by term): e_i, then 1.0 / 0.0 = active; ds (fp32 [2 * n_slots], by slot): the gradient, then
+// 1.0 / 0.0 = the slot's term was active.  Every entry is written: an unused one as 0.0.
+// ---------------------------------------------------------------------------------------------------------
+struct BSum {
+    WSum ws; int slot[HN_MAX_LOSS_TERMS]; int n_slots; const float* s; float clamp; float* record; float* ds;
+};
+__global__ void balanced_sum_kernel(const BSum p) {
+#pragma clang fp contract(off)
+    if (threadIdx.x != 0) return;
+    const WSum& q = p.ws;
+    float e[HN_MAX_LOSS_TERMS], sc[HN_MAX_LOSS_TERMS], x[HN_MAX_LOSS_TERMS];
+    bool act[HN_MAX_LOSS_TERMS];
+#pragma unroll
+    for (int i = 0; i < HN_MAX_LOSS_TERMS; ++i) {
+        e[i] = 0.f; sc[i] = 0.f; x[i] = 0.f; act[i] = false;
+        if (i < q.n) {
+            x[i] = q.x[i][0];
+            act[i] = x[i] != 0.f;
+            sc[i] = fminf(fmaxf(p.s[p.slot[i]], -p.clamp), p.clamp);
+            if (q.out) e[i] = expf(-sc[i]);
+            else e[i] = p.record[i];                        // backward alone: the forward's multipliers
+        }
+    }
+    if (q.out) {
+        float tot = 0.f;
+        int i = 0;
+        while (i < q.n) {
+            const int g = q.grp[i];
+            float s = 0.f;
+            bool first = true;
+            for (; i < q.n && q.grp[i] == g; ++i) {
+                if (!act[i]) continue;
+                const float xw = x[i] * q.w[i];
+                const float t = xw * e[i];
+                s = first ? t : s + t;
+                first = false;
+            }
+            const float sg = s * q.gw[g];
+            tot = tot + sg;
+        }
+        for (int i = 0; i < q.n; ++i)
+            if (act[i]) tot = tot + sc[i];
+        q.out[0] = tot;
+#pragma unroll
+        for (int i = 0; i < HN_MAX_LOSS_TERMS; ++i) {
+            p.record[i] = i < q.n ? e[i] : 0.f;
+            p.record[HN_MAX_LOSS_TERMS + i] = (i < q.n && act[i]) ? 1.f : 0.f;
+        }
+    }
+    if (q.grads) {
+        const float go = q.gout[0];
+        for (int k = 0; k < 2 * p.n_slots; ++k) p.ds[k] = 0.f;
+        for (int i = 0; i < q.n; ++i) {
+            const float gwi = q.gw[q.grp[i]];
+            const float gg = go * gwi;
+            const float gw_ = gg * q.w[i];
+            q.grads[i] = gw_ * e[i];                        // (also of an inactive term: at s = 0 the parent's seed, whatever x_i is)
+            if (!act[i]) continue;
+            const float xw = x[i] * q.w[i];
+            const float t = xw * e[i];
+            const float u = t * gwi;
+            const float v = 1.f - u;
+            const float d = go * v;
+            const float sv = p.s[p.slot[i]];
+            const bool keep = (sv > -p.clamp && sv < p.clamp) || (sv >= p.clamp && d > 0.f) || (sv <= -p.clamp && d < 0.f);
+            p.ds[p.slot[i]] = keep ? d : 0.f;
+            p.ds[p.n_slots + p.slot[i]] = 1.f;
+        }
+    }
+}
+/* hn_weighted_sum's arguments, plus: slot (HOST, [n], strictly increasing, < n_slots <= 8): the entry of s / ds that term i owns; s (DEVICE
+ * fp32 [n_slots]): the log-variances, read at the n slots only; clamp = S > 0; record (DEVICE fp32 [16], always): written by a forward
+ * call, read by a call without `out`; ds (DEVICE fp32 [2 * n_slots], with grads). */
+extern "C" int hn_balanced_sum(const void* const* xs, const float* w, const float* gw, const int* grp, const int* slot, int n, int n_slots,
+                               const float* s, float clamp, const float* gout, float* out, float* record, float* grads, float* ds,
+                               hipStream_t st) {
+    HN_CHECK_ARG(xs && w && gw && grp && slot && n > 0 && n <= HN_MAX_LOSS_TERMS && n_slots >= n && n_slots <= HN_MAX_LOSS_TERMS);
+    HN_CHECK_ARG(s && record && clamp > 0.f && clamp <= 80.f && (out || grads) && (!grads || (gout && ds)));
+    BSum p = {};
+    for (int i = 0; i < n; ++i) {
+        HN_CHECK_ARG(xs[i] && grp[i] >= 0 && grp[i] < HN_MAX_LOSS_TERMS && (i == 0 || grp[i] >= grp[i - 1]));
+        HN_CHECK_ARG(slot[i] >= 0 && slot[i] < n_slots && (i == 0 || slot[i] > slot[i - 1]));
+        p.ws.x[i] = (const float*)xs[i]; p.ws.w[i] = w[i]; p.ws.grp[i] = grp[i]; p.slot[i] = slot[i];
+    }
+    for (int g = 0; g <= grp[n - 1]; ++g) p.ws.gw[g] = gw[g];
+    p.ws.n = n; p.ws.gout = gout; p.ws.out = out; p.ws.grads = grads;
+    p.n_slots = n_slots; p.s = s; p.clamp = clamp; p.record = record; p.ds = ds;
+    hipLaunchKernelGGL(balanced_sum_kernel, dim3(1), dim3(64), 0, st, p);
+    HN_LAUNCH_CHECK();
+}
+
+// Adam steps every element of the log-variance tensor; a slot whose term was inactive (or is not trained in this phase) must keep s and
+// both moments to the bit.  hold (fp32 [3 * n]): act == nullptr copies s, m, v into it (before the step); otherwise slot i is written
+// back from it where !(act[i] > 0) (after the step; act = the ds vector's second half, or its mean over a group of micro-batches).
+__global__ void balance_hold_kernel(float* s, float* m, float* v, float* hold, const float* act, int n) {
+    const int i = threadIdx.x;
+    if (i >= n) return;
+    if (!act) { hold[i] = s[i]; hold[n + i] = m[i]; hold[2 * n + i] = v[i]; return; }
+    if (!(act[i] > 0.f)) { s[i] = hold[i]; m[i] = hold[n + i]; v[i] = hold[2 * n + i]; }
+}
+extern "C" int hn_balance_hold(float* s, float* m, float* v, float* hold, const float* act, int n, hipStream_t st) {
+    HN_CHECK_ARG(s && m && v && hold && n > 0 && n <= HN_MAX_LOSS_TERMS);
+    hipLaunchKernelGGL(balance_hold_kernel, dim3(1), dim3(64), 0, st, s, m, v, hold, act, n);
+    HN_LAUNCH_CHECK();
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Adam step of ALL parameters in one launch (torch.optim.Adam as the reference constructs it, model/train.py:147: L2 weight decay added to
 // the gradient, bias-corrected moments, eps outside the square root).  The foreach implementation is ~10 launches over 693 tensor lists

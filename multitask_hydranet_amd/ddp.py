@@ -95,6 +95,9 @@ class GradReducer:
         self.capture_stream = None              # set_capture_stream(): where the in-line captured exchange is enqueued
         self._pending_uploads = []              # gather tables filled during a capture, uploaded by adopt_bucket_grads()
         self._hooks = []
+        # small fp32 device tensors that a backward writes in place before any parameter gradient exists (the log-variances' gradient
+        # of train.loss_balance): averaged over the ranks in place, by a collective of their own issued with the LAST bucket's
+        self.extras: List[torch.Tensor] = []
         self.arm()
 
     # ------------------------------------------------------------------------------------------------------------------------------
@@ -203,6 +206,12 @@ class GradReducer:
             if self.world > 1:
                 flat.mul_(1.0 / self.world)
 
+    def _exchange_extras(self, b):
+        """with the last bucket (every step launches it): the extras, averaged in place on the stream the bucket's exchange runs on"""
+        if b is self.buckets[-1]:
+            for t in self.extras:
+                self._allreduce_mean(t)
+
     def _launch(self, b):
         if not self.active:
             return
@@ -227,6 +236,7 @@ class GradReducer:
                                    "steps on the capture stream (torch.cuda.graph(g, stream=warmup_stream))" % (torch.cuda.current_stream(), cs))
             self._gather(b)
             self._allreduce_mean(b["flat"])
+            self._exchange_extras(b)
             if b["land"] is not None:
                 self._copy_many(b, "plan_land", b["land"], b["views"], 2)
         elif self.stream is not None:
@@ -236,6 +246,7 @@ class GradReducer:
             with torch.cuda.stream(self.stream):
                 self._gather(b)
                 self._allreduce_mean(b["flat"])
+                self._exchange_extras(b)
                 if b["land"] is not None:
                     self._copy_many(b, "plan_land", b["land"], b["views"], 2)
                 done = torch.cuda.Event()
@@ -246,6 +257,7 @@ class GradReducer:
         else:
             self._gather(b)
             self._point(b)
+            self._exchange_extras(b)
             b["work"] = dist.all_reduce(b["flat"], op=dist.ReduceOp.SUM, group=self.group, async_op=True)
 
     def _point(self, b):

@@ -130,6 +130,8 @@ class HydraNet(nn.Module):
         self.grad_scope = None              # "lane" | "det" | "seg": head-only fine-tuning phase (see _forward)
         self.det_pos_iou = None             # mean IoU of the positive anchors at the last cal_loss under an IoU loss_reg_type (device scalar)
         self.lane_pos_liou = None           # mean line IoU of the positive lane anchors at the last cal_loss under lane.loss_loc_type: liou
+        self.loss_log_vars = None           # enable_loss_balance(): fp32 [6] log-variances, one per loss term (plain tensors: no state_dict key)
+        self.loss_log_vars_grad = None
 
         spec = _Spec(self)
         self._declare_backbone(spec)
@@ -1007,9 +1009,69 @@ class HydraNet(nn.Module):
             ld["loss_lane_cls_pos"], ld["loss_lane_cls_neg"], ld["loss_lane_loc"] = pos, neg, loc
         return ld
 
+    # train.loss_balance: uncertainty.  The fixed slot of every loss term in loss_log_vars, in total_loss's order.
+    LOSS_BALANCE_SLOTS = ("loss_seg", "loss_det_cls", "loss_det_reg", "loss_lane_cls_pos", "loss_lane_cls_neg", "loss_lane_loc")
+
+    def enable_loss_balance(self, clamp: float = 6.0, init: float = 0.0):
+        """learned homoscedastic-uncertainty weights in total_loss (ops.balanced_loss_sum): one log-variance per loss term in ONE fp32
+        device tensor, loss_log_vars [6] (LOSS_BALANCE_SLOTS; every slot starts at `init`).  total_loss's backward writes d total / d s
+        into loss_log_vars_grad [6] -- a view of loss_balance_grad_act [12], whose second half is the slots' activity -- and its forward
+        writes exp(-s) and the activity per term into a record.  All of it plain tensors of one allocation: neither parameters nor
+        buffers, so state_dict() keeps its keys; who steps the log-variances (HydraTrainer) owns their optimizer.  Call it once the
+        module is on its device."""
+        clamp = K.loss_balance_clamp(clamp)
+        if isinstance(init, bool) or not isinstance(init, (int, float)) or not abs(float(init)) <= clamp:
+            raise ValueError("the log-variances' initial value must be a number within the clamp +-%r, got %r" % (clamp, init))
+        n = len(self.LOSS_BALANCE_SLOTS)
+        dev = next(self.parameters()).device
+        mem = torch.zeros((3 * n + 2 * K.BALANCE_MAX_TERMS,), device=dev, dtype=torch.float32)      # s | ds | activity | record: one read
+        self._loss_balance_mem = mem
+        self.loss_log_vars = mem[:n]
+        self.loss_balance_grad_act = mem[n:3 * n]
+        self.loss_log_vars_grad = mem[n:2 * n]
+        self._loss_balance_record = mem[3 * n:]
+        self.loss_log_vars.fill_(float(init))
+        self.loss_balance_clamp = clamp
+
+    def _loss_balance_terms(self):
+        """the loss terms the current phase trains, in slot order: all of the trained tasks', or one head's in a head-only phase"""
+        on = dict(seg=self.train_seg, det=self.train_detect, lane=self.train_lane)
+        if self.grad_scope is not None:
+            on = {k: v and k == self.grad_scope for k, v in on.items()}
+        return [n for n in self.LOSS_BALANCE_SLOTS if on[n.split("_")[1]]]
+
+    @property
+    def loss_balance(self):
+        """{loss name: (s, exp(-clamped s) of the last total_loss, active there)} of the terms the last total_loss summed (one
+        device-to-host read); None before enable_loss_balance"""
+        if self.loss_log_vars is None:
+            return None
+        n = len(self.LOSS_BALANCE_SLOTS)
+        host = self._loss_balance_mem.cpu()
+        s, rec = host[:n].tolist(), host[3 * n:].tolist()
+        return {name: (s[self.LOSS_BALANCE_SLOTS.index(name)], rec[i], rec[K.BALANCE_MAX_TERMS + i] != 0.0)
+                for i, name in enumerate(getattr(self, "_loss_balance_last", ()))}
+
     def total_loss(self, ld):
         """HydraTrainer.cal_total_loss, model/train.py:192-203."""
         c = self.cfgs
+        if self.loss_log_vars is not None:
+            if not all(isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.float32 for v in ld.values()):
+                raise ValueError("train.loss_balance sums fp32 device losses (hn_balanced_sum); there is no host form of it")
+            names = self._loss_balance_terms()
+            groups = []
+            if "loss_seg" in names:
+                groups.append((1.0, [(ld["loss_seg"], c["segment"]["segment_weight"])]))
+            if "loss_det_cls" in names:
+                d = c["detection"]
+                groups.append((d["detection_weight"], [(ld["loss_det_cls"], d["loss_cls_weight"]), (ld["loss_det_reg"], d["loss_reg_weight"])]))
+            if "loss_lane_loc" in names:
+                l = c["lane"]
+                groups.append((l["lane_weight"], [(ld["loss_lane_cls_pos"], l["loss_cls_pos_weight"]),
+                                                  (ld["loss_lane_cls_neg"], l["loss_cls_neg_weight"]), (ld["loss_lane_loc"], l["loss_loc_weight"])]))
+            self._loss_balance_last = tuple(names)
+            return K.balanced_loss_sum(groups, self.loss_log_vars, self.loss_balance_grad_act, self.loss_balance_clamp,
+                                       slots=[self.LOSS_BALANCE_SLOTS.index(n) for n in names], record=self._loss_balance_record)
         if all(isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.float32 for v in ld.values()):
             groups = []                                      # one launch (fwd) + one (bwd) instead of ~22 scalar torch kernels
             if self.train_seg:

@@ -662,4 +662,78 @@ def weighted_loss_sum(groups):
     return WeightedLossSum.apply((tuple(w), tuple(gw), tuple(grp)), *xs)
 
 
+# --------------------------------------------------------------------------------------------------------------
+# train.loss_balance: uncertainty: the same sum under one learned log-variance per term, hn_balanced_sum.
+# --------------------------------------------------------------------------------------------------------------
+BALANCE_MAX_TERMS = 8                                          # HN_MAX_LOSS_TERMS
+
+
+def loss_balance_clamp(clamp):
+    """the clamp S of the log-variances as a float; ValueError unless it is a finite number in (0, 80] (expf(80) is finite in fp32)"""
+    if isinstance(clamp, bool) or not isinstance(clamp, (int, float)) or not (0.0 < float(clamp) <= 80.0):
+        raise ValueError(f"the log-variance clamp must be a number in (0, 80], got {clamp!r}")
+    return float(clamp)
+
+
+class BalancedLossSum(torch.autograd.Function):
+    """total = [sum_g (sum_{i in g} (x_i * w_i) * exp(-s_i)) * gw_g] + sum_i s_i over the active terms (x_i != 0), s clamped to +-clamp;
+    meta = (w, gw, group ids, slots, clamp, log_vars, grad_out, record): log_vars fp32 [n_slots] on the device, grad_out fp32
+    [2 * n_slots] (backward writes d total / d s and the slots' activity there: a caller-owned static tensor, not a leaf's .grad),
+    record fp32 [16] (forward writes exp(-s) and the activity per term)."""
+
+    @staticmethod
+    def forward(ctx, meta, *xs):
+        w, gw, grp, slots, clamp, s, ds, record = meta
+        n, ns = len(xs), s.numel()
+        ctx.shapes = [x.shape for x in xs]
+        xs = [x.reshape(1) for x in xs]
+        assert all(x.dtype == F32 and x.is_cuda for x in xs)
+        for t, k in ((s, ns), (ds, 2 * ns), (record, 2 * BALANCE_MAX_TERMS)):
+            assert t.dtype == F32 and t.is_cuda and t.is_contiguous() and t.numel() == k and not t.requires_grad
+        out = torch.empty((1,), device=xs[0].device, dtype=F32)
+        ctx.host = (_ptr_array(xs), (ctypes.c_float * n)(*w), (ctypes.c_float * len(gw))(*gw), (ctypes.c_int * n)(*grp),
+                    (ctypes.c_int * n)(*slots), n, ns, clamp)
+        pa, wa, ga, ia, sa, _, _, _ = ctx.host
+        lib().call("hn_balanced_sum", ctypes.addressof(pa), ctypes.addressof(wa), ctypes.addressof(ga), ctypes.addressof(ia),
+                   ctypes.addressof(sa), n, ns, ptr(s), clamp, None, ptr(out), ptr(record), None, None)
+        ctx.keep = (xs, s, ds, record)                    # the pointer table refers to these
+        return out.view(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        pa, wa, ga, ia, sa, n, ns, clamp = ctx.host
+        _, s, ds, record = ctx.keep
+        grads = torch.empty((n,), device=gout.device, dtype=F32)
+        g = gout.reshape(1)
+        if g.dtype != F32:
+            g = g.float()
+        lib().call("hn_balanced_sum", ctypes.addressof(pa), ctypes.addressof(wa), ctypes.addressof(ga), ctypes.addressof(ia),
+                   ctypes.addressof(sa), n, ns, ptr(s), clamp, ptr(g), None, ptr(record), ptr(grads), ptr(ds))
+        return (None, *[grads[i:i + 1].view(shape) for i, shape in enumerate(ctx.shapes)])
+
+
+def balanced_loss_sum(groups, log_vars, grad_out, clamp, slots=None, record=None):
+    """groups = [(group weight, [(loss tensor, weight), ...]), ...] as for weighted_loss_sum -> the total under learned uncertainty
+    weights.  log_vars: fp32 device tensor of the log-variances; slots: the entry of it each term owns, in term order, strictly
+    increasing (default 0, 1, ...); grad_out: fp32 [2 * len(log_vars)], written by backward (d total / d log_vars, then 1.0 / 0.0 per
+    slot = its term was active); record (default: a fresh tensor): fp32 [16], written by forward."""
+    xs, w, gw, grp = [], [], [], []
+    for gi, (gweight, terms) in enumerate(groups):
+        gw.append(float(gweight))
+        for x, wi in terms:
+            xs.append(x)
+            w.append(float(wi))
+            grp.append(gi)
+    slots = tuple(range(len(xs))) if slots is None else tuple(int(k) for k in slots)
+    ns = log_vars.numel()
+    if not xs or len(xs) > BALANCE_MAX_TERMS or ns > BALANCE_MAX_TERMS or len(slots) != len(xs):
+        raise ValueError(f"balanced_loss_sum takes 1 to {BALANCE_MAX_TERMS} terms and one slot per term: got {len(xs)} terms, {len(slots)} slots, "
+                         f"{ns} log-variances")
+    if any(not 0 <= k < ns for k in slots) or any(b <= a for a, b in zip(slots, slots[1:])):
+        raise ValueError(f"the slots {slots} are not strictly increasing indices into {ns} log-variances")
+    if record is None:
+        record = torch.zeros((2 * BALANCE_MAX_TERMS,), device=log_vars.device, dtype=F32)
+    return BalancedLossSum.apply((tuple(w), tuple(gw), tuple(grp), slots, loss_balance_clamp(clamp), log_vars, grad_out, record), *xs)
+
+
 __all__ = [n for n in dir() if not n.startswith("__")]      # everything, incl. single-underscore helpers: the package is one namespace

@@ -62,6 +62,56 @@ def accum_options(train_cfg: dict, hip_adam: bool) -> int:
     return k
 
 
+def loss_balance_options(train_cfg: dict, hip_adam: bool):
+    """cfgs["train"]["loss_balance"] -> None (absent or "none": the static weights alone) or dict(lr, init, clamp) for "uncertainty":
+    learned homoscedastic-uncertainty weights.  loss_balance_lr (default train.lr; constant, not under the cosine schedule)
+    > 0, loss_balance_clamp (default 6.0) in (0, 80], |loss_balance_init| (default 0.0) <= the clamp.  The log-variances are stepped
+    by the HIP Adam, so it needs hip_adam=True.  Anything else raises ValueError."""
+    mode = train_cfg.get("loss_balance")
+    if mode is None or mode == "none":
+        return None
+    if mode != "uncertainty":
+        raise ValueError("train.loss_balance is 'uncertainty' or 'none', not %r" % (mode,))
+    if not hip_adam:
+        raise ValueError("train.loss_balance steps the log-variances with the HIP Adam: it needs hip_adam=True")
+
+    def number(key, default):
+        v = train_cfg.get(key, default)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or abs(v) == float("inf"):
+            raise ValueError("train.%s is a finite number, not %r" % (key, v))
+        return float(v)
+    lr, init, clamp = number("loss_balance_lr", train_cfg["lr"]), number("loss_balance_init", 0.0), number("loss_balance_clamp", 6.0)
+    if not lr > 0.0:
+        raise ValueError("train.loss_balance_lr is > 0, not %r" % (lr,))
+    if not 0.0 < clamp <= 80.0:
+        raise ValueError("train.loss_balance_clamp lies in (0, 80], not %r" % (clamp,))
+    if abs(init) > clamp:
+        raise ValueError("train.loss_balance_init = %r lies outside the clamp +-%r" % (init, clamp))
+    return dict(lr=lr, init=init, clamp=clamp)
+
+
+class _BalanceGrads:
+    """Adam.step(grads=) for the log-variances under train.accum_steps: the accumulator's mean of d total / d s (the first half of its
+    view for the gradient-and-activity vector)"""
+
+    def __init__(self, acc, key, s):
+        self.acc, self.key, self.s, self._ds = acc, key, s, None
+
+    @property
+    def pending(self):
+        return self.acc.pending
+
+    def grad(self, p):
+        if p is not self.s:
+            return None
+        if self._ds is None:
+            self._ds = self.acc.grad(self.key)[:self.s.numel()]       # (one object: Adam's fast path compares gradients by identity)
+        return self._ds
+
+    def activity(self):
+        return self.acc.grad(self.key)[self.s.numel():]
+
+
 def optimizer_steps_per_epoch(n_iter: int, k: int) -> int:
     """optimizer steps of an epoch of n_iter loader batches with k micro-batches per step: ceil(n_iter / k) -- a trailing partial group
     is stepped at the epoch's end (HydraTrainer.flush_accumulated)"""
@@ -135,7 +185,15 @@ class HydraTrainer:
         micro-batch (and are snapshotted once per group: a skipped group restores what they were before its first micro-batch).
         Data parallel: nothing in the reducer changes -- every micro-batch's backward is a complete exchange and the accumulator reads
         the exchanged gradients (the mean of the averages is the average of the means), which is k times the traffic of exchanging
-        once per group; that form is not built."""
+        once per group; that form is not built.
+        cfgs["train"]["loss_balance"] = "uncertainty" (absent or "none": off; hip_adam only) / ["loss_balance_lr"] /
+        ["loss_balance_init"] / ["loss_balance_clamp"]: one learned log-variance per loss term weighs the six terms next to the static
+        weights (HydraNet.enable_loss_balance; hn_balanced_sum in place of hn_weighted_sum).  The six scalars are one plain device
+        tensor, stepped by a second, one-tensor HIP Adam (`balance_optimizer`: no weight decay, a constant learning rate of its own)
+        right after the weights' step and under the same decision: a step the guard skips leaves them and their moments untouched,
+        under accum_steps they step once per group on the mean of the group's gradients; they take no part in the clipping norm or the
+        weight average.  A term whose loss was exactly 0 in the step (a task without a labelled image, a head-only phase's other
+        terms) keeps its log-variance and both moments to the bit."""
         self.cfgs = cfgs
         self.capture_step = capture_step
         self._cap = None                       # (shape key, graph, static batch, static loss dict)
@@ -159,6 +217,8 @@ class HydraTrainer:
         self.protect_bn_stats, self.ema_buffers = bn_state_options(t, hip_adam)
         self.buffer_keeper = None              # bn_state.BufferKeeper, built at the first training step when either key is on
         self.accum_steps = accum_options(t, hip_adam)
+        self.loss_balance = loss_balance_options(t, hip_adam)      # None, or dict(lr, init, clamp) of train.loss_balance: uncertainty
+        self.balance_optimizer = None          # the log-variances' own optim.Adam
         self.accumulator = None                # optim.GradAccumulator when train.accum_steps > 1
         self._packer = None                    # checkpoint.StatePacker of save_state / load_state, rebuilt when the set of state tensors changes
         self._ckpt_thread = None               # the background writer of save_state(wait=False)
@@ -218,8 +278,13 @@ class HydraTrainer:
         else:
             self.optimizer = torch.optim.Adam(self.hydranet.parameters(), self.lr, weight_decay=self.weight_decay)
         self._guarded = self.grad_clip_norm is not None or self.skip_nonfinite
+        extra = []
+        if self.loss_balance is not None:
+            extra = [self._enable_loss_balance()]
         if self.accum_steps > 1:
-            self.accumulator = GradAccumulator(self.hydranet.parameters())
+            self.accumulator = GradAccumulator(list(self.hydranet.parameters()) + extra)
+            if extra:
+                self._balance_grads = _BalanceGrads(self.accumulator, extra[0], self.hydranet.loss_log_vars)
         if self.skip_nonfinite:
             # the device guard replaces the reference's host guard (HydraNet._guard: seven synchronising reads of device scalars per step,
             # sys.exit() on the first bad batch): a non-finite step is skipped, and only a whole print interval of them ends the run
@@ -245,8 +310,11 @@ class HydraTrainer:
         else:
             prefix = {"lane": "laneheader.", "det": "detectheader.", "seg": "segheader."}[phase]
             named = [(n, p) for n, p in self.hydranet.named_parameters() if n.startswith(prefix)]
-        return GradReducer(named, world_size=self.world, skip=unused_parameters(self.hydranet), payload_dtype=self._grad_payload,
-                           force_collectives=self._force_distribute)
+        red = GradReducer(named, world_size=self.world, skip=unused_parameters(self.hydranet), payload_dtype=self._grad_payload,
+                          force_collectives=self._force_distribute)
+        if getattr(self, "balance_optimizer", None) is not None:
+            red.extras.append(self.hydranet.loss_balance_grad_act)      # d total / d s and the activity: the ranks' mean, so they cannot drift
+        return red
 
     def set_phase(self, phase: str):
         """One branch of main()'s schedule (train.py:462-505): the optimizer's first param group holds the parameters of the whole model
@@ -276,6 +344,47 @@ class HydraTrainer:
         self.phase = phase
         self.hydranet.grad_scope = None if phase == "joint" else phase
 
+    def _enable_loss_balance(self):
+        """train.loss_balance: the model's log-variances, their one-tensor Adam with its state (allocated now: a state file lists the
+        same tensors before and after the first step) and the hold buffer of _balance_step -> the tensor that stands for the
+        gradient-and-activity vector in a GradAccumulator (its .grad is that vector; its own values are never read)"""
+        b, net = self.loss_balance, self.hydranet
+        net.enable_loss_balance(b["clamp"], b["init"])
+        s = net.loss_log_vars
+        s._hn_mut_cell = [0]                   # (a cell of its own: stepping it leaves every eval-mode cache of the weights alone)
+        s.grad = net.loss_log_vars_grad        # written by every backward of total_loss: never accumulated into, never zeroed
+        opt = self.balance_optimizer = Adam([s], b["lr"], weight_decay=0.0, skip_nonfinite=self.skip_nonfinite)
+        opt.state[s] = dict(step=torch.zeros((), dtype=torch.float32), exp_avg=torch.zeros_like(s), exp_avg_sq=torch.zeros_like(s))
+        self._balance_hold = torch.zeros((3 * s.numel(),), device=self.device, dtype=torch.float32)
+        self._balance_grads = None
+        for red in self._reducers.values():
+            red.extras.append(net.loss_balance_grad_act)
+        key = torch.zeros_like(net.loss_balance_grad_act)
+        key.grad = net.loss_balance_grad_act
+        return key
+
+    def _balance_step(self, accumulated: bool = False):
+        """the log-variances' Adam step, right after the weights': the guard's skip word of the weights' step decides for it too
+        (train.skip_nonfinite), and hn_balance_hold around it gives every slot without an active term in this step (or group) its
+        value and moments back.  Three small launches (and the guard's three with train.skip_nonfinite); none without train.loss_balance."""
+        opt = self.balance_optimizer
+        if opt is None:
+            return
+        from ._lib import lib
+        net = self.hydranet
+        s = net.loss_log_vars
+        st, n = opt.state[s], s.numel()
+        tensors = (s.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), self._balance_hold.data_ptr())
+        lib().call("hn_balance_hold", *tensors, None, n)
+        kw = dict(guard_words=[self.optimizer.guard_record[2:3]]) if self.skip_nonfinite else {}
+        if accumulated:
+            opt.step(grads=self._balance_grads, **kw)
+            act = self._balance_grads.activity()
+        else:
+            opt.step(**kw)
+            act = net.loss_balance_grad_act[n:]
+        lib().call("hn_balance_hold", *tensors, act.data_ptr(), n)
+
     def _optimizer_step(self, total_loss: torch.Tensor):
         """Adam step; with train.skip_nonfinite the guard also sees the total loss and the persistent stage kernels' status word (a replayed
         step whose persistent launch expired must not reach Adam).  With more than one rank only the exchanged gradients are identical
@@ -293,6 +402,7 @@ class HydraTrainer:
         acc = self.accumulator
         if acc is None:
             self._optimizer_step(loss_dict["total_loss"])
+            self._balance_step()
             if keeper is not None:
                 keeper.settle(self.optimizer.guard_record)          # a skipped step: the statistics back; a taken one: their average
             self.scheduler.step()
@@ -313,6 +423,7 @@ class HydraTrainer:
             self.optimizer.step(grads=acc, losses=[acc.loss_means()[-1:]], guard_words=[K_xstage_status_word(self.device), acc.sticky_word])
         else:
             self.optimizer.step(grads=acc)
+        self._balance_step(accumulated=True)
         if self.buffer_keeper is not None:
             self.buffer_keeper.settle(self.optimizer.guard_record)
         self.scheduler.step()
@@ -537,6 +648,21 @@ class HydraTrainer:
         print("%s Epoch [%i|%i] Iter [%i] Lr %.5f  " % (mode.upper(), epoch, self.epoch, batch_idx, lr) +
               "  ".join("%s %.3f" % (k, float(v.detach())) for k, v in loss_dict.items()) +
               ("" if guard is None else "  grad_norm %.3f  coef %.3f  skipped %i" % (guard["norm"], guard["coef"], guard["skipped"])))
+        if mode == "train" and self.balance_optimizer is not None:
+            print(self.loss_balance_line())
+
+    def loss_balance_line(self) -> str:
+        """the print interval's line under train.loss_balance: per term its log-variance s, exp(-s) and exp(-s) x its static weights
+        (term weight x group weight).  One read of the model's record, after the reads the loss line has just made."""
+        c = self.cfgs
+        static = dict(loss_seg=c["segment"]["segment_weight"],
+                      loss_det_cls=c["detection"]["loss_cls_weight"] * c["detection"]["detection_weight"],
+                      loss_det_reg=c["detection"]["loss_reg_weight"] * c["detection"]["detection_weight"],
+                      loss_lane_cls_pos=c["lane"]["loss_cls_pos_weight"] * c["lane"]["lane_weight"],
+                      loss_lane_cls_neg=c["lane"]["loss_cls_neg_weight"] * c["lane"]["lane_weight"],
+                      loss_lane_loc=c["lane"]["loss_loc_weight"] * c["lane"]["lane_weight"])
+        return "      balance (s, exp(-s), x static)  " + "  ".join(
+            "%s %.3f %.3f %.4g%s" % (k[5:], s, e, e * static[k], "" if on else " (inactive)") for k, (s, e, on) in self.hydranet.loss_balance.items())
 
     def valid(self, epoch: int = 0, eval_dir: Optional[str] = None, lane_coder=None, det_conf_thres: float = 0.3, det_iou_thres: float = 0.3,
               coco_gt=None, use_ema: Optional[bool] = None):
@@ -668,9 +794,12 @@ class HydraTrainer:
 
     def _state_keys(self) -> dict:
         """the train keys that shape the state, as this trainer resolved them: a state file loads only where they agree"""
-        return dict(grad_clip_norm=self.grad_clip_norm, skip_nonfinite=self.skip_nonfinite, ema_decay=self.ema_decay,
+        keys = dict(grad_clip_norm=self.grad_clip_norm, skip_nonfinite=self.skip_nonfinite, ema_decay=self.ema_decay,
                     ema_warmup=self.ema_warmup if self.ema_decay is not None else None, protect_bn_stats=self.protect_bn_stats,
                     ema_buffers=self.ema_buffers, accum_steps=self.accum_steps)
+        if self.loss_balance is not None:       # (only when on: a file written without it keeps exactly its manifest)
+            keys["loss_balance"] = "uncertainty"
+        return keys
 
     def _state_tensors(self):
         """[(name, tensor)] of everything that travels in a state file's blob, in a fixed order: the model's parameters and persistent
@@ -687,6 +816,10 @@ class HydraTrainer:
             named.append(("guard/record", opt.guard_record))
         if self.buffer_keeper is not None and self.buffer_keeper.avg is not None:
             named += [("keeper/avg/" + n, a) for n, a in zip(self.buffer_keeper.names, self.buffer_keeper.avg)]
+        if self.balance_optimizer is not None:
+            s = self.hydranet.loss_log_vars
+            st = self.balance_optimizer.state[s]
+            named += [("balance/log_vars", s), ("balance/exp_avg", st["exp_avg"]), ("balance/exp_avg_sq", st["exp_avg_sq"])]
         return named
 
     def _state_packer(self):
@@ -707,9 +840,12 @@ class HydraTrainer:
             if st:
                 per[n] = dict(step=int(st["step"]), **({"ema_start": int(st["ema_start"])} if "ema_start" in st else {}))
         groups = [{k: (list(v) if isinstance(v, tuple) else v) for k, v in g.items() if k != "params"} for g in opt.param_groups]
-        return dict(epoch=int(epoch), phase=self.phase, train=self._state_keys(), params=per, param_groups=groups,
+        host = dict(epoch=int(epoch), phase=self.phase, train=self._state_keys(), params=per, param_groups=groups,
                     scheduler=self.scheduler.state_dict(), settles=None if self.buffer_keeper is None else int(self.buffer_keeper.settles),
                     world=self.world)
+        if self.balance_optimizer is not None:
+            host["balance_step"] = int(self.balance_optimizer.state[self.hydranet.loss_log_vars]["step"])
+        return host
 
     def checkpoint_wait(self):
         """join a save_state(wait=False) in flight (a no-op without one); an error of the background writer is raised here"""
@@ -787,9 +923,11 @@ class HydraTrainer:
         except (KeyError, TypeError, ValueError) as e:
             raise ValueError("%s: the manifest lacks host-side state (%s)" % (path, e))
         mine = self._state_keys()
-        for k in self.STATE_KEYS:
-            if theirs.get(k) != mine[k]:
-                raise ValueError("%s was saved with train.%s = %r, this trainer has %r" % (path, k, theirs.get(k), mine[k]))
+        for k in self.STATE_KEYS + ("loss_balance",):
+            if theirs.get(k) != mine.get(k):
+                raise ValueError("%s was saved with train.%s = %r, this trainer has %r" % (path, k, theirs.get(k), mine.get(k)))
+        if self.balance_optimizer is not None and not isinstance(host.get("balance_step"), int):
+            raise ValueError("%s: the manifest lacks the log-variances' step count" % path)
         if phase not in PHASES or self._phase_module(phase) is None or len(groups) != len(opt.param_groups):
             raise ValueError("%s: phase %r / %i param groups do not fit this trainer" % (path, phase, len(groups)))
         params = dict(net.named_parameters())
@@ -807,6 +945,8 @@ class HydraTrainer:
         if self.ema_buffers and settles is not None:
             from .bn_state import SUFFIXES
             want += [("keeper/avg/" + n, b) for n, b in net.named_buffers() if n.endswith(SUFFIXES)]
+        if self.balance_optimizer is not None:
+            want += [("balance/" + k, net.loss_log_vars) for k in ("log_vars", "exp_avg", "exp_avg_sq")]
         ents = manifest["tensors"]
         for i in range(max(len(ents), len(want))):
             if i >= len(ents) or i >= len(want):
@@ -883,6 +1023,12 @@ class HydraTrainer:
         opt._fast.clear()
         opt._guard_plan = None
         opt._swap_plan = None
+        if self.balance_optimizer is not None:
+            bo = self.balance_optimizer
+            bo.state[net.loss_log_vars]["step"] = torch.full((), float(host["balance_step"]), dtype=torch.float32)
+            bo._plans.clear()
+            bo._fast.clear()
+            bo._guard_plan = None
         self.scheduler.load_state_dict(sched)
         for g, saved in zip(opt.param_groups, groups):
             g.update({k: (tuple(v) if k == "betas" else v) for k, v in saved.items()})
